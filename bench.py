@@ -16,6 +16,10 @@ frames per GPU, 64 left + 64 right coloured cones (the FSG recording itself is a
 Frames are independent, so ranks shard them with no data-path collective; RCCL carries only the start-up broadcast /
 check of the constant previous-path table, the timing barrier and the max-reduction of the elapsed time.
 
+A plain run sets up, warms up, times the K steps and prints the headline.  ``--full`` adds every other figure of the line
+(per-kernel times from untimed repeats, streaming, MultiPlanner, golden flip count, single-frame latency, chip time, CPU
+baseline, skidpad).  ``--dump-outputs DIR`` writes the result records of the last timed step as DIR/<field>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -53,7 +57,8 @@ PASS_OVERLAP = 20  # passes in flight in the timed region (fsdp_set_overlap).  R
 # 5.4 / 6.1-6.2 M with ten; 24 or more passes collapse (0.7-3.6 M).  22 queues, not 32: the queues of all processes on a GPU add up,
 # and a second process next to 24+ of them crawls (the skidpad child of this script: 5.3 -> 0.5 M; it gets 8 of its own).
 STREAM_DEPTH = 20  # pass slots of the host -> host streaming leg (two tickets queue on each; profiles/r06_streaming_probe.txt)
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X spec: 8 TB/s
+DUMP_BYTES = 60 << 20  # --dump-outputs: array bytes in all (a fixed sample of frames beyond it), under 64 MB with the .npy headers
 
 
 def usable_cores() -> int:
@@ -428,6 +433,20 @@ def golden_flip_count(pkg, ctx):
         return {"error": repr(e)}
 
 
+def dump_outputs(res: np.ndarray, out_dir: Path, seed: int = 0) -> None:
+    """--dump-outputs: the result records of the last timed step (what fsdp_download hands the caller of the resident path), one
+    float64 array per record field as out_dir/<field>.npy, frames first (the integer fields are exact in float64).  Beyond
+    DUMP_BYTES in all, a fixed seeded sample of frames in ascending order; frame_index.npy names the frames written."""
+    per_frame = 8 * (1 + sum(int(np.prod(res.dtype[f].shape, dtype=np.int64)) for f in res.dtype.names))
+    idx = np.arange(len(res))
+    if len(res) * per_frame > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(len(res), DUMP_BYTES // per_frame, replace=False))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "frame_index.npy", idx.astype(np.float64))
+    for f in res.dtype.names:
+        np.save(out_dir / f"{f}.npy", res[f][idx].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -450,7 +469,15 @@ def main():
     ap.add_argument("--allow-tcp-fallback", action="store_true",
                     help="N > 1 ranks: accept a run whose start-up collectives went over the TCP star because RCCL did not come up on "
                          "every rank (the line then says communicator: tcp-fallback); without it such a run exits with status 3")
+    ap.add_argument("--full", action="store_true",
+                    help="every figure of the line besides the headline: per-kernel times (untimed repeats), streaming, MultiPlanner, "
+                         "golden flip count, single-frame latency, chip time, CPU baseline, skidpad (the --no-* options and "
+                         "--stream-batches select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the result records of the last timed step (rank 0's frames) as DIR/<field>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if os.environ.get("FSDP_HANG_DUMP"):  # diagnostics: Python stacks of all threads after N seconds, then exit
         import faulthandler
 
@@ -543,7 +570,7 @@ def main():
     # In the timed region HIP events bracket the launches of the path stage's main kernel (fit_kernel: the dominant kernel,
     # the one the roofline object is about) of every pass, on the stream the kernel runs on.  Events around all seven
     # launches of a pass cost about 3 % of the throughput (an event record is a packet in the stream's queue): the other
-    # kernels' overlapped durations come from a second, untimed run of the same `steps` passes right after the clock stops.
+    # kernels' overlapped durations come from a second, untimed run of the same `steps` passes right after the clock stops (--full).
     ctx.time_detail(False)
     ctx.sync()
     d.barrier()
@@ -561,33 +588,47 @@ def main():
     ev_total_ms, ev_main_ms = ctx.time_results()
     names = ctx.stage_names()
     main_ms = [x / args.steps for x in ev_main_ms]  # non-zero for the bracketed kernel only
-    ctx.time_detail(True, kernel_clock=True)
-    _, ev_stage_ms = ctx.time_runs(args.steps)      # untimed: every kernel bracketed, same passes in flight
-    stage_ms = [x / args.steps for x in ev_stage_ms]
-    # the refit kernel by its own clock (first wavefront's start to last wavefront's end of every launch) — taken in this
-    # untimed repeat: the readings are two atomics per workgroup, and the timed region runs the production launches without them
-    kclock_ms, kclock_n = ctx.time_kernel_clock()
-    ctx.time_detail(True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx.download(), Path(args.dump_outputs))  # the most recent pass = the last timed step
+    stage_ms = main_ms
+    if args.full:
+        ctx.time_detail(True, kernel_clock=True)
+        _, ev_stage_ms = ctx.time_runs(args.steps)      # untimed: every kernel bracketed, same passes in flight
+        stage_ms = [x / args.steps for x in ev_stage_ms]
+        # the refit kernel by its own clock (first wavefront's start to last wavefront's end of every launch) — taken in this
+        # untimed repeat: the readings are two atomics per workgroup, and the timed region runs the production launches without them
+        kclock_ms, kclock_n = ctx.time_kernel_clock()
+        ctx.time_detail(True)
 
-    # for reference: the same kernels one pass after the other (no overlap) — per-launch durations without chip sharing
-    ctx.set_overlap(1)
-    n_ser = max(3, min(args.steps, 10))
-    ser_total_ms, ser_stage_ms = ctx.time_runs(n_ser)
-    names_serial = ctx.stage_names()
-    serial_ms = [x / n_ser for x in ser_stage_ms]
-    res = ctx.download()
-    status_hist = {int(k): int(v) for k, v in zip(*np.unique(res["status"], return_counts=True))}
-    arc_frames = int(((res["path_fallback"] & 16) != 0).sum())
+        # for reference: the same kernels one pass after the other (no overlap) — per-launch durations without chip sharing
+        ctx.set_overlap(1)
+        n_ser = max(3, min(args.steps, 10))
+        ser_total_ms, ser_stage_ms = ctx.time_runs(n_ser)
+        names_serial = ctx.stage_names()
+        serial_ms = [x / n_ser for x in ser_stage_ms]
+        res = ctx.download()
+        status_hist = {int(k): int(v) for k, v in zip(*np.unique(res["status"], return_counts=True))}
+        arc_frames = int(((res["path_fallback"] & 16) != 0).sum())
 
     if rank == 0:
         value = frames_global * args.steps / elapsed
+        # a plain run knows only the kernel bracketed in the timed region; --full takes the dominant kernel from the repeat
         dom = int(np.argmax(stage_ms))
         # the kernel bracketed in the timed region (fit_kernel) is the dominant one on the bench workload; where another
         # kernel takes longer per launch (config 4: the sorting kernel over 200 cones), its duration comes from the repeat
         dom_ms = main_ms[dom] if main_ms[dom] > 0 else stage_ms[dom]
-        achieved = algo_bytes * n_local / (dom_ms * 1e-3) / 1e9
-        pmc = _pmc(pkg)
-        pk = (pmc or {}).get(names[dom], {})
+        achieved = algo_bytes * n_local / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else None  # (no bracketed launch ran)
+        roofline = {
+            "bound": "hbm",
+            "kernel": names[dom],
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS if achieved else None,
+            "basis": "average duration of the dominant kernel's launches inside the timed region (twenty passes in flight share the chip)",
+            "kernel_ms_timed_region": main_ms[dom] if main_ms[dom] > 0 else None,
+            "kernel_bracketed_in_timed_region": names[int(np.argmax(main_ms))],
+        }
         out = {
             "metric": "PathPlanner frames/s at 128 cones/frame" if args.config == 2 else "PathPlanner frames/s at 200 cones/frame (config 4)",
             "value": value,
@@ -615,17 +656,14 @@ def main():
                 "rccl_ranks": int(getattr(d, "rccl_ranks", 0)),
                 "pass_overlap": overlap,
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": names[dom],
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
+            "roofline": roofline,
+            "lib_sha256_16": _lib_hash(pkg),
+        }
+        if args.full:
+            pmc = _pmc(pkg)
+            pk = (pmc or {}).get(names[dom], {})
+            roofline.update({
                 "traffic": pk.get("hbm_bytes_per_launch", 0) / 1e9 if pk.get("hbm_bytes_per_launch") else None,
-                "basis": "average duration of the dominant kernel's launches inside the timed region (twenty passes in flight share the chip)",
-                "kernel_ms_timed_region": main_ms[dom] if main_ms[dom] > 0 else None,
-                "kernel_bracketed_in_timed_region": names[int(np.argmax(main_ms))],
                 # the same launches by the kernel's own clock readings (s_memrealtime: first wavefront's start to last
                 # wavefront's end = what a kernel trace calls the duration).  The event bracket above starts when the previous
                 # kernel of the stream ends, so it also holds the time the launch waits in its hardware queue — with twenty
@@ -654,53 +692,51 @@ def main():
                         "runs on; passes overlap, so a launch shares the chip with the other streams' kernels — kernel_ms = "
                         "every kernel bracketed, same passes repeated after the clock stopped; kernel_ms_serial = the same "
                         "launches alone); the path is FP64-issue/latency bound (serial spline QR), not HBM bound",
-            },
-            "status_histogram": status_hist,
-            "arc_extension_frames": arc_frames,
-            "lib_sha256_16": _lib_hash(pkg),
-        }
-        if args.config == 2 and args.stream_batches > 0:
-            out["streaming"] = streaming_leg(pkg, ctx, n_local, min(overlap, STREAM_DEPTH), args.stream_batches, d.shard_seed(args.seed))
-        if args.config == 2 and args.stream_batches > 0 and (world == 1 or single):
-            # multi.MultiPlanner from this one process: on every GPU of a --single-process run, else four contexts on the one GPU
-            if not single:
-                ctx.set_overlap(1)  # (gives the twenty slots' streams back: hardware queues are shared by every context on the GPU)
-            devs = d.devices if single else [ctx.device or 0] * 4
-            nb = max(4, args.stream_batches // (1 if single else len(devs)))
-            out["multi_planner_stream"] = multi_planner_leg(pkg, devs, n_local, 3, nb, d.shard_seed(args.seed),
-                                                            (out.get("streaming") or {}).get("value"))
-        if world == 1 and not args.no_latency:
-            # sample-count flips against the reference, measured on the committed golden fuzz set
-            out["flip_count"] = golden_flip_count(pkg, ctx)
-            # BASELINE metric, second half: p50 single-frame latency (batch = 1, host buffers, PCIe-inclusive)
-            o1, c1, p1 = off[:2], cones[: off[1]], poses[:1]
-            lat = []
-            for _ in range(300):
-                t1 = time.perf_counter()
-                ctx.plan_batch(o1, c1, p1)
-                lat.append(time.perf_counter() - t1)
-            out["p50_single_frame_us"] = float(np.median(lat[50:]) * 1e6)
-            # the reproducible per-kernel figure next to roofline.kernel_ms (round-4 review, weak #11)
-            out["roofline"].update(chip_time_leg())
-            chip = (out["roofline"].get("chip_ns_per_frame") or {}).get(names[dom])
-            if chip:
-                # The line's achieved / frac: the dominant kernel ALONE on a chip it fills (one launch of 98 304 frames, HIP events
-                # around it on its stream, measured by a child of this run) — a property of the kernel, reproducible from profiles/
-                # (r06_batch_sweep_packed_kernels.jsonl, r06_chip_time_rocprofv3_summary.txt).  The duration of one of twenty
-                # overlapped launches (..._timed_region below) is a property of how twenty streams interleave on the box at hand.
-                rf = out["roofline"]
-                rf["achieved_timed_region"], rf["frac_timed_region"] = rf["achieved"], rf["frac"]
-                rf["achieved"] = algo_bytes / chip  # bytes per ns = GB/s
-                rf["frac"] = rf["achieved"] / HBM_PEAK_GBS
-                rf["basis"] = (f"{algo_bytes} algorithmic bytes per frame / {chip:.1f} ns of chip time per frame of {names[dom]} "
-                               "(chip_ns_per_frame: the kernel alone, 98 304 frames per launch)")
-            if not args.no_cpu_baseline:
-                out["cpu_baseline"] = cpu_baseline(off, cones, poses)
-                out["p50_single_frame_vs_cpu_1thread"] = out["p50_single_frame_us"] / out["cpu_baseline"]["single_thread_us_per_frame"]
-            # BASELINE configs[4] next to the headline: 1024 stateful skidpad planners over the recording, host to host (a
-            # process of its own: tools/bench_skidpad.py; its own context on the same GPU, after everything timed above)
-            if not args.no_skidpad:
-                out["skidpad_config5"] = skidpad_leg()
+            })
+            out["status_histogram"] = status_hist
+            out["arc_extension_frames"] = arc_frames
+            if args.config == 2 and args.stream_batches > 0:
+                out["streaming"] = streaming_leg(pkg, ctx, n_local, min(overlap, STREAM_DEPTH), args.stream_batches, d.shard_seed(args.seed))
+            if args.config == 2 and args.stream_batches > 0 and (world == 1 or single):
+                # multi.MultiPlanner from this one process: on every GPU of a --single-process run, else four contexts on the one GPU
+                if not single:
+                    ctx.set_overlap(1)  # (gives the twenty slots' streams back: hardware queues are shared by every context on the GPU)
+                devs = d.devices if single else [ctx.device or 0] * 4
+                nb = max(4, args.stream_batches // (1 if single else len(devs)))
+                out["multi_planner_stream"] = multi_planner_leg(pkg, devs, n_local, 3, nb, d.shard_seed(args.seed),
+                                                                (out.get("streaming") or {}).get("value"))
+            if world == 1 and not args.no_latency:
+                # sample-count flips against the reference, measured on the committed golden fuzz set
+                out["flip_count"] = golden_flip_count(pkg, ctx)
+                # BASELINE metric, second half: p50 single-frame latency (batch = 1, host buffers, PCIe-inclusive)
+                o1, c1, p1 = off[:2], cones[: off[1]], poses[:1]
+                lat = []
+                for _ in range(300):
+                    t1 = time.perf_counter()
+                    ctx.plan_batch(o1, c1, p1)
+                    lat.append(time.perf_counter() - t1)
+                out["p50_single_frame_us"] = float(np.median(lat[50:]) * 1e6)
+                # the reproducible per-kernel figure next to roofline.kernel_ms (round-4 review, weak #11)
+                out["roofline"].update(chip_time_leg())
+                chip = (out["roofline"].get("chip_ns_per_frame") or {}).get(names[dom])
+                if chip:
+                    # The line's achieved / frac: the dominant kernel ALONE on a chip it fills (one launch of 98 304 frames, HIP events
+                    # around it on its stream, measured by a child of this run) — a property of the kernel, reproducible from profiles/
+                    # (r06_batch_sweep_packed_kernels.jsonl, r06_chip_time_rocprofv3_summary.txt).  The duration of one of twenty
+                    # overlapped launches (..._timed_region below) is a property of how twenty streams interleave on the box at hand.
+                    rf = out["roofline"]
+                    rf["achieved_timed_region"], rf["frac_timed_region"] = rf["achieved"], rf["frac"]
+                    rf["achieved"] = algo_bytes / chip  # bytes per ns = GB/s
+                    rf["frac"] = rf["achieved"] / HBM_PEAK_GBS
+                    rf["basis"] = (f"{algo_bytes} algorithmic bytes per frame / {chip:.1f} ns of chip time per frame of {names[dom]} "
+                                   "(chip_ns_per_frame: the kernel alone, 98 304 frames per launch)")
+                if not args.no_cpu_baseline:
+                    out["cpu_baseline"] = cpu_baseline(off, cones, poses)
+                    out["p50_single_frame_vs_cpu_1thread"] = out["p50_single_frame_us"] / out["cpu_baseline"]["single_thread_us_per_frame"]
+                # BASELINE configs[4] next to the headline: 1024 stateful skidpad planners over the recording, host to host (a
+                # process of its own: tools/bench_skidpad.py; its own context on the same GPU, after everything timed above)
+                if not args.no_skidpad:
+                    out["skidpad_config5"] = skidpad_leg()
         print(json.dumps(out), flush=True)
     # The line is out.  Tear-down (last barrier, ncclCommDestroy, hipHostFree of ~1 GB of page-locked buffers, the HIP
     # runtime's own exit handlers) has nothing left to report, and a benchmark process that hangs on its way out after a

@@ -22,16 +22,16 @@ if has profile; then
   python tools/kernel_stats.py gpurun_out/prof_r06/chip "FSDP_PACK=1 python tools/batch_sweep.py 98304 (one pass at a time over a resident 98 304-frame batch: 12 launches per kernel)" > $R/chip_time_rocprofv3_summary.txt 2>&1
 fi
 if has bench; then
-  $T python bench.py --steps 20 --warmup 3 2>$R/bench.err | tail -1 > $R/bench_line.json
-  $T python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-latency 2>/dev/null | tail -1 > $R/bench_line_100steps.json
-  $T python bench.py --config 4 --frames 8192 --no-cpu-baseline --no-latency 2>/dev/null | tail -1 > $R/bench_cfg4_shard.json
-  FSDP_FORCE_DIST=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 2>/dev/null | grep '^{' | tail -1 > $R/bench_line_torchrun_rccl_1rank.json
+  $T python bench.py --full --steps 20 --warmup 3 2>$R/bench.err | tail -1 > $R/bench_line.json
+  $T python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-latency 2>/dev/null | tail -1 > $R/bench_line_100steps.json
+  $T python bench.py --full --config 4 --frames 8192 --no-cpu-baseline --no-latency 2>/dev/null | tail -1 > $R/bench_cfg4_shard.json
+  FSDP_FORCE_DIST=1 $T python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 2>/dev/null | grep '^{' | tail -1 > $R/bench_line_torchrun_rccl_1rank.json
   # two ranks on the one GPU: RCCL cannot come up, the ranks agree on the TCP star.  Without --allow-tcp-fallback that is exit status 3
-  FSDP_SHARE_GPU=1 FSDP_RCCL_INIT_TIMEOUT=40 $T python bench.py --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 > $R/bench_2ranks_refused.out 2>$R/bench_2ranks_refused.err
+  FSDP_SHARE_GPU=1 FSDP_RCCL_INIT_TIMEOUT=40 $T python bench.py --full --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 > $R/bench_2ranks_refused.out 2>$R/bench_2ranks_refused.err
   echo "exit status without --allow-tcp-fallback: $?" > $R/bench_2ranks_exit_status.txt
-  FSDP_SHARE_GPU=1 FSDP_RCCL_INIT_TIMEOUT=40 $T python bench.py --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 --allow-tcp-fallback 2>$R/bench_2ranks.err | grep '^{' | tail -1 > $R/bench_line_2ranks_one_gpu_tcp_fallback.json
+  FSDP_SHARE_GPU=1 FSDP_RCCL_INIT_TIMEOUT=40 $T python bench.py --full --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 --allow-tcp-fallback 2>$R/bench_2ranks.err | grep '^{' | tail -1 > $R/bench_line_2ranks_one_gpu_tcp_fallback.json
   echo "exit status with --allow-tcp-fallback: ${PIPESTATUS[0]}" >> $R/bench_2ranks_exit_status.txt
-  FSDP_SHARE_GPU=1 $T python bench.py --gpus 2 --single-process --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 2>$R/bench_single_process.err | grep '^{' | tail -1 > $R/bench_line_2contexts_one_process.json
+  FSDP_SHARE_GPU=1 $T python bench.py --full --gpus 2 --single-process --steps 20 --warmup 3 --no-cpu-baseline --no-latency --stream-batches 0 2>$R/bench_single_process.err | grep '^{' | tail -1 > $R/bench_line_2contexts_one_process.json
   $T python tools/bench_configs.py > $R/bench_configs.jsonl 2>&1
   $T python tools/batch_sweep.py 1024 2048 4096 8192 16384 32768 65536 98304 > $R/batch_sweep.jsonl 2>&1
   FSDP_PACK=1 $T python tools/batch_sweep.py 2048 4096 8192 16384 32768 98304 > $R/batch_sweep_packed_kernels.jsonl 2>&1

@@ -35,7 +35,7 @@ def short(name):
 
 
 durations = {}
-for sub, label in (("trace", "python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-latency  [passes overlapped, as the bench runs: 5 warm-up + 5 priming passes, the 20 timed passes, their 20-pass repeat with every kernel bracketed, 10 passes one at a time]"),
+for sub, label in (("trace", "python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-latency  [passes overlapped, as the bench runs: 5 warm-up + 5 priming passes, the 20 timed passes, their 20-pass repeat with every kernel bracketed, 10 passes one at a time]"),
                    ("trace_serial", "same command with --no-overlap  [one pass after the other]")):
     con = db(sub)
     print(f"== rocprofv3 --kernel-trace --stats ({label}) ==")

@@ -2,8 +2,8 @@
 """Kernel timeline of one bench run from a rocprofv3 --kernel-trace database (rocpd sqlite): per dispatch the stream /
 queue, start and end relative to the first dispatch of the timed region, and the number of kernels running at every
 start.  Run on the GPU box:
-  rocprofv3 --kernel-trace -d gpurun_out/tl -o tl -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-latency
-  python tools/timeline.py gpurun_out/tl [first_n]"""
+  rocprofv3 --kernel-trace -d OUT_DIR -o tl -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-latency
+  python tools/timeline.py OUT_DIR [first_n]"""
 import glob
 import re
 import sqlite3
