@@ -142,7 +142,8 @@ def make_params(overrides=None) -> Params:
     for k, v in (overrides or {}).items():
         if k == "experimental_performance_improvements":
             if v:
-                raise NotImplementedError("the experimental sorting cache is out of scope (SURVEY.md section 2 row 15)")
+                raise NotImplementedError("the experimental sorting cache is planner state, not a context parameter: "
+                                          "PathPlanner(..., experimental_performance_improvements=True) or Context.sort_cache_reset")
             continue
         if k not in PARAM_NAMES:
             raise TypeError(f"unknown parameter {k!r}")
@@ -205,6 +206,8 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     lib.fsdp_skidpad_submit.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
     lib.fsdp_route_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)]
+    lib.fsdp_sort_cache_reset.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.fsdp_sort_cache_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     got = (ctypes.c_int32 * 4)()
     lib.fsdp_shapes(got)
     want = [shapes.max_len, shapes.max_neighbors, shapes.max_match, shapes.path_points]
@@ -226,6 +229,7 @@ EXPORTED_SYMBOLS = [
     "fsdp_host_alloc", "fsdp_host_free", "fsdp_host_register", "fsdp_host_unregister", "fsdp_host_is_pinned", "fsdp_submit", "fsdp_collect", "fsdp_ticket_done",
     "fsdp_submit_compact", "fsdp_plan_batch_compact", "fsdp_set_option", "fsdp_pcie_probe",
     "fsdp_skidpad_submit", "fsdp_route_stats", "fsdp_ticket_capacity", "fsdp_selftest_det3", "fsdp_debug_arena", "fsdp_selftest_absminmax", "fsdp_selftest_libm", "fsdp_selftest_givens",
+    "fsdp_sort_cache_reset", "fsdp_sort_cache_hits",
 ]
 
 
@@ -353,6 +357,7 @@ class Context:
         if rc != 0:
             raise FsdpError(f"fsdp_create failed ({rc}): {lib.fsdp_last_error(None).decode()}")
         self._lib, self._h, self.device, self.n_frames = lib, h, device, 0
+        self.n_cache = 0
         self.shapes, self.result_dtype, self.path_result_dtype = shapes, shapes.result_dtype, shapes.path_result_dtype
         self.compact_dtype = shapes.compact_dtype
         for k, v in {**DEFAULT_OPTIONS, **(options or {})}.items():
@@ -405,7 +410,20 @@ class Context:
             raise ValueError("cone_offsets must be non-decreasing")
         return offsets, cones, poses, n
 
-    def plan_batch(self, offsets, cones, poses, prev_paths=None, out=None, compact: bool = False) -> np.ndarray:
+    def sort_cache_reset(self, n_planners: int):
+        """fsdp_sort_cache_reset: the reference's experimental sorting cache for n_planners planners advanced in lock-step by
+        plan_batch_sequential / sort_batch (frame i = planner i), all entries empty; 0 turns it off."""
+        self._check(self._lib.fsdp_sort_cache_reset(self._h, int(n_planners)), "fsdp_sort_cache_reset")
+        self.n_cache = int(n_planners)
+
+    def sort_cache_hits(self) -> np.ndarray:
+        """(n_planners, 2) int8 per side (left, right) of the most recent cache call: 1 reused, 0 checked and searched, -1 the side
+        returned before the check."""
+        out = np.zeros((self.n_cache, 2), dtype=np.int8)
+        self._check(self._lib.fsdp_sort_cache_hits(self._h, ctypes.c_void_p(out.ctypes.data)), "fsdp_sort_cache_hits")
+        return out
+
+    def plan_batch(self, offsets, cones, poses, prev_paths=None, out=None, compact: bool = False, _sequential: bool = False) -> np.ndarray:
         """One blocking call: the batch in, its results out (a batch of 16 384 frames or more is pipelined in chunks inside the
         library).  prev_paths: per-frame previous paths (plan_batch_sequential).  out: the array the results go to — a page-locked
         one (pinned_empty) is written in place by the GPU.  compact: fsdp_compact_result records (path, sorted indices, status:
@@ -421,7 +439,7 @@ class Context:
         cp = cones.ctypes.data if len(cones) else None
         if compact:
             self._check(self._lib.fsdp_plan_batch_compact(self._h, n, offsets.ctypes.data, cp, poses.ctypes.data, pp, out.ctypes.data), "fsdp_plan_batch_compact")
-        elif prev is not None:
+        elif prev is not None or _sequential:
             self._check(self._lib.fsdp_plan_batch_sequential(self._h, n, offsets.ctypes.data, cp, poses.ctypes.data, pp, out.ctypes.data), "fsdp_plan_batch_sequential")
         else:
             self._check(self._lib.fsdp_plan_batch(self._h, n, offsets.ctypes.data, cp, poses.ctypes.data, out.ctypes.data), "fsdp_plan_batch")
@@ -429,8 +447,9 @@ class Context:
         return out
 
     def plan_batch_sequential(self, offsets, cones, poses, prev_paths) -> np.ndarray:
-        """plan_batch with a per-frame previous path (n_frames,40,4): the stateful fallbacks of the reference."""
-        return self.plan_batch(offsets, cones, poses, prev_paths=prev_paths)
+        """plan_batch with a per-frame previous path (n_frames,40,4): the stateful fallbacks of the reference.  With the sorting
+        cache on (sort_cache_reset) frame i is planner i, and prev_paths may be None (fresh path-stage history)."""
+        return self.plan_batch(offsets, cones, poses, prev_paths=prev_paths, _sequential=self.n_cache > 0)
 
     def sort_batch(self, offsets, cones, poses) -> np.ndarray:
         offsets, cones, poses, n = self._prep(offsets, cones, poses)

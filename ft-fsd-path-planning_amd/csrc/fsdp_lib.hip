@@ -94,6 +94,7 @@ struct Work {
   int32_t* d_skid_status = nullptr;       // skid_reloc_kernel's status of the step this slot holds
   bool skid_attempted = true;             // ... which ran for that step (not once every planner is relocalized)
   SortSharedBig* d_sort_big = nullptr;    // frame states of sort_big_kernel, allocated when the route is first needed
+  int cache_base = 0;                     // sorting cache: planner of the slot's frame 0 (a chunk of a blocking call)
   int cap_frames = 0;
   // use_unknown_cones = False (filter_kernel.h): the batch without its UNKNOWN cones, and the way back for the indices
   int32_t* f_cnt = nullptr;
@@ -227,6 +228,19 @@ struct fsdp_ctx {
   MatchOut* h_match = nullptr;
   PathOut* h_path = nullptr;
   int cap_staging = 0;
+  // the sorting cache (fsdp_sort_cache_reset, sort_cache.h): one entry per planner in each of two buffers; the kernels of a
+  // call read buffer cache_cur and write the other, and the call swaps them once it has succeeded
+  int n_cache = 0;
+  int cache_cur = 0;
+  SortCacheHdr* d_cache_hdr[2] = {};
+  double* d_cache_xyt[2] = {};
+  int32_t* d_cache_off[2] = {};
+  size_t cache_rows[2] = {};                  // rows the cone stores hold
+  std::vector<int32_t> cache_layout[2];       // host copies of the two buffers' region offsets
+  std::vector<int32_t> cache_region;          // rows of a planner's region: the most cones it was ever given
+  int8_t* d_cache_hits = nullptr;
+  std::vector<int8_t> cache_hits;             // codes of the most recent call
+  bool cache_call = false;                    // the call in progress advances the cached planners
 };
 // (an empty route launch costs a stream ~1 % of a pass; a pass repeated because the kernel was missing costs a whole pass and
 // stalls the caller's collect: once needed, a route stays for a long time)
@@ -410,6 +424,20 @@ static void mark(const Work& q, StageEvents* t, MarkKind kind = MARK_PLAIN) {
 
 static bool sort128(const fsdp_ctx* c, const Inputs& in) { return in.max_cones <= SortShared128::MAX_N && !c->no_sort128; }
 
+static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
+  const int p = c->cache_cur, x = 1 - p;
+  SortCacheView v;
+  v.prev = c->d_cache_hdr[p];
+  v.next = c->d_cache_hdr[x];
+  v.prev_xyt = c->d_cache_xyt[p];
+  v.prev_off = c->d_cache_off[p];
+  v.next_xyt = c->d_cache_xyt[x];
+  v.next_off = c->d_cache_off[x];
+  v.hits = c->d_cache_hits;
+  v.base = q.cache_base;
+  return v;
+}
+
 static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in) {
   StageIn st;
   if (in.h_off) {
@@ -424,6 +452,16 @@ static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in) {
     st.dst_prev = in.d_prev;
     st.n_frames = in.n_frames;
   }
+  if (c->cache_call) {
+    const SortCacheView v = cache_view(c, q);
+    if (sort128(c, in))
+      hipLaunchKernelGGL(sort_kernel_128_cached, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones,
+                         in.d_poses, q.d_sort, q.d_big, c->d_params, st, v);
+    else
+      hipLaunchKernelGGL(sort_kernel_cached, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones,
+                         in.d_poses, q.d_sort, q.d_big, c->d_params, st, v);
+    return;
+  }
   if (sort128(c, in))
     hipLaunchKernelGGL(sort_kernel_128, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones,
                        in.d_poses, q.d_sort, q.d_big, c->d_params, st);
@@ -433,6 +471,11 @@ static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in) {
 }
 static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in) {
   if (!q.d_sort_big) HIP_TRY(c, hipMalloc(&q.d_sort_big, sizeof(SortSharedBig) * SORT_BIG_BLOCKS));
+  if (c->cache_call) {
+    hipLaunchKernelGGL(sort_big_kernel_cached, dim3(SORT_BIG_BLOCKS), dim3(WAVE), 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort,
+                       q.d_big, q.d_sort_big, c->d_params, cache_view(c, q));
+    return 0;
+  }
   hipLaunchKernelGGL(sort_big_kernel, dim3(SORT_BIG_BLOCKS), dim3(WAVE), 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big,
                      q.d_sort_big, c->d_params);
   return 0;
@@ -635,7 +678,7 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, StageEvents* t =
   if (filtered)
     if (int rc = launch_filter(c, q, in_, &fin)) return rc;
   const Inputs& in = filtered ? fin : in_;
-  std::string names = std::string(sort128(c, in) ? "sort_kernel_128" : "sort_kernel") + ",";
+  std::string names = std::string(sort128(c, in) ? "sort_kernel_128" : "sort_kernel") + (c->cache_call ? "_cached," : ",");
   if (c->poison) {
     // (tests) whatever a previous pass, another batch or the allocator left in the slot's buffers is gone: 0xFF bytes = NaNs, -1 indices
     const size_t m = (size_t)in.n_frames;
@@ -653,7 +696,7 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, StageEvents* t =
   if (with_big) {
     mark(q, t);
     if (int rc = launch_sort_big(c, q, in)) return rc;
-    names += "sort_big_kernel,";
+    names += c->cache_call ? "sort_big_kernel_cached," : "sort_big_kernel,";
   }
   mark(q, t);
   launch_match(c, q, in);
@@ -863,6 +906,75 @@ static int stage_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, int n_frame
   return 0;
 }
 
+// ---- the sorting cache ----------------------------------------------------------------------------------------------------
+static void cache_free(fsdp_ctx* c) {
+  for (int b = 0; b < 2; b++) {
+    (void)hipFree(c->d_cache_hdr[b]);
+    (void)hipFree(c->d_cache_xyt[b]);
+    (void)hipFree(c->d_cache_off[b]);
+    c->d_cache_hdr[b] = nullptr;
+    c->d_cache_xyt[b] = nullptr;
+    c->d_cache_off[b] = nullptr;
+    c->cache_rows[b] = 0;
+    c->cache_layout[b].clear();
+  }
+  (void)hipFree(c->d_cache_hits);
+  c->d_cache_hits = nullptr;
+  c->cache_region.clear();
+  c->cache_hits.clear();
+  c->n_cache = 0;
+  c->cache_cur = 0;
+}
+
+// A call that advances the cached planners: frame i is planner i.  The buffer the call writes gets room for every planner's
+// entry — a region as large as the most cones the planner was ever given (its previous entry, which a frame the reference
+// raises on keeps, fits too).  Nothing is in flight (the blocking calls have synchronised).
+static int cache_prepare(fsdp_ctx* c, int n_frames, const int32_t* off, const char* who) {
+  if (n_frames != c->n_cache) {
+    c->err = std::string(who) + ": the sorting cache is on for " + std::to_string(c->n_cache) + " planners, the batch holds " +
+             std::to_string(n_frames) + " frames (frame i is planner i)";
+    return 1;
+  }
+  const int x = 1 - c->cache_cur;
+  std::vector<int32_t> lay((size_t)n_frames + 1);
+  size_t rows = 0;
+  for (int i = 0; i < n_frames; i++) {
+    c->cache_region[(size_t)i] = std::max(c->cache_region[(size_t)i], off[i + 1] - off[i]);
+    lay[(size_t)i] = (int32_t)rows;
+    rows += (size_t)c->cache_region[(size_t)i];
+    if (rows > 0x7fffffff) {
+      c->err = std::string(who) + ": the sorting cache's cone store exceeds 2^31 rows";
+      return 1;
+    }
+  }
+  lay[(size_t)n_frames] = (int32_t)rows;
+  if (rows > c->cache_rows[x]) {
+    const size_t want = rows + rows / 2 + 64;
+    HIP_TRY(c, regrow(c->d_cache_xyt[x], 3 * want));
+    c->cache_rows[x] = want;
+  }
+  if (lay != c->cache_layout[x]) {
+    HIP_TRY(c, copy_sync(c, c->d_cache_off[x], lay.data(), sizeof(int32_t) * lay.size(), hipMemcpyHostToDevice));
+    c->cache_layout[x].swap(lay);
+  }
+  for (Work& w : c->slot) w.cache_base = 0;
+  return 0;
+}
+
+// after a successful call: its hit codes to the host, and its entries become the previous ones
+static int cache_finish(fsdp_ctx* c) {
+  HIP_TRY(c, copy_sync(c, c->cache_hits.data(), c->d_cache_hits, c->cache_hits.size(), hipMemcpyDeviceToHost));
+  c->cache_cur = 1 - c->cache_cur;
+  return 0;
+}
+
+// cache_call is set for the duration of one call
+struct CacheCall {
+  fsdp_ctx* c;
+  CacheCall(fsdp_ctx* c_, bool on) : c(c_) { c->cache_call = on; }
+  ~CacheCall() { c->cache_call = false; }
+};
+
 extern "C" {
 
 const char* fsdp_version(void) { return "fsdp-hip 0.3 (gfx950)"; }
@@ -1034,6 +1146,7 @@ void fsdp_destroy(fsdp_ctx* c) {
   (void)hipFree(c->d_g_sel);
   (void)hipFree(c->d_default_path);
   (void)hipFree(c->d_params);
+  cache_free(c);
   if (c->h_sort) (void)hipHostFree(c->h_sort);
   if (c->h_match) (void)hipHostFree(c->h_match);
   if (c->h_path) (void)hipHostFree(c->h_path);
@@ -1528,7 +1641,7 @@ int fsdp_route_stats(fsdp_ctx* c, int* expect_big, int* expect_retry, long long*
 constexpr int PLAN_CHUNKS = 4, PLAN_CHUNK_FROM = 16384, PLAN_CHUNK_MIN = 512;
 
 static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev,
-                         fsdp_frame_result* results, bool compact) {
+                         fsdp_frame_result* results, bool compact, bool sequential = false) {
   if (!c) return 1;
   if (c->outstanding) return busy_error(c, "fsdp_plan_batch");
   if (n_frames > 0 && !results) return 1;
@@ -1540,7 +1653,12 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
   size_t total;
   int max_cones;
   if (int rc = check_batch(c, n_frames, off, cones, poses, &total, &max_cones)) return rc;
+  const bool cached = sequential && c->n_cache > 0;
+  if (cached && n_frames != c->n_cache) return cache_prepare(c, n_frames, off, "fsdp_plan_batch_sequential");
   if (int rc = sync_all(c)) return rc;
+  if (cached)
+    if (int rc = cache_prepare(c, n_frames, off, "fsdp_plan_batch_sequential")) return rc;
+  const CacheCall cache_call(c, cached);
   c->last_slot = 0;
   c->last_n = n_frames;
   if (n_frames == 0) return 0;
@@ -1553,6 +1671,7 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
     Work& q = c->slot[k];  // (slots beyond the overlap depth get their stream here: a chunk is a pass in flight)
     Work::Ticket& t = q.tk[0];
     if ((rc = ensure_work(c, q, hi - lo))) break;
+    q.cache_base = lo;  // (the chunk's frames are planners lo..hi-1 of the sorting cache)
     t.n = hi - lo;
     t.skid = false;
     t.off = off + lo;
@@ -1581,12 +1700,13 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
     if (rc == 0) rc = rck;
   }
   c->next_ticket -= issued;  // (the chunks' numbers were internal: the caller's tickets keep counting up from where they were)
+  if (rc == 0 && cached) rc = cache_finish(c);  // (once, after every chunk; a failed call leaves the previous entries in place)
   return rc;
 }
 
 int fsdp_plan_batch_sequential(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
                                const double* prev_paths, fsdp_frame_result* results) {
-  return plan_blocking(c, n_frames, off, cones, poses, prev_paths, results, false);
+  return plan_blocking(c, n_frames, off, cones, poses, prev_paths, results, false, true);
 }
 
 int fsdp_plan_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
@@ -1597,6 +1717,45 @@ int fsdp_plan_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double*
 int fsdp_plan_batch_compact(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev_paths,
                             fsdp_compact_result* results) {
   return plan_blocking(c, n_frames, off, cones, poses, prev_paths, (fsdp_frame_result*)results, true);
+}
+
+int fsdp_sort_cache_reset(fsdp_ctx* c, int n_planners) {
+  if (!c) return 1;
+  if (c->mission == 2) {
+    c->err = "fsdp_sort_cache_reset: a skidpad context never sorts cones";
+    return 1;
+  }
+  if (n_planners < 0) {
+    c->err = "fsdp_sort_cache_reset: n_planners must be >= 0";
+    return 1;
+  }
+  if (c->outstanding) return busy_error(c, "fsdp_sort_cache_reset");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = sync_all(c)) return rc;
+  cache_free(c);
+  if (n_planners == 0) return 0;
+  const size_t n = (size_t)n_planners;
+  for (int b = 0; b < 2; b++) {
+    HIP_TRY(c, regrow(c->d_cache_hdr[b], n));
+    HIP_TRY(c, hipMemsetAsync(c->d_cache_hdr[b], 0, sizeof(SortCacheHdr) * n, c->stream));  // (valid = 0: no entry)
+    HIP_TRY(c, regrow(c->d_cache_off[b], n + 1));
+    HIP_TRY(c, hipMemsetAsync(c->d_cache_off[b], 0, sizeof(int32_t) * (n + 1), c->stream));
+    HIP_TRY(c, regrow(c->d_cache_xyt[b], 3));
+    c->cache_rows[b] = 1;
+    c->cache_layout[b].assign(n + 1, 0);
+  }
+  HIP_TRY(c, regrow(c->d_cache_hits, 2 * n));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->cache_region.assign(n, 0);
+  c->cache_hits.assign(2 * n, (int8_t)-1);
+  c->n_cache = n_planners;
+  return 0;
+}
+
+int fsdp_sort_cache_hits(const fsdp_ctx* c, int8_t* out) {
+  if (!c || !out || c->n_cache == 0) return 1;
+  memcpy(out, c->cache_hits.data(), c->cache_hits.size());
+  return 0;
 }
 
 // Options (include/fsdp.h fsdp_set_option): what tests and measurements pin.  Results never depend on them.
@@ -1887,8 +2046,13 @@ int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double*
   size_t total;
   int max_cones;
   if (int rc = check_batch(c, n_frames, off, cones, poses, &total, &max_cones)) return rc;
+  const bool cached = c->n_cache > 0;
+  if (cached && n_frames != c->n_cache) return cache_prepare(c, n_frames, off, "fsdp_sort_batch");
   if (n_frames == 0) return 0;
   if (int rc = sync_all(c)) return rc;
+  if (cached)
+    if (int rc = cache_prepare(c, n_frames, off, "fsdp_sort_batch")) return rc;
+  const CacheCall cache_call(c, cached);
   Work& q = c->slot[0];
   if (int rc = ensure_work(c, q, n_frames)) return rc;
   if (int rc = upload_inputs(c, q.in, q.stream, n_frames, off, cones, poses, nullptr, total, max_cones)) return rc;
@@ -1910,6 +2074,8 @@ int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double*
     HIP_TRY(c, hipMemcpyAsync(moff.data(), q.f_off, sizeof(int32_t) * ((size_t)n_frames + 1), hipMemcpyDeviceToHost, q.stream));
   }
   HIP_TRY(c, hipStreamSynchronize(q.stream));
+  if (cached)
+    if (int rc = cache_finish(c)) return rc;
   for (int i = 0; i < n_frames; i++) {
     memset(&results[i], 0, sizeof(fsdp_frame_result));
     assemble(&c->h_sort[i], nullptr, nullptr, &results[i]);

@@ -18,6 +18,7 @@
 #include <stddef.h>
 
 #include "fsdp_device.h"
+#include "sort_cache.h"
 
 namespace fsdp {
 
@@ -183,7 +184,9 @@ __device__ inline bool inside_ellipse_of_edge(double px, double py, double cx, d
 
 // end_configurations.py:108-223 for ONE candidate neighbour `cand` of the popped node.
 // check_if_neighbor_lies_between_last_in_attempt_and_candidate (:226-257) for one (candidate, neighbour) pair
-template <class SH>
+// (CACHE, here and below: the cache-enabled kernels get their own copies of the stage's functions, so that the kernels without the cache
+// keep the inlining decisions — and hence the code — they had before; the argument changes nothing else)
+template <class SH, bool CACHE = false>
 __device__ __forceinline__ bool neighbour_lies_between(const SH& S, int node, int cand, int nb) {  // (cone indices only)
   if (nb == cand) return false;
   const double lx = S.x[node], ly = S.y[node];
@@ -199,7 +202,7 @@ __device__ __forceinline__ bool neighbour_lies_between(const SH& S, int node, in
 // two edges of the attempt (ang_sl: attempt[pos-1] -> node, ang_tl: attempt[pos-2] -> attempt[pos-1]) are the atan2
 // values computed when those cones were candidates themselves (same operands, same bits); ang_cand returns the direction
 // of the edge node -> candidate for the candidate's own children.
-template <class SH>
+template <class SH, bool CACHE = false>
 __device__ inline bool candidate_can_be_added(const SH& S, const Params& P, int side, int cone_type, int pos, int node, int cand, bool between,
                                               double px, double py, double dx, double dy, double dnx, double dny, double a_car,
                                               double ang_sl, double ang_tl, double& ang_cand) {
@@ -274,9 +277,11 @@ __device__ __forceinline__ double np_sum_reg(const double (&a)[MAX_LEN], int n) 
 // Phase 1 of a side (S4-S7): start cones, mutual-kNN adjacency, reachability -> S.ctl[side].
 // reuse_adjacency: the mutual-kNN lists were built by the other side's call and no cone of the frame carries a side
 // colour, so they are the same for this side (no-colour mode builds them once per frame).
-template <class SH>
+// CACHE: the sorting cache's check follows the start cones (core_trace_sorter.py:293-300); a side that reuses the cached
+// result loads it into S.best / best_len / n_configs / best_cost and stays inactive (no adjacency, search or costing).
+template <class SH, bool CACHE = false>
 __device__ __forceinline__ void sort_side_prepare(SH& S, const Params& P, int n, int cone_type, int side, double px, double py, double dx,
-                                         double dy, bool reuse_adjacency) {
+                                         double dy, bool reuse_adjacency, SortCacheFrame* cf = nullptr) {
   const int lane = lane_id();
   const int other_type = (cone_type == T_LEFT) ? T_RIGHT : T_LEFT;
   if (lane == 0) {
@@ -354,6 +359,26 @@ __device__ __forceinline__ void sort_side_prepare(SH& S, const Params& P, int n,
     S.first_k[side][1] = fk1;
   }
   const int start_idx = fk0;
+  if constexpr (CACHE) {
+    // input_is_very_similar_to_previous_input: the cached starting cones of this side (same count), then the whole frame
+    const SortCacheHdr& e = cf->v->prev[cf->planner];
+    bool hit = cf->all_similar && e.has[side] != 0 && e.n_start[side] == n_first;
+    for (int r = 0; r < n_first && hit; r++) {
+      const int k = r == 0 ? fk0 : fk1;
+      hit = cache_row_similar(S.x[k], S.y[k], (double)S.type[k], &e.start[side][0][0], n_first);
+    }
+    cf->hit[side] = hit ? 1 : 0;
+    if (hit) {
+      if (lane < MAX_LEN) S.best[side][lane] = e.best[side][lane];
+      if (lane == 0) {
+        S.best_len[side] = e.best_len[side];
+        S.n_configs[side] = e.n_configs[side];
+        S.best_cost[side] = e.best_cost[side];
+      }
+      __syncthreads();
+      return;
+    }
+  }
 
   // ---------------- S5: mutual-kNN adjacency (adjacency_matrix.py:60-128) ----------------
   PROF_MARK(2);
@@ -571,7 +596,7 @@ struct PairMask<true> {
 // Phase 2 (S8): DFS over the cost tree (end_configurations.py:320-431) of BOTH sides at once, one half-wavefront per
 // side.  A pop keeps at most 5 candidate lanes and 25 (candidate, neighbour) lanes busy, so the two independent searches
 // share every instruction; the loop runs until both stacks are empty.
-template <class SH>
+template <class SH, bool CACHE = false>
 __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double py, double dx, double dy) {
   const int lane = lane_id();
   const int side = lane >> 5, sl = lane & 31;
@@ -636,7 +661,7 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
     for (int r = 0; r < PAIR_ROUNDS; r++) {
       const int pr = sl + 32 * r;
       bool btw = false;
-      if (pr < n_nb * n_nb) btw = neighbour_lies_between(S, node, S.nbr[adj][node][pr / n_nb], S.nbr[adj][node][pr % n_nb]);
+      if (pr < n_nb * n_nb) btw = neighbour_lies_between<SH, CACHE>(S, node, S.nbr[adj][node][pr / n_nb], S.nbr[adj][node][pr % n_nb]);
       bm |= (pair_mask_t)(unsigned)(__ballot(btw) >> (32 * side)) << (32 * r);
     }
     bool can = false;
@@ -644,7 +669,7 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
     if (sl < n_nb) {
       const bool between = ((bm >> (sl * n_nb)) & (((pair_mask_t)1 << n_nb) - 1u)) != 0u;
       const double ang_tl = (pos >= 2) ? S.attempt_ang[side][pos - 1] : 0.0;
-      can = candidate_can_be_added(S, P, side, cone_type, pos, node, S.nbr[adj][node][sl], between, px, py, dx, dy, dnx, dny, a_car,
+      can = candidate_can_be_added<SH, CACHE>(S, P, side, cone_type, pos, node, S.nbr[adj][node][sl], between, px, py, dx, dy, dnx, dny, a_car,
                                    node_ang, ang_tl, cand_ang);
     }
     const unsigned m = (unsigned)(__ballot(can) >> (32 * side));
@@ -676,7 +701,7 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
 }
 
 // Phase 3 of a side (S10-S12): post filters, side counting, costs, pick.  Returns the frame status of this side.
-template <class SH>
+template <class SH, bool CACHE = false>
 __device__ __forceinline__ int sort_side_finish(SH& S, int n, int cone_type, int side, double px, double py, double dx,
                                        double dy) {
   const int lane = lane_id();
@@ -1140,7 +1165,7 @@ __device__ __forceinline__ int sort_side_finish(SH& S, int n, int cone_type, int
 }
 
 // combine_traces.py:115-275 (wave-uniform; every lane computes the same scalars)
-template <class SH>
+template <class SH, bool CACHE = false>
 __device__ inline void combine_sides(SH& S, int& nl, int& nr) {
   nl = S.best_len[0];
   nr = S.best_len[1];
@@ -1256,10 +1281,78 @@ struct StageIn {
   int32_t base = 0;                   // src_off[0]: src_cones points at row `base` of the caller's array, the device copies start at 0
 };
 
-// The sorting stage of one frame on one wavefront; S = the frame state (LDS or global memory).
+// The cache entry a frame leaves for its planner's next call (rule of core_trace_sorter.py:189-195), and the frame's hit codes.
+// A frame the reference raises on (101 / 102: sort_left_right never reaches the assignment) keeps the previous entry; a
+// capacity refusal drops it (the next call misses); a frame beyond the LDS capacities is left to sort_big_kernel, which reads
+// the same previous entry.
 template <class SH>
+__device__ inline void sort_cache_commit(const SH& S, const SortCacheFrame& cf, int n, int status) {
+  constexpr bool BIG = SH::CAP == BIG_CONES;
+  const int lane = lane_id();
+  if (!BIG && (status == ST_OVERFLOW_CONES || status == ST_OVERFLOW_ENDS)) return;
+  const SortCacheView& v = *cf.v;
+  const int p = cf.planner;
+  const SortCacheHdr& e = v.prev[p];
+  SortCacheHdr& o = v.next[p];
+  double* dst = v.next_xyt + 3 * (size_t)v.next_off[p];
+  if (lane == 0) {
+    v.hits[2 * (size_t)p + 0] = (int8_t)cf.hit[0];
+    v.hits[2 * (size_t)p + 1] = (int8_t)cf.hit[1];
+  }
+  if (status == ST_REF_UNDEFINED_SET_DIFF || status == ST_REF_UNDEFINED_DFS_OOB) {
+    const int m = e.valid ? e.n : 0;
+    const double* src = v.prev_xyt + 3 * (size_t)v.prev_off[p];
+    for (int k = lane; k < 3 * m; k += WAVE) dst[k] = src[k];
+    const int32_t* hs = reinterpret_cast<const int32_t*>(&e);
+    int32_t* hd = reinterpret_cast<int32_t*>(&o);
+    static_assert(sizeof(SortCacheHdr) % 4 == 0, "header copied as words");
+    for (int k = lane; k < (int)(sizeof(SortCacheHdr) / 4); k += WAVE) hd[k] = hs[k];
+    return;
+  }
+  if (status != ST_OK) {  // (sort_big_kernel: 201 / 202)
+    if (lane == 0) o.valid = 0;
+    return;
+  }
+  for (int i = lane; i < n; i += WAVE) {
+    dst[3 * i + 0] = S.x[i];
+    dst[3 * i + 1] = S.y[i];
+    dst[3 * i + 2] = (double)S.type[i];
+  }
+#pragma unroll
+  for (int side = 0; side < 2; side++) {
+    const int h = cf.hit[side];
+    if (lane < MAX_LEN) o.best[side][lane] = S.best[side][lane];
+    if (lane < 6) {
+      const int r = lane / 3, c = lane - 3 * r;
+      double sv = 0.0;
+      if (h == 1) {
+        sv = e.start[side][r][c];
+      } else if (h == 0 && r < (S.first_k[side][1] >= 0 ? 2 : 1)) {
+        const int k = S.first_k[side][r];
+        sv = c == 0 ? S.x[k] : c == 1 ? S.y[k] : (double)S.type[k];
+      }
+      o.start[side][r][c] = sv;
+    }
+    if (lane == 0) {
+      o.has[side] = h == 1 ? 1 : (h == 0 && S.n_configs[side] > 0) ? 1 : 0;
+      o.n_start[side] = h == 1 ? e.n_start[side] : (S.first_k[side][1] >= 0 ? 2 : 1);
+      o.best_len[side] = S.best_len[side];
+      o.n_configs[side] = S.n_configs[side];
+      o.best_cost[side] = S.best_cost[side];
+    }
+  }
+  if (lane == 0) {
+    o.n = n;
+    o.valid = 1;
+  }
+}
+
+// The sorting stage of one frame on one wavefront; S = the frame state (LDS or global memory).  CACHE: the sorting cache of
+// planner cache->base + frame is read and its next entry written (sort_cache.h).
+template <class SH, bool CACHE = false>
 __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
-                                  const double* __restrict__ poses, SortOut* __restrict__ out, const StageIn& stage = StageIn()) {
+                                  const double* __restrict__ poses, SortOut* __restrict__ out, const StageIn& stage = StageIn(),
+                                  const SortCacheView* cache = nullptr) {
   const int lane = lane_id();
   const bool staging = stage.src_off != nullptr;
   const int32_t* offs = staging ? stage.src_off : cone_offsets;
@@ -1330,6 +1423,24 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
   }
   __syncthreads();
   if (lane == 0) S.adj_built = 0;
+  SortCacheFrame cf;
+  if constexpr (CACHE) {
+    // cone_arrays_are_similar(cones_flat, cached cones_flat, 0.1) once per frame (both sides share it): lanes = this frame's
+    // cones, the cached ones read wave-uniformly; the first failing block of 64 cones ends the sweep
+    cf.v = cache;
+    cf.planner = cache->base + frame;
+    const SortCacheHdr& e = cache->prev[cf.planner];
+    bool ok = status == ST_OK && n >= 3 && e.valid != 0 && e.n == n;
+    if (ok) {
+      const double* rows = cache->prev_xyt + 3 * (size_t)cache->prev_off[cf.planner];
+      for (int i0 = 0; i0 < n && ok; i0 += WAVE) {
+        const int i = i0 + lane;
+        const bool bad = i < n && !cache_row_similar(S.x[i], S.y[i], (double)S.type[i], rows, n);
+        ok = __ballot(bad) == 0ull;
+      }
+    }
+    cf.all_similar = ok;
+  }
   // no cone with a side colour: both sides see the same distance matrix and hence the same mutual-kNN adjacency
   bool coloured = false;
   for (int i = lane; i < n; i += WAVE) coloured = coloured || S.type[i] == T_LEFT || S.type[i] == T_RIGHT;
@@ -1338,20 +1449,20 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
 #define FSDP_SORT_STOP 9  // (instruction accounting builds stop the stage after phase 1..4: tools/sort_phase_insts.sh)
 #endif
   if (status == ST_OK && FSDP_SORT_STOP > 1) {
-    sort_side_prepare(S, P, n, T_LEFT, 0, px, py, dx, dy, false);
-    // (the left call returns before building the adjacency when it finds no start cone or n < 3)
+    sort_side_prepare<SH, CACHE>(S, P, n, T_LEFT, 0, px, py, dx, dy, false, &cf);
+    // (the left call returns before building the adjacency when it finds no start cone or n < 3, or reuses the cached result)
     const bool left_built = S.adj_built != 0;
-    sort_side_prepare(S, P, n, T_RIGHT, 1, px, py, dx, dy, colourless && left_built);
-    if (FSDP_SORT_STOP > 2) sort_dfs_both(S, P, px, py, dx, dy);
+    sort_side_prepare<SH, CACHE>(S, P, n, T_RIGHT, 1, px, py, dx, dy, colourless && left_built, &cf);
+    if (FSDP_SORT_STOP > 2) sort_dfs_both<SH, CACHE>(S, P, px, py, dx, dy);
     if (FSDP_SORT_STOP > 3) {
-      status = sort_side_finish(S, n, T_LEFT, 0, px, py, dx, dy);
+      status = sort_side_finish<SH, CACHE>(S, n, T_LEFT, 0, px, py, dx, dy);
       __syncthreads();
-      if (status == ST_OK) status = sort_side_finish(S, n, T_RIGHT, 1, px, py, dx, dy);
+      if (status == ST_OK) status = sort_side_finish<SH, CACHE>(S, n, T_RIGHT, 1, px, py, dx, dy);
     }
   }
   __syncthreads();
   int nl = 0, nr = 0;
-  if (status == ST_OK && FSDP_SORT_STOP > 4) combine_sides(S, nl, nr);
+  if (status == ST_OK && FSDP_SORT_STOP > 4) combine_sides<SH, CACHE>(S, nl, nr);
   if (lane == 0) {
     o->status = status;
     o->n_left = nl;
@@ -1369,21 +1480,22 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
     o->left_idx[lane] = (status == ST_OK && lane < nl) ? (int32_t)S.best[0][lane] : -1;
     o->right_idx[lane] = (status == ST_OK && lane < nr) ? (int32_t)S.best[1][lane] : -1;
   }
+  if constexpr (CACHE) sort_cache_commit(S, cf, n, status);
   __syncthreads();
 }
 
 // One workgroup (= one wavefront) per frame, frame state in LDS.  big (optional): [0] = counter, [1..] = frames beyond
 // the LDS capacities (more cones than the state holds, more than 64 raw end configurations), planned again by
 // sort_big_kernel.
-template <class SH>
+template <class SH, bool CACHE = false>
 __device__ __forceinline__ void sort_kernel_body(SH& S, int n_frames, const int32_t* __restrict__ cone_offsets,
                                                  const double* __restrict__ cones_xyt, const double* __restrict__ poses,
                                                  SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
-                                                 const StageIn& stage) {
+                                                 const StageIn& stage, const SortCacheView* cache = nullptr) {
   const int frame = blockIdx.x;
   if (frame >= n_frames) return;
   PROF_INIT();
-  sort_frame(S, *prm, frame, cone_offsets, cones_xyt, poses, out, stage);
+  sort_frame<SH, CACHE>(S, *prm, frame, cone_offsets, cones_xyt, poses, out, stage, cache);
   if (big != nullptr && lane_id() == 0 && (out[frame].status == ST_OVERFLOW_CONES || out[frame].status == ST_OVERFLOW_ENDS))
     big[1 + atomicAdd(&big[0], 1)] = frame;
   PROF_FLUSH();
@@ -1425,6 +1537,34 @@ __global__ void __launch_bounds__(64) sort_big_kernel(const int32_t* __restrict_
   SortSharedBig& S = state[blockIdx.x];
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     sort_frame(S, *prm, big[1 + i], cone_offsets, cones_xyt, poses, out);
+    __syncthreads();
+  }
+}
+
+// ---- the same three kernels with the sorting cache (sort_cache.h): launched only for the calls that advance planners with
+// the cache on (fsdp_sort_cache_reset); the kernels above are untouched by it ----
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3)))
+sort_kernel_cached(int n_frames, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
+                   const double* __restrict__ poses, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
+                   StageIn stage, SortCacheView cache) {
+  __shared__ SortShared S;
+  sort_kernel_body<SortShared, true>(S, n_frames, cone_offsets, cones_xyt, poses, out, big, prm, stage, &cache);
+}
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SORT128_WAVES)))
+sort_kernel_128_cached(int n_frames, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
+                       const double* __restrict__ poses, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
+                       StageIn stage, SortCacheView cache) {
+  __shared__ SortShared128 S;
+  sort_kernel_body<SortShared128, true>(S, n_frames, cone_offsets, cones_xyt, poses, out, big, prm, stage, &cache);
+}
+__global__ void __launch_bounds__(64) sort_big_kernel_cached(const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
+                                                             const double* __restrict__ poses, SortOut* __restrict__ out,
+                                                             const int* __restrict__ big, SortSharedBig* __restrict__ state,
+                                                             const Params* __restrict__ prm, SortCacheView cache) {
+  const int n = big[0];
+  SortSharedBig& S = state[blockIdx.x];
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    sort_frame<SortSharedBig, true>(S, *prm, big[1 + i], cone_offsets, cones_xyt, poses, out, StageIn(), &cache);
     __syncthreads();
   }
 }

@@ -126,10 +126,18 @@ class PathPlanner:
                  devices: Sequence[int] | str | None = None):
         """devices: GPUs ``plan_batch`` shards its frames over from this one process (multi.MultiPlanner): a list of
         device indices, or "all" for every visible GPU; None (default) = the single GPU ``device``.  The single-frame
-        call always runs on the first of them."""
-        if experimental_performance_improvements:
-            # reference README.md:24-27: off by default, changes results, meaningless for independent frames
-            raise NotImplementedError("the experimental sorting cache is out of scope (SURVEY.md §2 row 15)")
+        call always runs on the first of them.
+
+        experimental_performance_improvements: the reference's sorting cache (README.md:24-27, core_trace_sorter.py:218-300):
+        a side whose starting cones and whole cone list lie within 0.1 m of the previous call's reuses that call's sorted
+        configuration (its indices, applied to the current cones).  It is state of this planner's single-frame calls
+        (include/fsdp.h fsdp_sort_cache_reset), so it needs ``stateful=True`` and one GPU; ``plan_batch`` keeps its
+        fresh-planner semantics and never reads or writes it.  The acceleration, ebs_test and skidpad missions never sort
+        cones: there the flag has no effect."""
+        if experimental_performance_improvements and not stateful:
+            raise ValueError("experimental_performance_improvements caches the previous call's sorting: it needs stateful=True")
+        if experimental_performance_improvements and devices is not None:
+            raise ValueError("experimental_performance_improvements is state of the single-frame planner: it takes no devices=")
         self.mission = MissionTypes(mission)
         self.global_path = None
         self._accel = None
@@ -158,6 +166,10 @@ class PathPlanner:
             # params: overrides of the configuration constants by the reference's kwarg names (config.py), e.g.
             # dict(max_dist=5.5, max_length=10, smoothing=0.1); None = the reference's defaults
             self._ctx = _capi.Context(device=device, mission=int(self.mission), params=params)
+        # full_pipeline.py:122-140: only the missions that sort cones have something to cache
+        self._sort_cache = bool(experimental_performance_improvements) and self._accel is None and self._skid is None
+        if self._sort_cache:
+            self._ctx.sort_cache_reset(1)
 
     @property
     def relocalization_info(self):
@@ -218,7 +230,8 @@ class PathPlanner:
 
     # ---- batched form -------------------------------------------------------------------
     def plan_batch(self, cone_offsets, cones_xyt, poses) -> np.ndarray:
-        """Structured array (one row per frame, dtype _capi.RESULT_DTYPE)."""
+        """Structured array (one row per frame, dtype _capi.RESULT_DTYPE).  Independent frames, each planned by a fresh planner:
+        neither the previous path nor the sorting cache of experimental_performance_improvements takes part."""
         if self._skid is not None:
             raise RuntimeError("the skidpad mission is stateful: use skidpad.SkidpadBatch.step for batches of planner instances")
         if self._multi is not None:  # contiguous frame ranges, one per GPU, from this thread (multi.py)
@@ -249,7 +262,9 @@ class PathPlanner:
         if self._accel is not None:
             return self._accelerate(cones, xyt, pose, return_intermediate_results)
         off1 = np.array([0, len(xyt)], np.int32)
-        if self.stateful and self._prev is not None:
+        if self._sort_cache:  # every call advances the planner's sorting cache, the first one included
+            r = self._ctx.plan_batch_sequential(off1, xyt, pose[None], None if self._prev is None else self._prev[None])[0]
+        elif self.stateful and self._prev is not None:
             r = self._ctx.plan_batch_sequential(off1, xyt, pose[None], self._prev[None])[0]
         else:
             r = self._ctx.plan_batch(off1, xyt, pose[None])[0]

@@ -3,6 +3,7 @@
 loop :103-131).  Same file schema: a list of {"car_position":[x,y], "car_direction":[dx,dy], "slam_cones":[5 lists of [x,y]]}.
 
   python -m fsd_path_planning_amd.replay --data-path fsg_19_2_laps.json [--remove-color-info] [--batched] [--output-path out.npz]
+                                          [--experimental-performance-improvements]  (per-frame mode only)
 
 Two replay modes:
   per-frame : one PathPlanner, one calculate_path_in_global_frame call per frame, wall-clock per call (what the
@@ -89,10 +90,11 @@ def load_data_json(data_path: Path, remove_color_info: bool = False) -> Tuple[np
     return rec.poses[:, :2].copy(), rec.poses[:, 2:].copy(), [rec.frame_cones_by_type(k) for k in range(len(rec))]
 
 
-def replay_per_frame(mission, positions, directions, observations, device=None):
-    warm = PathPlanner(mission, device=device)  # warm-up on a throw-away planner (json_demo.py:89-94)
+def replay_per_frame(mission, positions, directions, observations, device=None, experimental_performance_improvements: bool = False):
+    flag = experimental_performance_improvements  # the reference's sorting cache (json_demo.py:68,75)
+    warm = PathPlanner(mission, flag, device=device)  # warm-up on a throw-away planner (json_demo.py:89-94)
     warm.calculate_path_in_global_frame(observations[0], positions[0], directions[0])
-    planner = PathPlanner(mission, device=device)
+    planner = PathPlanner(mission, flag, device=device)
     paths, times, reloc_frame = [], [], None
     for i, (p, d, c) in enumerate(zip(positions, directions, observations)):
         if reloc_frame is None and planner.relocalization_info is not None:
@@ -191,7 +193,11 @@ def main(argv=None):
     ap.add_argument("--devices", type=str, default=None, help='--batched: GPUs the stream is sharded over from this process, e.g. "0,1,2,3" or "all"')
     ap.add_argument("--batch-frames", type=int, default=4096, help="--batched: frames per batch of the stream")
     ap.add_argument("--depth", type=int, default=4, help="--batched: batches in flight")
+    ap.add_argument("--experimental-performance-improvements", action="store_true",
+                    help="per-frame replay: the reference's sorting cache (PathPlanner(mission, True))")
     a = ap.parse_args(argv)
+    if a.batched and a.experimental_performance_improvements:
+        ap.error("--experimental-performance-improvements is state of one planner: per-frame replay only (not with --batched)")
     mission = select_mission_by_filename(a.data_path.name)
     positions, directions, observations = load_data_json(a.data_path, a.remove_color_info)
     out = {"file": str(a.data_path), "mission": mission.name, "frames": len(positions)}
@@ -206,8 +212,9 @@ def main(argv=None):
                    status_histogram={int(k): int(v) for k, v in zip(*np.unique(res["status"], return_counts=True))})
         paths = res["path"]
     else:
-        paths, times, reloc_frame, info = replay_per_frame(mission, positions, directions, observations, a.device)
-        out.update(mode="per-frame", p50_us=float(np.median(times) * 1e6), mean_us=float(times.mean() * 1e6),
+        paths, times, reloc_frame, info = replay_per_frame(mission, positions, directions, observations, a.device,
+                                                           a.experimental_performance_improvements)
+        out.update(mode="per-frame", experimental_performance_improvements=a.experimental_performance_improvements, p50_us=float(np.median(times) * 1e6), mean_us=float(times.mean() * 1e6),
                    max_us=float(times.max() * 1e6), frames_over_100ms=int((times > 0.1).sum()), relocalized_at_frame=reloc_frame)
         if info is not None:
             out.update(translation=[float(x) for x in info.translation], rotation_deg=float(np.rad2deg(info.rotation)))

@@ -44,7 +44,7 @@ def _overrides(defaults, kwargs):
     for k, v in kwargs.items():
         if k == "experimental_performance_improvements":
             if v:
-                raise NotImplementedError("the experimental sorting cache is out of scope (SURVEY.md section 2 row 15)")
+                raise NotImplementedError("experimental_performance_improvements belongs to ConeSorting (the sorting cache)")
             continue
         if k not in defaults:
             raise TypeError(f"unexpected keyword argument {k!r}")
@@ -70,9 +70,16 @@ class ConeSorting:
                     threshold_directional_angle=np.deg2rad(40), threshold_absolute_angle=np.deg2rad(65), use_unknown_cones=True)
 
     def __init__(self, device=None, **kwargs):
+        # experimental_performance_improvements (core_cone_sorting.py:58,99): the reference's sorting cache — consecutive
+        # run_cone_sorting calls chain like its TraceSorter's; the cache is state of this object, on a context of its own
+        cache = bool(kwargs.pop("experimental_performance_improvements", False))
         self._params = _overrides(self.DEFAULTS, kwargs)
         self.input = ConeSortingInput()
         self._device = device
+        self._own_ctx = None
+        if cache:
+            self._own_ctx = _capi.Context(device=device, mission=4, params=self._params)
+            self._own_ctx.sort_cache_reset(1)
 
     def set_new_input(self, slam_input: ConeSortingInput) -> None:
         self.input = slam_input
@@ -80,7 +87,8 @@ class ConeSorting:
     def run_cone_sorting(self) -> Tuple[np.ndarray, np.ndarray]:
         xyt = flatten_cones_by_type_array(self.input.slam_cones)
         pose = np.concatenate([np.asarray(self.input.slam_position, float).reshape(2), np.asarray(self.input.slam_direction, float).reshape(2)])
-        r = _ctx(self._device, self._params).sort_batch(np.array([0, len(xyt)], np.int32), xyt, pose[None])[0]
+        ctx = self._own_ctx or _ctx(self._device, self._params)
+        r = ctx.sort_batch(np.array([0, len(xyt)], np.int32), xyt, pose[None])[0]
         _check(r["status"])
         self.last_result = r
         return xyt[r["left_idx"][: r["n_left"]], :2], xyt[r["right_idx"][: r["n_right"]], :2]

@@ -209,6 +209,25 @@ int fsdp_plan_batch_sequential(fsdp_ctx* ctx, int n_frames, const int32_t* cone_
 /* the resident form of the above: applies to the next fsdp_run calls until reset with NULL */
 int fsdp_set_previous_paths(fsdp_ctx* ctx, const double* prev_paths);
 
+/* The reference's experimental sorting cache (PathPlanner(mission, experimental_performance_improvements=True),
+ * core_trace_sorter.py:57-327): a side whose starting cones and whole cone list both lie within 0.1 m (same types) of the
+ * planner's previous call reuses that call's configurations instead of searching again — applied to the CURRENT cones, as
+ * the reference does.  Per-planner state on the device.
+ *   fsdp_sort_cache_reset(ctx, n): n > 0 turns the cache on for n planners advanced in lock-step, all entries empty; 0 turns
+ *   it off (the default).  A skidpad context returns an error.
+ *   While it is on, fsdp_plan_batch_sequential (prev_paths NULL allowed: fresh path-stage history, the cache still applies)
+ *   and fsdp_sort_batch take n_frames == n planners, frame i = planner i, and read and replace the planners' entries; a call
+ *   with another n_frames returns an error and leaves the cache as it was, and so does any failed call.  The chunked form of
+ *   the blocking call (16 384+ frames) gives the same results.
+ *   No other entry point reads or writes the cache: fsdp_plan_batch[_compact], fsdp_submit* / fsdp_collect, fsdp_upload /
+ *   fsdp_run, the match / path stage calls and the skidpad calls plan as if it were off.  Like every call on a context, the
+ *   cache calls are not to be made from two threads at once.
+ *   fsdp_sort_cache_hits(ctx, out): per planner and side (left, right) of the most recent cache call, int8 (n, 2):
+ *   1 = the cached result was reused, 0 = checked and searched, -1 = the side returned before the check (fewer than 3 cones,
+ *   no starting cone).  Returns an error while the cache is off. */
+int fsdp_sort_cache_reset(fsdp_ctx* ctx, int n_planners);
+int fsdp_sort_cache_hits(const fsdp_ctx* ctx, int8_t* out);
+
 /* PathPlanner.set_global_path (full_pipeline.py:81-82) / the known path of a relocalized planner (:118-136): with a
  * global path (n,2) the path of every following frame is drawn from it (core_calculate_path.py:514-529: the part within
  * 30 m of the car, rolled to start a third of the table before the closest point) instead of from the matched cones.
