@@ -49,27 +49,26 @@ struct Inputs {
   int n_frames = 0;
   int max_cones = 0;      // most cones in a frame (picks the sorting kernel's state size)
   bool use_prev = false;  // d_prev holds this batch's previous paths
-  // the next pass's sorting kernel brings the batch onto the device itself (sort_kernel.h StageIn): device views of the
-  // caller's page-locked buffers, valid for that one launch
-  const int32_t* h_off = nullptr;
-  const double* h_cones = nullptr;
-  const double* h_poses = nullptr;
-  const double* h_prev = nullptr;
-  int32_t h_base = 0;              // cone_offsets[0] of the caller's batch (the device copies are rebased to 0)
   std::vector<int32_t> off_rebased;  // offsets - cone_offsets[0] for the copy paths (kept until the slot's next batch)
 };
 
-// A batch whose offsets do not start at 0 (a slice of a larger batch): the copy paths move offsets rebased to 0 and the
-// cones from the slice's first row.  Returns true when `off` now points at the slot's own (pageable) rebased copy.
-static bool rebase_batch(Inputs& in, int n_frames, const int32_t*& off, const double*& cones) {
-  if (n_frames <= 0 || off[0] == 0) return false;
-  const int32_t b = off[0];
-  in.off_rebased.resize((size_t)n_frames + 1);
-  for (int i = 0; i <= n_frames; i++) in.off_rebased[(size_t)i] = off[i] - b;
-  if (cones) cones += 3 * (size_t)b;
-  off = in.off_rebased.data();
-  return true;
-}
+// one batch of frames as the caller hands it over (host memory, checked by check_batch).  cone_offsets[0] = off[0] >= 0: the
+// batch's cones are the rows [off[0], off[n]) of `cones` — a slice of a larger batch is handed over by pointing at its offsets
+// (include/fsdp.h)
+struct Batch {
+  int n = 0;
+  const int32_t* off = nullptr;
+  const double* cones = nullptr;
+  const double* poses = nullptr;
+  const double* prev = nullptr;  // optional previous paths (n,40,4)
+  size_t total = 0;              // cone rows: off[n] - off[0]
+  int max_cones = 0;             // most cones in a frame
+  // frames [lo, hi) (max_cones stays the whole batch's: every part runs the kernels the whole would)
+  Batch slice(int lo, int hi) const {
+    return Batch{hi - lo, off + lo, cones, poses + 4 * (size_t)lo, prev ? prev + (size_t)PATH_POINTS * 4 * (size_t)lo : nullptr,
+                 (size_t)(off[hi] - off[lo]), max_cones};
+  }
+};
 
 // Tickets queue up behind each other on a slot's stream (stream order protects the slot's buffers), so a slot always has
 // its next batch waiting when the current one ends — the host's collect / submit round trip is off the GPU's critical path.
@@ -103,31 +102,23 @@ struct Work {
   int32_t* f_map = nullptr;
   int f_cap_frames = 0;
   size_t f_cap_cones = 0;
-  PassTrailer* h_trailer = nullptr;  // N_TRAILERS of them: pinned, host-coherent, written by assemble_kernel
-  int trailer_idx = SLOT_QUEUE;      // which one the next pass writes: a ticket's entry index, or SLOT_QUEUE (resident / blocking passes)
+  PassTrailer* h_trailer = nullptr;  // N_TRAILERS of them: pinned, host-coherent, written by assemble_kernel: a ticket's entry
+                                     // index, or SLOT_QUEUE (resident / blocking passes)
   PassTrailer* d_trailer = nullptr;  // their device address
   int seq = 0;                       // passes launched on this slot
   // the most recent pass launched on the slot (verify_pass re-runs it with the route kernels when they were needed)
   const Inputs* pass_in = nullptr;
   bool ran_big = false, ran_retry = false, unverified = false, pass_skid = false;
-  fsdp_frame_result* result_dst = nullptr;  // where assemble_kernel writes the next pass's results: NULL = d_result; a ticket with a
-                                            // page-locked result buffer: that buffer, straight over PCIe (no copy command at all)
-  bool result_compact = false;              // ... as fsdp_compact_result records (fsdp_submit_compact)
   // tickets of fsdp_submit / fsdp_skidpad_submit queued on this slot's stream (id -1: free entry)
   struct Ticket {
     long long id = -1;
-    int n = 0;
     bool skid = false;
     bool pending = false;  // skidpad step whose path kernel waits for the rest of its group (flush_skid)
     int seq = 0;                       // the slot's pass counter of this ticket's pass (checked against its trailer)
     bool ran_big = false, ran_retry = false;
+    long long in_flight = 0;           // frames on the GPU the pass was planned for (launch_path; a repeated pass keeps them)
     // the caller's buffers: valid and untouched until fsdp_collect (a pass that has to be repeated reads them again)
-    const int32_t* off = nullptr;
-    const double* cones = nullptr;
-    const double* poses = nullptr;
-    const double* prev = nullptr;
-    size_t total = 0;
-    int max_cones = 0;
+    Batch batch;
     fsdp_frame_result* user_results = nullptr;
     fsdp_skidpad_info* user_info = nullptr;
     bool via_stage = false;                // results go through h_stage (the caller's buffer is pageable)
@@ -136,9 +127,8 @@ struct Work {
     size_t rec_bytes() const { return !compact ? sizeof(fsdp_frame_result) : (skid ? sizeof(PathOut) : sizeof(fsdp_compact_result)); }
     fsdp_frame_result* h_stage = nullptr;  // pinned + mapped: the assembly kernel writes a pageable caller's results here
     char* h_in = nullptr;                  // pinned + mapped: a small pageable batch is packed here and read by the sorting kernel itself
-    size_t cap_in = 0;
     SkidInfo* h_info = nullptr;            // pinned
-    int cap_stage = 0, cap_info = 0;
+    size_t cap_stage = 0, cap_in = 0, cap_info = 0;  // their capacities (grow_pinned)
     hipEvent_t done = nullptr;             // recorded behind the ticket's last command
   } tk[SLOT_QUEUE];
 };
@@ -153,7 +143,14 @@ struct fsdp_ctx {
   Inputs res;             // the resident batch of fsdp_upload (every slot's fsdp_run pass reads it)
   bool resident = false;  // res describes a batch fsdp_run may plan
   bool res_checked = false;  // a verified pass over the resident batch has set expect_big / expect_retry exactly
-  int last_n = 0;         // frames of the most recent full pass (what fsdp_download writes)
+  // The most recent pass (launch_pass, a skidpad step), what fsdp_download, fsdp_resident_frames and fsdp_debug_* read: they
+  // return data of exactly this pass or fail.  slot < 0: none, or its buffers were released / reused since.
+  struct LastPass {
+    int slot = -1;
+    int n = 0;               // its frames
+    bool in_result = false;  // its results are in the slot's result block (an fsdp_run / fsdp_time_runs pass)
+    bool whole = false;      // it covered the whole call (not a chunk of a blocking call)
+  } last;
   double* d_default_path = nullptr;  // (40,4)
   Params params;                     // configuration constants (fsdp_params) ...
   Params* d_params = nullptr;        // ... and their device copy, read by every kernel
@@ -169,7 +166,6 @@ struct fsdp_ctx {
   bool profile_sort = false;  // profiling build: which kernel fsdp_profile_path runs
   int overlap = 1;
   unsigned turn = 0;
-  int last_slot = 0;
   long long next_ticket = 0;
   int last_ticket_slot = -1;  // slot of the most recent ticket
   int outstanding = 0;  // tickets submitted and not yet collected
@@ -223,11 +219,11 @@ struct fsdp_ctx {
   int skid_pending[SKID_GROUP_MAX] = {};  // slots whose step waits for its group's launch, oldest first
   int n_skid_pending = 0;
   int n_instances = 0;
-  // pinned host staging of the stage-level entry points (hipHostMalloc; grown by ensure_staging)
+  // pinned host staging of the stage-level entry points (grow_pinned)
   SortOut* h_sort = nullptr;
   MatchOut* h_match = nullptr;
   PathOut* h_path = nullptr;
-  int cap_staging = 0;
+  size_t cap_sort = 0, cap_match = 0, cap_path = 0;
   // the sorting cache (fsdp_sort_cache_reset, sort_cache.h): one entry per planner in each of two buffers; the kernels of a
   // call read buffer cache_cur and write the other, and the call swaps them once it has succeeded
   int n_cache = 0;
@@ -307,6 +303,7 @@ static int ensure_work(fsdp_ctx* c, Work& w, int n) {
   }
   if (n <= w.cap_frames) return 0;
   HIP_TRY(c, hipStreamSynchronize(w.stream));
+  if (c->last.slot == w.index) c->last = fsdp_ctx::LastPass();  // (its results and scratch are about to go)
   const size_t m = (size_t)n;
   HIP_TRY(c, regrow(w.d_sort, m));
   HIP_TRY(c, regrow(w.d_match, m));
@@ -353,22 +350,19 @@ static void free_work(Work& w) {
   }
 }
 
-// pinned result staging of the stage-level entry points, n frames
-static int ensure_staging(fsdp_ctx* c, int n) {
-  if (n <= c->cap_staging) return 0;
-  if (c->h_sort) (void)hipHostFree(c->h_sort);
-  if (c->h_match) (void)hipHostFree(c->h_match);
-  if (c->h_path) (void)hipHostFree(c->h_path);
-  c->h_sort = nullptr;
-  c->h_match = nullptr;
-  c->h_path = nullptr;
-  c->cap_staging = 0;
-  const size_t want = (size_t)(n < 64 ? 64 : n);
-  HIP_TRY(c, hipHostMalloc((void**)&c->h_sort, sizeof(SortOut) * want, hipHostMallocDefault));
-  HIP_TRY(c, hipHostMalloc((void**)&c->h_match, sizeof(MatchOut) * want, hipHostMallocDefault));
-  HIP_TRY(c, hipHostMalloc((void**)&c->h_path, sizeof(PathOut) * want, hipHostMallocDefault));
-  c->cap_staging = (int)want;
-  return 0;
+// a page-locked host block `p` of `cap` T's holds at least `count` (the block is replaced, with room for at least `want`: what
+// it held is gone; nothing queued may use it any more).  flags: mapped where a kernel reads or writes the block, default where
+// only a copy command does.
+template <class T>
+static hipError_t grow_pinned(T*& p, size_t& cap, size_t count, unsigned flags, size_t want = 0) {
+  if (count <= cap) return hipSuccess;
+  if (p) (void)hipHostFree(p);
+  p = nullptr;
+  cap = 0;
+  want = std::max(count, want);
+  const hipError_t e = hipHostMalloc((void**)&p, sizeof(T) * want, flags);
+  if (e == hipSuccess) cap = want;
+  return e;
 }
 
 // p as the GPU addresses it if p is page-locked host memory (fsdp_host_alloc, fsdp_host_register: mapped into the device's
@@ -383,7 +377,6 @@ static void* device_view(const void* p) {
   }
   return a.type == hipMemoryTypeHost ? a.devicePointer : nullptr;
 }
-static bool is_pinned(const void* p) { return device_view(p) != nullptr; }
 // the whole extent [p, p + bytes) is page-locked and one mapping: a view that starts inside a registered range and runs past
 // its end would let a kernel read / write unmapped host memory (a device fault instead of an error code) — such a buffer
 // takes the pageable path (round-3 advisor)
@@ -393,6 +386,14 @@ static bool is_pinned(const void* p, size_t bytes) {
   if (bytes <= 1) return true;
   const char* de = (const char*)device_view((const char*)p + bytes - 1);
   return de != nullptr && de - dv == (ptrdiff_t)(bytes - 1);
+}
+// every row of the batch the staging kernels read (stage_in_kernel, sort_kernel's StageIn) is page-locked: the offsets, the cone
+// rows from cones + 3 * off[0], the poses and the previous paths
+static bool inputs_pinned(const Batch& b) {
+  const size_t n = (size_t)b.n;
+  return b.n > 0 && is_pinned(b.off, sizeof(int32_t) * (n + 1)) && is_pinned(b.poses, sizeof(double) * 4 * n) &&
+         (b.total == 0 || is_pinned(b.cones + 3 * (size_t)b.off[0], sizeof(double) * 3 * b.total)) &&
+         (!b.prev || is_pinned(b.prev, sizeof(double) * PATH_POINTS * 4 * n));
 }
 
 // ---- the kernels of one pass ----------------------------------------------------------------------------------------------
@@ -438,20 +439,8 @@ static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
   return v;
 }
 
-static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in) {
-  StageIn st;
-  if (in.h_off) {
-    st.src_off = in.h_off;
-    st.base = in.h_base;
-    st.src_cones = in.h_cones;
-    st.src_poses = in.h_poses;
-    st.src_prev = in.h_prev;
-    st.dst_off = in.d_off;
-    st.dst_cones = in.d_cones;
-    st.dst_poses = in.d_poses;
-    st.dst_prev = in.d_prev;
-    st.n_frames = in.n_frames;
-  }
+// st: the batch's stage-in (src_off != NULL: the kernel brings it onto the device itself)
+static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& st) {
   if (c->cache_call) {
     const SortCacheView v = cache_view(c, q);
     if (sort128(c, in))
@@ -545,7 +534,7 @@ static long long frames_in_flight(const fsdp_ctx* c, int n, bool ticket) {
   long long sum = n;
   for (int i = 0; i < FSDP_MAX_OVERLAP; i++)
     for (const Work::Ticket& t : c->slot[i].tk)
-      if (t.id >= 0 && !t.skid) sum += t.n;
+      if (t.id >= 0 && !t.skid) sum += t.batch.n;
   return sum;
 }
 
@@ -620,25 +609,39 @@ static void launch_path_retry(fsdp_ctx* c, Work& q, const Inputs& in, bool sized
   hipLaunchKernelGGL(path_retry_kernel, dim3(rb), dim3(WAVE), 0, q.stream, in.d_poses, q.d_match, c->d_default_path, prev, c->d_gpath,
                      c->n_gpath, q.d_arena, q.d_path, q.d_retry, c->d_params);
 }
-static void launch_assemble(fsdp_ctx* c, Work& q, int n, bool skid, fsdp_frame_result* dst = nullptr, hipStream_t stream = nullptr,
-                            const SkidInfo* info_src = nullptr, SkidInfo* info_dst = nullptr, const int32_t* remap = nullptr,
-                            const int32_t* remap_off = nullptr, bool compact = false) {
+// What a pass writes where, and where its sorting kernel finds the batch
+struct PassIO {
+  fsdp_frame_result* host = nullptr;  // NULL: results into the slot's result block; else the device view of a page-locked host buffer
+                                      // that assemble_kernel writes straight over PCIe (a ticket: no copy command at all)
+  bool compact = false;               // ... as fsdp_compact_result records (fsdp_submit_compact)
+  int trailer = SLOT_QUEUE;           // the pass's trailer: a ticket's entry index, or SLOT_QUEUE (resident / blocking passes)
+  SkidInfo* info = nullptr;           // skidpad: device view of the page-locked block the planners' information records go to
+  StageIn stage;                      // src_off != NULL: device views of the caller's page-locked batch, which the sorting kernel
+                                      // brings onto the device itself (sort_kernel.h StageIn)
+};
+
+// skid: a skidpad step's records (path stage only, on the context's stream)
+static void launch_assemble(fsdp_ctx* c, Work& q, int n, const PassIO& io, bool skid) {
   long long blocks = ((long long)n + 3) / 4;  // one wavefront per frame, four per workgroup (grid-stride beyond the cap)
   // results that go straight to host memory leave at the link's pace: a few hundred wavefronts keep it busy, more would
   // only sit on the SIMDs' wavefront slots with their stores pending while the other slots' kernels wait for a place
-  (void)c;
-  const long long cap = dst ? 128 : 16384;  // (32 / 128 / 512 workgroups towards host memory: 5.1 / 5.2 / 5.4 M frames/s streamed, inside the noise: profiles/r06_streaming_probe.txt)
+  const long long cap = io.host ? 128 : 16384;  // (32 / 128 / 512 workgroups towards host memory: 5.1 / 5.2 / 5.4 M frames/s streamed, inside the noise: profiles/r06_streaming_probe.txt)
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   q.seq++;
-  if (compact) {  // fsdp_compact_result records (into the slot's result block or the caller's page-locked buffer)
-    hipLaunchKernelGGL(assemble_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, stream ? stream : q.stream, n, q.d_sort, q.d_match, q.d_path,
-                       (fsdp_compact_result*)(dst ? dst : q.d_result), q.d_big, q.d_retry, q.d_trailer + q.trailer_idx, q.seq, remap, remap_off);
+  hipStream_t s = skid ? c->stream : q.stream;
+  const bool filtered = !skid && !c->params.use_unknown_cones;  // (indices back into the caller's cone lists: launch_filter's map)
+  const int32_t* remap = filtered ? q.f_map : nullptr;
+  const int32_t* remap_off = filtered ? q.f_off : nullptr;
+  if (io.compact) {  // fsdp_compact_result records (into the slot's result block or the caller's page-locked buffer)
+    hipLaunchKernelGGL(assemble_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, q.d_sort, q.d_match, q.d_path,
+                       (fsdp_compact_result*)(io.host ? io.host : q.d_result), q.d_big, q.d_retry, q.d_trailer + io.trailer, q.seq, remap, remap_off);
     return;
   }
-  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)blocks), dim3(256), 0, stream ? stream : q.stream, n, skid ? (const SortOut*)nullptr : q.d_sort,
-                     skid ? (const MatchOut*)nullptr : q.d_match, q.d_path, dst ? dst : q.d_result, q.d_big, q.d_retry, q.d_trailer + q.trailer_idx, q.seq,
-                     (const int32_t*)info_src, (int32_t*)info_dst, info_dst ? (int)(sizeof(SkidInfo) / 4) * n : 0, remap, remap_off);
+  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, skid ? (const SortOut*)nullptr : q.d_sort,
+                     skid ? (const MatchOut*)nullptr : q.d_match, q.d_path, io.host ? io.host : q.d_result, q.d_big, q.d_retry, q.d_trailer + io.trailer,
+                     q.seq, (const int32_t*)(io.info ? q.d_skid_info : nullptr), (int32_t*)io.info, io.info ? (int)(sizeof(SkidInfo) / 4) * n : 0,
+                     remap, remap_off);
 }
 
 // use_unknown_cones = False: the batch without its UNKNOWN cones into the slot's filter buffers; returns the view the
@@ -666,10 +669,11 @@ static int launch_filter(fsdp_ctx* c, Work& q, const Inputs& in, Inputs* view) {
   return 0;
 }
 
-// sorting -> matching -> path stage -> result assembly of batch `in` on slot q
+// sorting -> matching -> path stage -> result assembly of batch `in` on slot q; it becomes the context's most recent pass
 // in_flight: frames on the GPU while this pass runs, its own included (launch_path); < 0: a resident batch replayed through
 // every slot of the overlap depth
-static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, StageEvents* t = nullptr, bool force_routes = false, long long in_flight = -1) {
+static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io = PassIO(), StageEvents* t = nullptr, bool force_routes = false,
+                       long long in_flight = -1) {
   c->primed[q.index] = true;
   const bool with_big = force_routes || c->always_route || c->expect_big;
   const bool with_retry = force_routes || c->always_route || c->expect_retry;
@@ -692,7 +696,7 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, StageEvents* t =
     (void)hipMemsetAsync(q.d_retry + 1, 0xff, sizeof(int) * m, q.stream);
   }
   mark(q, t);
-  launch_sort(c, q, in);
+  launch_sort(c, q, in, io.stage);
   if (with_big) {
     mark(q, t);
     if (int rc = launch_sort_big(c, q, in)) return rc;
@@ -710,17 +714,16 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, StageEvents* t =
     names += "path_retry_kernel,";
   }
   mark(q, t, after_path);
-  launch_assemble(c, q, in.n_frames, false, q.result_dst, nullptr, nullptr, nullptr, filtered ? q.f_map : nullptr, filtered ? q.f_off : nullptr,
-                  q.result_compact);
+  launch_assemble(c, q, in.n_frames, io, false);
   names += "assemble_kernel";
   mark(q, t, MARK_LAST);
   c->stage_names = names;
   q.pass_in = &in_;
   q.ran_big = with_big;
   q.ran_retry = with_retry;
-  q.unverified = true;
+  q.unverified = io.trailer == SLOT_QUEUE;  // (a ticket's pass is settled by fsdp_collect, through the ticket's own trailer)
   q.pass_skid = false;
-  c->last_n = in.n_frames;
+  c->last = fsdp_ctx::LastPass{q.index, in.n_frames, io.host == nullptr, true};
   return 0;
 }
 
@@ -734,21 +737,10 @@ static PassTrailer read_trailer(const Work& q, int idx) {
   return tr;
 }
 
-// The slot's stream is idle: did its most recent pass get the route kernels it needed?  If not, the pass runs again with
-// both (same inputs, same slot; the caller copies results afterwards).  Also keeps the expectations up to date.
-// *rerun (optional) reports whether the pass was repeated.
-static int verify_pass(fsdp_ctx* c, Work& q, bool* rerun = nullptr) {
-  if (rerun) *rerun = false;
-  if (!q.unverified || q.pass_skid) {
-    q.unverified = false;
-    return 0;
-  }
-  q.unverified = false;
-  const PassTrailer tr = read_trailer(q, SLOT_QUEUE);
-  if (tr.seq != q.seq) {
-    c->err = "internal: pass trailer out of date (slot " + std::to_string(q.index) + ")";
-    return 2;
-  }
+// A pass's trailer against the routes it ran: keeps the expectations and the retry hint up to date — for a pass over the
+// resident batch exactly what that batch needs from now on, else with decay — and says whether the pass lacked a route
+// kernel it needed and must run again (with both).
+static bool settle_routes(fsdp_ctx* c, const PassTrailer& tr, bool ran_big, bool ran_retry, bool resident) {
   auto track = [](bool needed, bool& expect, int& clean) {
     if (needed) {
       expect = true;
@@ -759,7 +751,7 @@ static int verify_pass(fsdp_ctx* c, Work& q, bool* rerun = nullptr) {
     }
   };
   c->retry_hint = std::max(tr.n_retry, c->retry_hint - (c->retry_hint + 7) / 8);
-  if (q.pass_in == &c->res) {  // the resident batch: from now on its passes carry exactly the routes it needs
+  if (resident) {
     c->expect_big = tr.n_big > 0;
     c->expect_retry = tr.n_retry > 0;
     c->clean_big = c->clean_retry = 0;
@@ -768,13 +760,29 @@ static int verify_pass(fsdp_ctx* c, Work& q, bool* rerun = nullptr) {
     track(tr.n_big > 0, c->expect_big, c->clean_big);
     track(tr.n_retry > 0, c->expect_retry, c->clean_retry);
   }
-  if ((tr.n_big > 0 && !q.ran_big) || (tr.n_retry > 0 && !q.ran_retry)) {
-    c->reruns++;
-    if (int rc = launch_pass(c, q, *q.pass_in, nullptr, true)) return rc;
+  const bool rerun = (tr.n_big > 0 && !ran_big) || (tr.n_retry > 0 && !ran_retry);
+  if (rerun) c->reruns++;
+  return rerun;
+}
+
+// The slot's stream is idle: did its most recent pass get the route kernels it needed?  If not, the pass runs again with
+// both (same inputs, same slot; the caller copies results afterwards).
+static int verify_pass(fsdp_ctx* c, Work& q) {
+  if (!q.unverified || q.pass_skid) {
+    q.unverified = false;
+    return 0;
+  }
+  q.unverified = false;
+  const PassTrailer tr = read_trailer(q, SLOT_QUEUE);
+  if (tr.seq != q.seq) {
+    c->err = "internal: pass trailer out of date (slot " + std::to_string(q.index) + ")";
+    return 2;
+  }
+  if (settle_routes(c, tr, q.ran_big, q.ran_retry, q.pass_in == &c->res)) {
+    if (int rc = launch_pass(c, q, *q.pass_in, PassIO(), nullptr, true)) return rc;
     HIP_TRY(c, hipStreamSynchronize(q.stream));
     HIP_TRY(c, hipGetLastError());
     q.unverified = false;
-    if (rerun) *rerun = true;
   }
   return 0;
 }
@@ -835,8 +843,8 @@ static void assemble(const SortOut* s, const MatchOut* m, const PathOut* p, fsdp
   }
 }
 
-// validate a batch description; fills max_cones
-static int check_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, size_t* total, int* max_cones) {
+// validate a batch description into *b (prev: optional previous paths)
+static int check_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev, Batch* b) {
   if (n_frames < 0 || (n_frames > 0 && (!off || !poses))) {
     c->err = "batch: NULL offsets / poses";
     return 1;
@@ -847,8 +855,7 @@ static int check_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
     c->err = "cone_offsets[0] must be >= 0";
     return 1;
   }
-  *total = n_frames > 0 ? (size_t)(off[n_frames] - off[0]) : 0;
-  *max_cones = 0;
+  *b = Batch{n_frames, off, cones, poses, prev, n_frames > 0 ? (size_t)(off[n_frames] - off[0]) : 0, 0};
   if (n_frames > 0 && off[n_frames] < off[0]) {
     c->err = "cone_offsets must be non-decreasing";
     return 1;
@@ -859,49 +866,58 @@ static int check_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
       c->err = "cone_offsets must be non-decreasing";
       return 1;
     }
-    *max_cones = std::max(*max_cones, d);
+    b->max_cones = std::max(b->max_cones, d);
   }
-  if (*total > 0 && !cones) {
+  if (b->total > 0 && !cones) {
     c->err = "cones_xyt is NULL";
     return 1;
   }
   return 0;
 }
 
-// host -> device of a batch on `stream` (asynchronous for page-locked sources)
-static int upload_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, int n_frames, const int32_t* off, const double* cones, const double* poses,
-                         const double* prev, size_t total, int max_cones) {
-  if (int rc = ensure_inputs(c, in, n_frames > 0 ? n_frames : 1, total, prev != nullptr)) return rc;
-  in.n_frames = n_frames;
-  in.max_cones = max_cones;
-  in.use_prev = prev != nullptr;
-  if (n_frames == 0) return 0;
-  (void)rebase_batch(in, n_frames, off, cones);
-  HIP_TRY(c, hipMemcpyAsync(in.d_off, off, sizeof(int32_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, stream));
-  if (total) HIP_TRY(c, hipMemcpyAsync(in.d_cones, cones, sizeof(double) * 3 * total, hipMemcpyHostToDevice, stream));
-  HIP_TRY(c, hipMemcpyAsync(in.d_poses, poses, sizeof(double) * 4 * (size_t)n_frames, hipMemcpyHostToDevice, stream));
-  if (prev) HIP_TRY(c, hipMemcpyAsync(in.d_prev, prev, sizeof(double) * PATH_POINTS * 4 * (size_t)n_frames, hipMemcpyHostToDevice, stream));
+// room for batch b in `in`, which then describes it (the caller fills the buffers)
+static int take_batch(fsdp_ctx* c, Inputs& in, const Batch& b) {
+  if (int rc = ensure_inputs(c, in, b.n > 0 ? b.n : 1, b.total, b.prev != nullptr)) return rc;
+  in.n_frames = b.n;
+  in.max_cones = b.max_cones;
+  in.use_prev = b.prev != nullptr;
   return 0;
 }
 
-// the same through stage_in_kernel: every source is page-locked host memory
-static int stage_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, int n_frames, const int32_t* off, const double* cones, const double* poses,
-                        const double* prev, size_t total, int max_cones) {
-  if (int rc = ensure_inputs(c, in, n_frames > 0 ? n_frames : 1, total, prev != nullptr)) return rc;
-  in.n_frames = n_frames;
-  in.max_cones = max_cones;
-  in.use_prev = prev != nullptr;
-  if (n_frames == 0) return 0;
+// host -> device of a batch on `stream` (asynchronous for page-locked sources)
+static int upload_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, const Batch& b) {
+  if (int rc = take_batch(c, in, b)) return rc;
+  if (b.n == 0) return 0;
+  const int32_t* off = b.off;
+  const double* cones = b.cones;
+  if (off[0] != 0) {
+    // a slice of a larger batch: the offsets rebased to 0 (the slot's own pageable copy) and the cones from the slice's first row
+    in.off_rebased.resize((size_t)b.n + 1);
+    for (int i = 0; i <= b.n; i++) in.off_rebased[(size_t)i] = off[i] - off[0];
+    if (cones) cones += 3 * (size_t)off[0];
+    off = in.off_rebased.data();
+  }
+  HIP_TRY(c, hipMemcpyAsync(in.d_off, off, sizeof(int32_t) * ((size_t)b.n + 1), hipMemcpyHostToDevice, stream));
+  if (b.total) HIP_TRY(c, hipMemcpyAsync(in.d_cones, cones, sizeof(double) * 3 * b.total, hipMemcpyHostToDevice, stream));
+  HIP_TRY(c, hipMemcpyAsync(in.d_poses, b.poses, sizeof(double) * 4 * (size_t)b.n, hipMemcpyHostToDevice, stream));
+  if (b.prev) HIP_TRY(c, hipMemcpyAsync(in.d_prev, b.prev, sizeof(double) * PATH_POINTS * 4 * (size_t)b.n, hipMemcpyHostToDevice, stream));
+  return 0;
+}
+
+// the same through stage_in_kernel: every source is page-locked host memory (inputs_pinned)
+static int stage_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, const Batch& b) {
+  if (int rc = take_batch(c, in, b)) return rc;
+  if (b.n == 0) return 0;
   CopySegs S;
   S.n = 0;
   // a slice of a larger batch (cone_offsets[0] = b > 0): the kernel subtracts b from the offsets on their way in and the cones
   // are read from row b — nothing is rebased or copied on the host, nothing pageable is handed to the runtime (round-5 advisor:
   // a pageable copy made the host wait for the stream's earlier work)
-  S.rebase = off[0];
-  S.seg[S.n++] = CopySeg{device_view(off), in.d_off, sizeof(int32_t) * ((unsigned long long)n_frames + 1)};
-  if (total) S.seg[S.n++] = CopySeg{device_view(cones + 3 * (size_t)off[0]), in.d_cones, sizeof(double) * 3ull * total};
-  S.seg[S.n++] = CopySeg{device_view(poses), in.d_poses, sizeof(double) * 4ull * (unsigned long long)n_frames};
-  if (prev) S.seg[S.n++] = CopySeg{device_view(prev), in.d_prev, sizeof(double) * PATH_POINTS * 4ull * (unsigned long long)n_frames};
+  S.rebase = b.off[0];
+  S.seg[S.n++] = CopySeg{device_view(b.off), in.d_off, sizeof(int32_t) * ((unsigned long long)b.n + 1)};
+  if (b.total) S.seg[S.n++] = CopySeg{device_view(b.cones + 3 * (size_t)b.off[0]), in.d_cones, sizeof(double) * 3ull * b.total};
+  S.seg[S.n++] = CopySeg{device_view(b.poses), in.d_poses, sizeof(double) * 4ull * (unsigned long long)b.n};
+  if (b.prev) S.seg[S.n++] = CopySeg{device_view(b.prev), in.d_prev, sizeof(double) * PATH_POINTS * 4ull * (unsigned long long)b.n};
   hipLaunchKernelGGL(stage_in_kernel, dim3(256), dim3(256), 0, stream, S);
   return 0;
 }
@@ -1200,16 +1216,14 @@ int fsdp_upload(fsdp_ctx* c, int n_frames, const int32_t* off, const double* con
   if (!c) return 1;
   if (c->outstanding) return busy_error(c, "fsdp_upload");
   HIP_TRY(c, hipSetDevice(c->device));
-  size_t total;
-  int max_cones;
-  if (int rc = check_batch(c, n_frames, off, cones, poses, &total, &max_cones)) return rc;
+  Batch b;
+  if (int rc = check_batch(c, n_frames, off, cones, poses, nullptr, &b)) return rc;
   if (int rc = sync_all(c)) return rc;  // passes in flight still read the old inputs
   if (int rc = ensure_slots(c, n_frames > 0 ? n_frames : 1)) return rc;
-  if (int rc = upload_inputs(c, c->res, c->stream, n_frames, off, cones, poses, nullptr, total, max_cones)) return rc;
+  if (int rc = upload_inputs(c, c->res, c->stream, b)) return rc;
   c->resident = true;
   c->res_checked = false;
-  c->last_slot = 0;
-  c->last_n = n_frames;
+  c->last = fsdp_ctx::LastPass();  // (no pass has planned this batch yet)
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the other slots' streams read these inputs too; the caller's buffers are free again
   return 0;
 }
@@ -1233,7 +1247,7 @@ int fsdp_set_overlap(fsdp_ctx* c, int depth) {
   }
   c->overlap = depth;
   c->turn = 0;
-  c->last_slot = 0;
+  if (c->last.slot >= depth) c->last = fsdp_ctx::LastPass();  // (released above)
   c->last_ticket_slot = -1;
   for (bool& p : c->primed) p = false;  // the kernels of a pass depend on the frames in flight (launch_path)
   return ensure_slots(c, std::max(1, c->slot[0].cap_frames));
@@ -1256,13 +1270,12 @@ int fsdp_run(fsdp_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(q.stream));
     if (int rc = verify_pass(c, q)) return rc;
   }
-  c->last_slot = si;
   if (int rc = launch_pass(c, q, c->res)) return rc;
   HIP_TRY(c, hipGetLastError());
   return 0;
 }
 
-int fsdp_resident_frames(const fsdp_ctx* c) { return c ? c->last_n : 0; }
+int fsdp_resident_frames(const fsdp_ctx* c) { return c ? c->last.n : 0; }
 
 int fsdp_sync(fsdp_ctx* c) {
   if (!c) return 1;
@@ -1271,13 +1284,18 @@ int fsdp_sync(fsdp_ctx* c) {
 }
 
 int fsdp_download(fsdp_ctx* c, fsdp_frame_result* results) {
-  if (!c || (c->last_n > 0 && !results)) return 1;
+  if (!c) return 1;
   if (c->outstanding) return busy_error(c, "fsdp_download");
-  const int n = c->last_n;
-  if (n == 0) return 0;
+  if (c->last.slot < 0 || !c->last.in_result) {
+    c->err = "fsdp_download: the most recent pass left no results on the device (it was a ticket, a blocking call or a skidpad step, or no "
+             "fsdp_run has followed fsdp_upload / fsdp_set_overlap)";
+    return 1;
+  }
+  const int n = c->last.n;
+  if (!results) return 1;
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
-  Work& q = c->slot[c->last_slot];  // the most recent pass
+  Work& q = c->slot[c->last.slot];  // the most recent pass
   HIP_TRY(c, hipMemcpyAsync(results, q.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   return 0;
@@ -1336,70 +1354,56 @@ static Work::Ticket* find_ticket(fsdp_ctx* c, long long ticket, Work** slot) {
   return nullptr;
 }
 
-// enqueue ticket t's batch on slot q: inputs, the pass with its results' way back, the ticket's event
-// in_flight: frames on the GPU next to this batch, its own included (< 0: counted from the outstanding tickets)
+// enqueue ticket t's batch on slot q: inputs, the pass with its results' way back, the ticket's event (the pass is planned for
+// t.in_flight frames on the GPU)
 // A pageable batch of up to SMALL_BATCH_BYTES is packed into the ticket's own page-locked block by the host (a memcpy of a few KB)
 // and then treated like any page-locked batch: the sorting kernel reads it over PCIe, no copy command is issued at all — three or
 // four hipMemcpyAsync calls from pageable memory cost a single-frame call ~30 us of its ~860.
 constexpr size_t SMALL_BATCH_BYTES = 256 * 1024;
 
-static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_routes, long long in_flight = -1) {
-  const int n = t.n;
+static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_routes) {
+  Batch b = t.batch;
+  const int n = b.n;
   // a bigger batch than the slot has seen: its buffers are replaced — not under the feet of the passes queued on the stream
-  if (n > q.cap_frames || n > q.in.cap_frames || t.total > q.in.cap_cones || (t.prev && n > q.in.cap_prev)) HIP_TRY(c, hipStreamSynchronize(q.stream));
+  if (n > q.cap_frames || n > q.in.cap_frames || b.total > q.in.cap_cones || (b.prev && n > q.in.cap_prev)) HIP_TRY(c, hipStreamSynchronize(q.stream));
   if (int rc = ensure_work(c, q, n > 0 ? n : 1)) return rc;
-  const int32_t* off = t.off;
-  const double* cones = t.cones;
-  const double* poses = t.poses;
-  const double* prev = t.prev;
-  bool in_pinned = n > 0 && is_pinned(off, sizeof(int32_t) * ((size_t)n + 1)) && is_pinned(poses, sizeof(double) * 4 * (size_t)n) &&
-                   (t.total == 0 || is_pinned(cones + 3 * (size_t)off[0], sizeof(double) * 3 * t.total)) &&
-                   (!prev || is_pinned(prev, sizeof(double) * PATH_POINTS * 4 * (size_t)n));
-  const size_t off_bytes = (sizeof(int32_t) * ((size_t)n + 1) + 15) & ~(size_t)15, cone_bytes = sizeof(double) * 3 * t.total,
-               pose_bytes = sizeof(double) * 4 * (size_t)n, prev_bytes = prev ? sizeof(double) * PATH_POINTS * 4 * (size_t)n : 0;
+  bool in_pinned = inputs_pinned(b);
+  const size_t off_bytes = (sizeof(int32_t) * ((size_t)n + 1) + 15) & ~(size_t)15, cone_bytes = sizeof(double) * 3 * b.total,
+               pose_bytes = sizeof(double) * 4 * (size_t)n, prev_bytes = b.prev ? sizeof(double) * PATH_POINTS * 4 * (size_t)n : 0;
   const size_t in_bytes = off_bytes + cone_bytes + pose_bytes + prev_bytes;
   if (!in_pinned && n > 0 && in_bytes <= SMALL_BATCH_BYTES) {
-    if (in_bytes > t.cap_in) {
-      // (the block's previous user — this ticket entry's previous batch — was collected before the entry was handed out again)
-      if (t.h_in) (void)hipHostFree(t.h_in);
-      t.h_in = nullptr;
-      t.cap_in = 0;
-      const size_t want = std::max(in_bytes, (size_t)16384);
-      HIP_TRY(c, hipHostMalloc((void**)&t.h_in, want, hipHostMallocMapped));
-      t.cap_in = want;
-    }
+    // (the block's previous user — this ticket entry's previous batch — was collected before the entry was handed out again)
+    HIP_TRY(c, grow_pinned(t.h_in, t.cap_in, in_bytes, hipHostMallocMapped, 16384));
     int32_t* so = (int32_t*)t.h_in;
     double* sc = (double*)(t.h_in + off_bytes);
     double* sp = (double*)(t.h_in + off_bytes + cone_bytes);
     double* sv = (double*)(t.h_in + off_bytes + cone_bytes + pose_bytes);
-    const int32_t b = off[0];
-    for (int i = 0; i <= n; i++) so[i] = off[i] - b;
-    if (cone_bytes) memcpy(sc, cones + 3 * (size_t)b, cone_bytes);
-    memcpy(sp, poses, pose_bytes);
-    if (prev) memcpy(sv, prev, prev_bytes);
-    off = so;
-    cones = sc;
-    poses = sp;
-    prev = prev ? sv : nullptr;
+    for (int i = 0; i <= n; i++) so[i] = b.off[i] - b.off[0];
+    if (cone_bytes) memcpy(sc, b.cones + 3 * (size_t)b.off[0], cone_bytes);
+    memcpy(sp, b.poses, pose_bytes);
+    if (b.prev) memcpy(sv, b.prev, prev_bytes);
+    b = Batch{n, so, sc, sp, b.prev ? sv : nullptr, b.total, b.max_cones};
     in_pinned = true;
   }
-  const bool out_pinned = n > 0 && is_pinned(t.user_results, t.rec_bytes() * (size_t)n);
-  q.in.h_off = nullptr;
+  PassIO io;
   if (in_pinned && c->params.use_unknown_cones) {
     // the pass's sorting kernel reads the batch from the page-locked buffers and leaves the device copies (StageIn)
-    if (int rc = ensure_inputs(c, q.in, n, t.total, prev != nullptr)) return rc;
-    q.in.n_frames = n;
-    q.in.max_cones = t.max_cones;
-    q.in.use_prev = prev != nullptr;
-    q.in.h_off = (const int32_t*)device_view(off);
-    q.in.h_base = off[0];
-    // (the view of the slice's first row, addressed by offsets relative to h_base; never read when total = 0)
-    q.in.h_cones = t.total ? (const double*)device_view(cones + 3 * (size_t)off[0]) : (const double*)device_view(poses);
-    q.in.h_poses = (const double*)device_view(poses);
-    q.in.h_prev = prev ? (const double*)device_view(prev) : nullptr;
+    if (int rc = take_batch(c, q.in, b)) return rc;
+    StageIn& st = io.stage;
+    st.src_off = (const int32_t*)device_view(b.off);
+    st.base = b.off[0];
+    // (the view of the slice's first row, addressed by offsets relative to base; never read when total = 0)
+    st.src_cones = (const double*)device_view(b.total ? b.cones + 3 * (size_t)b.off[0] : b.poses);
+    st.src_poses = (const double*)device_view(b.poses);
+    st.src_prev = b.prev ? (const double*)device_view(b.prev) : nullptr;
+    st.dst_off = q.in.d_off;
+    st.dst_cones = q.in.d_cones;
+    st.dst_poses = q.in.d_poses;
+    st.dst_prev = q.in.d_prev;
+    st.n_frames = n;
   } else if (in_pinned) {
-    if (int rc = stage_inputs(c, q.in, q.stream, n, off, cones, poses, prev, t.total, t.max_cones)) return rc;
-  } else if (int rc = upload_inputs(c, q.in, q.stream, n, off, cones, poses, prev, t.total, t.max_cones)) {
+    if (int rc = stage_inputs(c, q.in, q.stream, b)) return rc;
+  } else if (int rc = upload_inputs(c, q.in, q.stream, b)) {
     return rc;
   }
   t.via_stage = false;
@@ -1407,32 +1411,19 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     // Results always leave the GPU inside the pass's last kernel, written over PCIe into page-locked memory: the caller's own buffer,
     // or — for a pageable one — the ticket's block, which fsdp_collect copies out (no copy command on the stream either way).
     fsdp_frame_result* dst = t.user_results;
-    if (!out_pinned) {
-      if (n > t.cap_stage) {
-        if (t.h_stage) (void)hipHostFree(t.h_stage);
-        t.h_stage = nullptr;
-        t.cap_stage = 0;
-        const int want = std::max(n, 64);
-        HIP_TRY(c, hipHostMalloc((void**)&t.h_stage, sizeof(fsdp_frame_result) * (size_t)want, hipHostMallocMapped));
-        t.cap_stage = want;
-      }
+    if (!is_pinned(t.user_results, t.rec_bytes() * (size_t)n)) {
+      HIP_TRY(c, grow_pinned(t.h_stage, t.cap_stage, (size_t)n, hipHostMallocMapped, 64));
       dst = t.h_stage;
       t.via_stage = true;
     }
-    q.result_dst = (fsdp_frame_result*)device_view(dst);
-    if (!q.result_dst) {
+    io.host = (fsdp_frame_result*)device_view(dst);
+    if (!io.host) {
       c->err = "internal: result block is not mapped into the device's address space";
       return 2;
     }
-    q.result_compact = t.compact;
-    q.trailer_idx = (int)(&t - q.tk);  // the ticket's own trailer
-    const int rc = launch_pass(c, q, q.in, nullptr, force_routes, in_flight >= 0 ? in_flight : frames_in_flight(c, n, true));
-    q.result_dst = nullptr;
-    q.result_compact = false;
-    q.trailer_idx = SLOT_QUEUE;
-    q.in.h_off = nullptr;  // (the views served that one sorting launch)
-    q.unverified = false;  // settled by fsdp_collect through the ticket
-    if (rc) return rc;
+    io.compact = t.compact;
+    io.trailer = (int)(&t - q.tk);  // the ticket's own trailer
+    if (int rc = launch_pass(c, q, q.in, io, nullptr, force_routes, t.in_flight)) return rc;
     t.seq = q.seq;
     t.ran_big = q.ran_big;
     t.ran_retry = q.ran_retry;
@@ -1456,9 +1447,8 @@ static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
     return 1;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  size_t total;
-  int max_cones;
-  if (int rc = check_batch(c, n_frames, off, cones, poses, &total, &max_cones)) return rc;
+  Batch b;
+  if (int rc = check_batch(c, n_frames, off, cones, poses, prev_paths, &b)) return rc;
   // the slot with the fewest tickets queued, starting from the one after the previous ticket's (in-order traffic: round robin)
   int si = -1, best = SLOT_QUEUE;
   long long oldest = -1;
@@ -1492,14 +1482,9 @@ static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
     HIP_TRY(c, hipStreamSynchronize(q.stream));
     if (int rc = verify_pass(c, q)) return rc;
   }
-  t->n = n_frames;
+  t->batch = b;
   t->skid = false;
-  t->off = off;
-  t->cones = cones;
-  t->poses = poses;
-  t->prev = prev_paths;
-  t->total = total;
-  t->max_cones = max_cones;
+  t->in_flight = frames_in_flight(c, n_frames, true);
   t->user_results = results;
   t->user_info = nullptr;
   t->compact = compact;
@@ -1515,7 +1500,6 @@ static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
   }
   t->id = c->next_ticket++;
   c->outstanding++;
-  c->last_slot = si;
   *ticket = t->id;
   return 0;
 }
@@ -1560,36 +1544,21 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
     c->err = std::string("fsdp_collect: ") + hipGetErrorString(e);
     rc = 2;
   }
-  const int n = t.n;
+  const int n = t.batch.n;
   if (rc == 0 && n > 0 && !t.skid) {
     // did the pass get the route kernels it needed?  (its own trailer: later passes of the slot write other ones)
     const PassTrailer tr = read_trailer(q, (int)(&t - q.tk));
     if (tr.seq != t.seq) {
       c->err = "internal: trailer of ticket " + std::to_string(ticket) + " overwritten";
       rc = 2;
-    } else {
-      auto track = [](bool needed, bool& expect, int& clean) {
-        if (needed) {
-          expect = true;
-          clean = 0;
-        } else if (expect && ++clean >= ROUTE_DECAY) {
-          expect = false;
-          clean = 0;
-        }
-      };
-      track(tr.n_big > 0, c->expect_big, c->clean_big);
-      track(tr.n_retry > 0, c->expect_retry, c->clean_retry);
-      c->retry_hint = std::max(tr.n_retry, c->retry_hint - (c->retry_hint + 7) / 8);
-      if ((tr.n_big > 0 && !t.ran_big) || (tr.n_retry > 0 && !t.ran_retry)) {
-        // the whole ticket once more, with both route kernels, behind whatever the slot's stream holds by now (the
-        // caller's buffers are still his to leave alone: the batch is read again from them)
-        c->reruns++;
-        rc = enqueue_ticket(c, q, t, true);
-        if (rc != 0) (void)hipStreamSynchronize(q.stream);  // (nothing of the repeated pass is left running over the caller's buffers)
-        if (rc == 0 && (e = hipEventSynchronize(t.done)) != hipSuccess) {
-          c->err = std::string("fsdp_collect: ") + hipGetErrorString(e);
-          rc = 2;
-        }
+    } else if (settle_routes(c, tr, t.ran_big, t.ran_retry, false)) {
+      // the whole ticket once more, with both route kernels and the kernels of its first pass, behind whatever the slot's
+      // stream holds by now (the caller's buffers are still his to leave alone: the batch is read again from them)
+      rc = enqueue_ticket(c, q, t, true);
+      if (rc != 0) (void)hipStreamSynchronize(q.stream);  // (nothing of the repeated pass is left running over the caller's buffers)
+      if (rc == 0 && (e = hipEventSynchronize(t.done)) != hipSuccess) {
+        c->err = std::string("fsdp_collect: ") + hipGetErrorString(e);
+        rc = 2;
       }
     }
   }
@@ -1650,17 +1619,15 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
     return 1;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  size_t total;
-  int max_cones;
-  if (int rc = check_batch(c, n_frames, off, cones, poses, &total, &max_cones)) return rc;
+  Batch b;
+  if (int rc = check_batch(c, n_frames, off, cones, poses, prev, &b)) return rc;
   const bool cached = sequential && c->n_cache > 0;
   if (cached && n_frames != c->n_cache) return cache_prepare(c, n_frames, off, "fsdp_plan_batch_sequential");
   if (int rc = sync_all(c)) return rc;
   if (cached)
     if (int rc = cache_prepare(c, n_frames, off, "fsdp_plan_batch_sequential")) return rc;
   const CacheCall cache_call(c, cached);
-  c->last_slot = 0;
-  c->last_n = n_frames;
+  c->last = fsdp_ctx::LastPass();
   if (n_frames == 0) return 0;
   const int chunks = c->plan_chunks > 0 ? std::max(1, std::min(c->plan_chunks, n_frames / PLAN_CHUNK_MIN)) : (n_frames >= PLAN_CHUNK_FROM ? PLAN_CHUNKS : 1);
   const size_t rec = compact ? sizeof(fsdp_compact_result) : sizeof(fsdp_frame_result);
@@ -1672,18 +1639,13 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
     Work::Ticket& t = q.tk[0];
     if ((rc = ensure_work(c, q, hi - lo))) break;
     q.cache_base = lo;  // (the chunk's frames are planners lo..hi-1 of the sorting cache)
-    t.n = hi - lo;
+    t.batch = b.slice(lo, hi);
     t.skid = false;
-    t.off = off + lo;
-    t.cones = cones;
-    t.poses = poses + 4 * (size_t)lo;
-    t.prev = prev ? prev + (size_t)PATH_POINTS * 4 * (size_t)lo : nullptr;
-    t.total = (size_t)(off[hi] - off[lo]);
-    t.max_cones = max_cones;
+    t.in_flight = n_frames;
     t.user_results = (fsdp_frame_result*)((char*)results + rec * (size_t)lo);
     t.user_info = nullptr;
     t.compact = compact;
-    if ((rc = enqueue_ticket(c, q, t, false, n_frames))) {
+    if ((rc = enqueue_ticket(c, q, t, false))) {
       (void)hipStreamSynchronize(q.stream);
       (void)hipGetLastError();
       t.user_results = nullptr;
@@ -1692,13 +1654,12 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
     }
     t.id = ids[issued++] = c->next_ticket++;
     c->outstanding++;
-    c->last_slot = k;
-    c->last_n = hi - lo;
   }
   for (int k = 0; k < issued; k++) {
     const int rck = fsdp_collect(c, ids[k]);  // (every issued chunk is waited for, also after an error: the buffers are the caller's again)
     if (rc == 0) rc = rck;
   }
+  if (chunks > 1) c->last.whole = false;  // (the most recent pass is one chunk)
   c->next_ticket -= issued;  // (the chunks' numbers were internal: the caller's tickets keep counting up from where they were)
   if (rc == 0 && cached) rc = cache_finish(c);  // (once, after every chunk; a failed call leaves the previous entries in place)
   return rc;
@@ -1970,7 +1931,6 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
   for (int it = 0; it < iters; it++) {
     const int si = (c->overlap > 1) ? (int)(c->turn++ % (unsigned)c->overlap) : 0;
     Work& q = c->slot[si];
-    c->last_slot = si;
     if (!started[si] && si != 0) HIP_TRY(c, hipStreamWaitEvent(q.stream, ev_begin, 0));
     started[si] = true;
     StageEvents t;
@@ -1980,7 +1940,7 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
     // timed without them are the production launches)
     t.clock_first = c->time_kernel_clock ? c->d_kclock + it : nullptr;
     t.clock_last = c->time_kernel_clock ? c->d_kclock + c->kclock_cap + it : nullptr;
-    if ((rc = launch_pass(c, q, c->res, &t))) return rc;
+    if ((rc = launch_pass(c, q, c->res, PassIO(), &t))) return rc;
     n_stages = t.n - 1;
     c->tev_recorded[it] = t.recorded;
     last_of_slot[si] = it;
@@ -2038,14 +1998,19 @@ int fsdp_stage_names(fsdp_ctx* c, char* out, int cap) {
 }
 
 // ---- stage-level entry points (host buffers, blocking, slot 0; the route kernels always run) ---------------------------
+// their slot, whose buffers then no longer hold the most recent pass
+static Work& stage_slot(fsdp_ctx* c) {
+  if (c->last.slot == 0) c->last = fsdp_ctx::LastPass();
+  return c->slot[0];
+}
+
 int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
                     fsdp_frame_result* results) {
   if (!c) return 1;
   if (c->outstanding) return busy_error(c, "fsdp_sort_batch");
   HIP_TRY(c, hipSetDevice(c->device));
-  size_t total;
-  int max_cones;
-  if (int rc = check_batch(c, n_frames, off, cones, poses, &total, &max_cones)) return rc;
+  Batch b;
+  if (int rc = check_batch(c, n_frames, off, cones, poses, nullptr, &b)) return rc;
   const bool cached = c->n_cache > 0;
   if (cached && n_frames != c->n_cache) return cache_prepare(c, n_frames, off, "fsdp_sort_batch");
   if (n_frames == 0) return 0;
@@ -2053,24 +2018,24 @@ int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double*
   if (cached)
     if (int rc = cache_prepare(c, n_frames, off, "fsdp_sort_batch")) return rc;
   const CacheCall cache_call(c, cached);
-  Work& q = c->slot[0];
+  Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
-  if (int rc = upload_inputs(c, q.in, q.stream, n_frames, off, cones, poses, nullptr, total, max_cones)) return rc;
+  if (int rc = upload_inputs(c, q.in, q.stream, b)) return rc;
   Inputs fin;
   const bool filtered = !c->params.use_unknown_cones;
   if (filtered)
     if (int rc = launch_filter(c, q, q.in, &fin)) return rc;
   const Inputs& in = filtered ? fin : q.in;
-  launch_sort(c, q, in);
+  launch_sort(c, q, in, StageIn());
   if (int rc = launch_sort_big(c, q, in)) return rc;
   HIP_TRY(c, hipMemsetAsync(q.d_big, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
-  if (int rcs = ensure_staging(c, n_frames)) return rcs;
+  HIP_TRY(c, grow_pinned(c->h_sort, c->cap_sort, (size_t)n_frames, hipHostMallocDefault, 64));
   HIP_TRY(c, hipMemcpyAsync(c->h_sort, q.d_sort, sizeof(SortOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
   std::vector<int32_t> map, moff;
   if (filtered) {  // indices back into the caller's index space (what assemble_kernel does for a full pass)
-    map.resize(total ? total : 1);
+    map.resize(b.total ? b.total : 1);
     moff.resize((size_t)n_frames + 1);
-    HIP_TRY(c, hipMemcpyAsync(map.data(), q.f_map, sizeof(int32_t) * total, hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(map.data(), q.f_map, sizeof(int32_t) * b.total, hipMemcpyDeviceToHost, q.stream));
     HIP_TRY(c, hipMemcpyAsync(moff.data(), q.f_off, sizeof(int32_t) * ((size_t)n_frames + 1), hipMemcpyDeviceToHost, q.stream));
   }
   HIP_TRY(c, hipStreamSynchronize(q.stream));
@@ -2131,12 +2096,12 @@ int fsdp_match_batch(fsdp_ctx* c, int n_frames, const double* sorted_left, const
     off[f + 1] = off[f] + nl + nr;
   }
   if (int rc = sync_all(c)) return rc;
-  Work& q = c->slot[0];
+  Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
-  if (int rc = upload_inputs(c, q.in, q.stream, n_frames, off.data(), cones.data(), poses, nullptr, cones.size() / 3, 2 * MAX_LEN)) return rc;
+  if (int rc = upload_inputs(c, q.in, q.stream, Batch{n_frames, off.data(), cones.data(), poses, nullptr, cones.size() / 3, 2 * MAX_LEN})) return rc;
   HIP_TRY(c, hipMemcpyAsync(q.d_sort, so.data(), sizeof(SortOut) * n_frames, hipMemcpyHostToDevice, q.stream));
   launch_match(c, q, q.in);
-  if (int rcs = ensure_staging(c, n_frames)) return rcs;
+  HIP_TRY(c, grow_pinned(c->h_match, c->cap_match, (size_t)n_frames, hipHostMallocDefault, 64));
   HIP_TRY(c, hipMemcpyAsync(c->h_match, q.d_match, sizeof(MatchOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   for (int i = 0; i < n_frames; i++) {
@@ -2178,7 +2143,7 @@ static int path_batch_impl(fsdp_ctx* c, int n_frames, const double* poses, const
     c->params.centers_cap = centers_cap;
     HIP_TRY(c, hipMemcpy(c->d_params, &c->params, sizeof(Params), hipMemcpyHostToDevice));
   }
-  Work& q = c->slot[0];
+  Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
   if (int rc = ensure_inputs(c, q.in, n_frames, 1, prev_paths != nullptr)) return rc;
   std::vector<MatchOut> mo(n_frames);
@@ -2208,7 +2173,7 @@ static int path_batch_impl(fsdp_ctx* c, int n_frames, const double* poses, const
   launch_path_retry(c, q, q.in);
   HIP_TRY(c, hipMemsetAsync(q.d_retry, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
   c->stage_names = names + "path_retry_kernel";
-  if (int rcs = ensure_staging(c, n_frames)) return rcs;
+  HIP_TRY(c, grow_pinned(c->h_path, c->cap_path, (size_t)n_frames, hipHostMallocDefault, 64));
   HIP_TRY(c, hipMemcpyAsync(c->h_path, q.d_path, sizeof(PathOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   for (int i = 0; i < n_frames; i++) {
@@ -2253,7 +2218,7 @@ int fsdp_profile_path(fsdp_ctx* c, long long* out32_per_frame) {
   Work& q = c->slot[0];
   std::string names;
   if (c->profile_sort)
-    launch_sort(c, q, c->res);
+    launch_sort(c, q, c->res, StageIn());
   else
     launch_path(c, q, c->res, nullptr, names, frames_in_flight(c, c->res.n_frames, false));
   HIP_TRY(c, hipMemsetAsync(q.d_big, 0, sizeof(int), q.stream));
@@ -2458,9 +2423,12 @@ static int flush_skid(fsdp_ctx* c) {
       HIP_TRY(c, hipEventRecord(t.done, xs));
       continue;
     }
-    if (t.user_results || t.user_info)
-      launch_assemble(c, q, t.user_results ? n : 0, true, direct, xs, t.user_info ? q.d_skid_info : nullptr,
-                      t.user_info ? (SkidInfo*)device_view(t.h_info) : nullptr);
+    if (t.user_results || t.user_info) {
+      PassIO io;
+      io.host = direct;
+      io.info = t.user_info ? (SkidInfo*)device_view(t.h_info) : nullptr;
+      launch_assemble(c, q, t.user_results ? n : 0, io, true);
+    }
     HIP_TRY(c, hipGetLastError());
     if (t.via_stage) HIP_TRY(c, hipMemcpyAsync(t.h_stage, q.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, xs));
     HIP_TRY(c, hipEventRecord(t.done, xs));
@@ -2485,9 +2453,8 @@ static int skidpad_submit_impl(fsdp_ctx* c, int n_instances, const int32_t* off,
     return 1;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  size_t total;
-  int max_cones;
-  if (int rc = check_batch(c, n_instances, off, cones, poses, &total, &max_cones)) return rc;
+  Batch b;
+  if (int rc = check_batch(c, n_instances, off, cones, poses, nullptr, &b)) return rc;
   // one step per slot (the slots only hold the steps' buffers, every command goes to the main stream): the next free one
   int si = (int)(c->next_ticket % c->overlap);
   for (int k = 0; k < c->overlap && c->slot[si].tk[0].id >= 0; k++) si = (si + 1) % c->overlap;
@@ -2504,30 +2471,16 @@ static int skidpad_submit_impl(fsdp_ctx* c, int n_instances, const int32_t* off,
   // at once, relocalization_base_class.py:56-57; the path comes from the known map): they stay on the host, and the
   // relocalization kernel is not launched.  (Known from the planner information of a collected step.)
   const bool attempt = !c->skid_all_reloc;
-  if (!attempt) total = 0;
-  const bool in_pinned = is_pinned(off, sizeof(int32_t) * ((size_t)n_instances + 1)) && is_pinned(poses, sizeof(double) * 4 * (size_t)n_instances) &&
-                         (total == 0 || is_pinned(cones, sizeof(double) * 3 * total));
-  if (in_pinned) {
-    if (int rc = stage_inputs(c, q.in, xs, n_instances, off, cones, poses, nullptr, total, max_cones)) return rc;
-  } else if (int rc = upload_inputs(c, q.in, xs, n_instances, off, cones, poses, nullptr, total, max_cones)) {
+  if (!attempt) b.total = 0;
+  if (inputs_pinned(b)) {
+    if (int rc = stage_inputs(c, q.in, xs, b)) return rc;
+  } else if (int rc = upload_inputs(c, q.in, xs, b)) {
     return rc;
   }
   q.skid_attempted = attempt;
-  if (info && n_instances > t.cap_info) {
-    if (t.h_info) (void)hipHostFree(t.h_info);
-    t.h_info = nullptr;
-    t.cap_info = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&t.h_info, sizeof(SkidInfo) * (size_t)n_instances, hipHostMallocDefault));
-    t.cap_info = n_instances;
-  }
+  if (info) HIP_TRY(c, grow_pinned(t.h_info, t.cap_info, (size_t)n_instances, hipHostMallocDefault));
   const bool direct = results && is_pinned(results, (compact ? sizeof(PathOut) : sizeof(fsdp_frame_result)) * (size_t)n_instances);
-  if (results && !direct && n_instances > t.cap_stage) {
-    if (t.h_stage) (void)hipHostFree(t.h_stage);
-    t.h_stage = nullptr;
-    t.cap_stage = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&t.h_stage, sizeof(fsdp_frame_result) * (size_t)n_instances, hipHostMallocDefault));
-    t.cap_stage = n_instances;
-  }
+  if (results && !direct) HIP_TRY(c, grow_pinned(t.h_stage, t.cap_stage, (size_t)n_instances, hipHostMallocDefault));
   if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
   if (attempt)
     hipLaunchKernelGGL(skid_reloc_kernel, dim3((unsigned)n_instances), dim3(WAVE), 0, c->stream, n_instances, q.in.d_off, q.in.d_cones, q.in.d_poses,
@@ -2537,7 +2490,7 @@ static int skidpad_submit_impl(fsdp_ctx* c, int n_instances, const int32_t* off,
   q.pass_in = &q.in;
   q.pass_skid = true;
   q.unverified = false;
-  t.n = n_instances;
+  t.batch = b;
   t.skid = true;
   t.pending = true;
   t.user_results = results;
@@ -2545,8 +2498,7 @@ static int skidpad_submit_impl(fsdp_ctx* c, int n_instances, const int32_t* off,
   t.via_stage = results && !direct;
   t.compact = compact;
   c->skid_pending[c->n_skid_pending++] = si;
-  c->last_slot = si;
-  c->last_n = n_instances;
+  c->last = fsdp_ctx::LastPass{si, n_instances, false, true};
   t.id = c->next_ticket++;
   c->outstanding++;
   *ticket = t.id;
@@ -2615,15 +2567,14 @@ int fsdp_skidpad_time_path(fsdp_ctx* c, int iters, float* ms_total) {
   if (c->outstanding) return busy_error(c, "fsdp_skidpad_time_path");
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
-  Work& q = c->slot[c->last_slot];
-  if (!q.pass_skid || q.in.n_frames != c->n_instances) {
+  if (c->last.slot < 0 || !c->slot[c->last.slot].pass_skid || c->last.n != c->n_instances) {
     c->err = "fsdp_skidpad_time_path: run a step first";
     return 1;
   }
   size_t bytes = sizeof(SkidState) * (size_t)c->n_instances;
   HIP_TRY(c, hipMemcpyAsync(c->d_skid_backup, c->d_skid, bytes, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev[4], c->stream));
-  for (int i = 0; i < iters; i++) launch_skid_path(c, &c->last_slot, 1, c->skid_step_no);  // (a step number of its own: nothing to wait for)
+  for (int i = 0; i < iters; i++) launch_skid_path(c, &c->last.slot, 1, c->skid_step_no);  // (a step number of its own: nothing to wait for)
   HIP_TRY(c, hipEventRecord(c->ev[5], c->stream));
   HIP_TRY(c, hipEventSynchronize(c->ev[5]));
   float t = 0;
@@ -2638,13 +2589,23 @@ int fsdp_skidpad_time_path(fsdp_ctx* c, int iters, float* ms_total) {
 }
 
 // ---- per-stage intermediate of the path stage: the refit's spline ------------------------------------------------------
+// the slot of the most recent pass, when it holds that pass of a whole call (everything in flight has finished)
+static Work* debug_slot(fsdp_ctx* c, const char* who) {
+  if (c->last.slot < 0 || !c->last.whole || c->last.n <= 0) {
+    c->err = std::string(who) + ": no pass to read (none yet, a blocking call cut into chunks, or its slot released or reused since)";
+    return nullptr;
+  }
+  return &c->slot[c->last.slot];
+}
+
 extern "C" int fsdp_debug_refit(fsdp_ctx* c, int32_t* n_knots, double* knots34, double* coeffs68) {
-  if (!c || !n_knots || !knots34 || !coeffs68 || c->last_n <= 0) return 1;
+  if (!c || !n_knots || !knots34 || !coeffs68) return 1;
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = sync_all(c);
-  if (rc) return rc;
-  Work& q = c->slot[c->last_slot];
-  const int n = c->last_n;
+  if (int rc = sync_all(c)) return rc;
+  Work* qp = debug_slot(c, "fsdp_debug_refit");
+  if (!qp) return 1;
+  Work& q = *qp;
+  const int n = c->last.n;
   std::vector<FitRec> recs((size_t)n);
   std::vector<PathMid> mids((size_t)n);
   const size_t fit_off = (size_t)ARENA_FIT * sizeof(double);  // frame_arena(): A.fit
@@ -2664,11 +2625,12 @@ extern "C" int fsdp_debug_refit(fsdp_ctx* c, int32_t* n_knots, double* knots34, 
 
 // raw doubles of a frame's scratch arena of the most recent pass (tests / debug builds)
 extern "C" int fsdp_debug_arena(fsdp_ctx* c, int frame, int offset, int count, double* out) {
-  if (!c || !out || frame < 0 || frame >= c->last_n || offset < 0 || count < 0 || offset + count > ARENA_DOUBLES) return 1;
+  if (!c || !out || frame < 0 || offset < 0 || count < 0 || offset + count > ARENA_DOUBLES) return 1;
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
-  Work& q = c->slot[c->last_slot];
-  HIP_TRY(c, copy_sync(c, out, q.d_arena + (size_t)frame * ARENA_DOUBLES + offset, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
+  Work* q = debug_slot(c, "fsdp_debug_arena");
+  if (!q || frame >= c->last.n) return 1;
+  HIP_TRY(c, copy_sync(c, out, q->d_arena + (size_t)frame * ARENA_DOUBLES + offset, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
   return 0;
 }
 

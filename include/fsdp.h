@@ -279,9 +279,11 @@ int fsdp_ticket_capacity(const fsdp_ctx* ctx);         /* tickets that may be ou
 int fsdp_upload(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt, const double* poses);
 int fsdp_run(fsdp_ctx* ctx);      /* enqueue one pass over the resident batch on the next slot's stream (async) */
 int fsdp_sync(fsdp_ctx* ctx);     /* wait for all passes in flight */
-int fsdp_resident_frames(const fsdp_ctx* ctx); /* frames of the most recent pass (what fsdp_download writes) */
-int fsdp_download(fsdp_ctx* ctx, fsdp_frame_result* results); /* the results of the most recent fsdp_run pass (tickets and blocking calls
-                                                                  hand their results to the caller's buffer, not to the slot's block) */
+int fsdp_resident_frames(const fsdp_ctx* ctx); /* frames of the most recent pass of any kind (0: none; what fsdp_download writes) */
+/* The results of the most recent pass when it was an fsdp_run or fsdp_time_runs pass.  Fails (fsdp_last_error) when the most
+ * recent pass was a ticket, a blocking call or a skidpad step (they hand their results to the caller's buffer, not to the
+ * slot's block), when no pass has followed fsdp_upload, and when fsdp_set_overlap has released the pass's slot. */
+int fsdp_download(fsdp_ctx* ctx, fsdp_frame_result* results);
 
 /* Pass overlap: depth d (<= FSDP_MAX_OVERLAP) gives the context d pass slots (HIP stream + buffers each); fsdp_submit
  * tickets and consecutive fsdp_run passes rotate through them, so the next passes fill the compute units that the slowest
@@ -471,7 +473,9 @@ int fsdp_comm_destroy(fsdp_ctx* ctx);        /* also done by fsdp_destroy */
 /* Per-stage intermediate of the path stage (tests): the smoothing spline of the refit (fit #2,
  * core_calculate_path.py:239-259 -> utils/spline_fit.py:117 splprep) of every frame of the most recent pass that went
  * through the three-kernel path stage: n_knots (n_frames) (-1: the frame took another route), knots (n_frames,34),
- * coefficients (n_frames,68) = x coefficients [0,n) then y coefficients [n,2n). */
+ * coefficients (n_frames,68) = x coefficients [0,n) then y coefficients [n,2n); n_frames = fsdp_resident_frames.  This and
+ * fsdp_debug_arena read exactly the most recent pass, or fail (fsdp_last_error): after a blocking call that was cut into
+ * chunks, and once that pass's slot was released (fsdp_set_overlap) or its buffers reused (a stage-level call, a larger batch). */
 int fsdp_debug_refit(fsdp_ctx* ctx, int32_t* n_knots, double* knots34, double* coeffs68);
 
 /* Raw doubles [offset, offset + count) of frame `frame`'s scratch arena after the most recent pass (tests, debug builds). */

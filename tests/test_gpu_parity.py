@@ -922,6 +922,59 @@ def test_refit_spline_equals_oracle(pkg, ctx):
     assert checked >= 40
 
 
+def test_debug_reads_of_a_chunked_blocking_call_fail(pkg):
+    """fsdp_debug_refit / fsdp_debug_arena read exactly the most recent pass: a blocking call cut into chunks has no one pass that
+    covers the call, so they fail instead of returning the last chunk's scratch (round-6 advisor)."""
+    import ctypes
+
+    off, cones, poses = pkg.synth.make_replay_batch(2048, 64, 0.15, seed=1, color=True)
+    ctx = pkg.Context(device=0, options={"plan_chunks": 4})
+    ctx.plan_batch(off, cones, poses)
+    with pytest.raises(pkg.FsdpError, match="fsdp_debug_refit"):
+        ctx.debug_refit()
+    out = np.zeros(1)
+    assert ctx._lib.fsdp_debug_arena(ctx._h, 0, 0, 1, ctypes.c_void_p(out.ctypes.data)) != 0
+    ctx.set_option("plan_chunks", 1)
+    ctx.plan_batch(off, cones, poses)
+    nk, _, _ = ctx.debug_refit()  # one pass over the whole call: readable
+    assert len(nk) == 2048 and (nk > 0).mean() > 0.95
+    ctx.close()
+
+
+def _same_records(a, b):
+    return a.dtype == b.dtype and len(a) == len(b) and all(
+        np.ascontiguousarray(a[f]).tobytes() == np.ascontiguousarray(b[f]).tobytes() for f in a.dtype.names)
+
+
+def test_download_returns_only_the_most_recent_run(pkg):
+    """fsdp_download returns the results of the most recent fsdp_run / fsdp_time_runs pass, or fails: after a blocking call,
+    after a ticket, after an upload that no pass has followed, and after fsdp_set_overlap released the pass's slot (round-6
+    advisor: these used to return stale device memory)."""
+    off, cones, poses = pkg.synth.make_replay_batch(512, 64, 0.15, seed=21, color=True)
+    ctx = pkg.Context(device=0)
+    ref = ctx.plan_batch(off, cones, poses)
+    with pytest.raises(pkg.FsdpError, match="fsdp_download"):
+        ctx.download()  # after a blocking call
+    ctx.upload(off, cones, poses)
+    with pytest.raises(pkg.FsdpError, match="fsdp_download"):
+        ctx.download()  # no pass over the uploaded batch yet
+    ctx.run()
+    assert _same_records(ctx.download(), ref)
+    assert _same_records(ctx.collect(ctx.submit(off, cones, poses)), ref)
+    with pytest.raises(pkg.FsdpError, match="fsdp_download"):
+        ctx.download()  # after a ticket
+    ctx.set_overlap(3)
+    for _ in range(3):
+        ctx.run()  # the last one in slot 2
+    assert _same_records(ctx.download(), ref)
+    ctx.set_overlap(2)
+    with pytest.raises(pkg.FsdpError, match="fsdp_download"):
+        ctx.download()  # slot 2 was released
+    ctx.run()
+    assert _same_records(ctx.download(), ref)
+    ctx.close()
+
+
 def test_device_det3_sign_is_numpys(pkg, ctx):
     """calculate_path/path_parameterization.py:86-92: the sign of the curvature is the sign of np.linalg.det of three
     homogeneous points — zero up to rounding on a straight stretch.  The device's restatement (path_kernel.h det3_lu,

@@ -163,7 +163,7 @@ def test_page_locked_batch_is_sharded_without_a_host_copy(pkg):
         mp.close()
 
 
-def test_slices_of_a_batch_through_the_c_abi(pkg):
+def test_slices_of_a_batch_through_the_c_abi(pkg, golden_dir):
     """include/fsdp.h: cone_offsets[0] need not be 0.  Slices [lo, hi) of one batch — pageable and page-locked, default and
     UNKNOWN-filtering contexts (the three input routes: copy engine, the sorting kernel reading the host buffer, the staging
     kernel) — equal the same frames planned as a batch of their own; sorted indices stay frame-relative."""
@@ -194,6 +194,28 @@ def test_slices_of_a_batch_through_the_c_abi(pkg):
     out = np.zeros(hi - lo, dtype=capi.RESULT_DTYPE)
     rc = ctx._lib.fsdp_plan_batch(ctx._h, hi - lo, capi._ip(off[lo:]), capi._dp(cones), capi._dp(poses[lo:]), ctypes.c_void_p(out.ctypes.data))
     assert rc == 0 and _same(out, ref[lo:hi])
+    # and a skidpad step: two steps of 16 planners laid out as one page-locked batch, the second handed over as its slice
+    # (cone_offsets[0] > 0: the library's page-locked test covers the rows the staging kernel reads) == the rebased arrays
+    n = 16
+    g = sk.load_sequence(golden_dir)
+    tf = sk.perturbed_instances(g, n)
+    (o0, c0, p0), (o1, c1, p1) = sk.batch_for_step(g, 0, tf), sk.batch_for_step(g, 1, tf)
+    both = np.concatenate([o0, o1[1:] + o0[-1]]).astype(np.int32)
+    po, pc, pp = capi.pinned_copy(both, np.int32), capi.pinned_copy(np.concatenate([c0, c1])), capi.pinned_copy(np.concatenate([p0, p1]))
+    ref = pkg.SkidpadBatch(n, device=0)
+    want = [ref.step(o0, c0, p0), ref.step(o1, c1, p1)]
+    got = pkg.SkidpadBatch(n, device=0)
+    lib, h = got._ctx._lib, got._ctx._h
+    for k in range(2):
+        res = capi.pinned_empty(n, got._ctx.result_dtype)
+        info = np.zeros(n, dtype=want[k][1].dtype)
+        t = ctypes.c_longlong(-1)
+        assert lib.fsdp_skidpad_submit(h, n, po.ctypes.data + 4 * n * k, pc.ctypes.data, pp.ctypes.data + 32 * n * k, res.ctypes.data,
+                                       info.ctypes.data, ctypes.byref(t)) == 0
+        assert lib.fsdp_collect(h, t) == 0
+        assert _same(res, want[k][0]) and _same(info, want[k][1]), k
+    ref.close()
+    got.close()
 
 
 def test_sharded_skidpad_compact_results(pkg, golden_dir):

@@ -25,8 +25,8 @@ def run(name, ctx, off, cones, poses, steps):
         ctx.set_overlap(ov); ctx.time_runs(ov)
         t3, _ = ctx.time_runs(3 * ov)
         deep[ov] = round((len(off) - 1) / (t3 / (3 * ov)) * 1e3)
+    res = ctx.download()  # (before the depth shrinks: that releases the slot of the most recent pass)
     ctx.set_overlap(10)
-    res = ctx.download()
     h = hashlib.sha256()
     for k in res.dtype.names: h.update(np.ascontiguousarray(res[k]).tobytes())
     n = len(off) - 1
