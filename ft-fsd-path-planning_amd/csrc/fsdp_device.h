@@ -14,13 +14,10 @@
 
 #include <stdint.h>
 
-#ifndef FSDP_EMU
-#include <hip/hip_runtime.h>
-#endif
+#include "device_prims.h"  // the HIP runtime, WAVE, Grp<G>, and everything else the host emulator builds differently
 
 namespace fsdp {
 
-constexpr int WAVE = 64;
 constexpr int MAX_CONES = 256;   // cones per frame handled in LDS (status OVERFLOW beyond)
 // Structural capacities.  Two builds of these sources exist (include/fsdp.h): the standard shapes are the reference's
 // defaults; -DFSDP_WIDE_SHAPES compiles the wide library for contexts whose parameters exceed them.
@@ -153,17 +150,7 @@ __device__ __forceinline__ double angle_between(double ax, double ay, double bx,
 // angle_between(...) < thr and > thr for a constant threshold, from the clipped cosine c: the arc cosine is monotone, so
 // the cosine decides unless it lies within 1e-9 of cos(thr) (nine orders of magnitude above acos' rounding) — only then
 // is the arc cosine itself evaluated and compared, like the reference does.  NaN (a zero vector) compares false everywhere.
-// The slow path is a CALL (FSDP_ACOS_COLD, default on): inlined, every predicate carried its own copy of the device library's acos, and
-// the polynomial's coefficients — shared by the copies, hoisted to the top of the sorting kernel — stayed alive across the whole kernel
-// and were spilled to scratch (18 registers, re-read by eight dependent scratch loads inside every acos of the cost phase).
-#ifndef FSDP_ACOS_COLD
-#define FSDP_ACOS_COLD 1
-#endif
-#if FSDP_ACOS_COLD && !defined(FSDP_EMU)
-__device__ __attribute__((noinline)) inline double acos_cold(double c) { return acos(c); }
-#else
-__device__ __forceinline__ double acos_cold(double c) { return acos(c); }
-#endif
+// The slow path is acos_cold (device_prims.h: a call on the device).
 __device__ __forceinline__ bool acos_less(double c, double thr, double cos_thr) {
   if (c > cos_thr + 1e-9) return true;
   if (c < cos_thr - 1e-9) return false;
@@ -290,6 +277,15 @@ struct ProfScope {
     __syncthreads();                                                                                  \
     if (g_prof && (threadIdx.x & 63) < 32) g_prof[(size_t)blockIdx.x * 32 + (threadIdx.x & 63)] += prof_lds()[threadIdx.x & 63]; \
   } while (0)
+// section accounting of the sorting kernels: PROF_MARK(k) closes the running section and opens section k
+#define PROF_MARK(k)                                                                          \
+  do {                                                                                        \
+    long long now_ = clock64();                                                               \
+    if (g_prof && (threadIdx.x & 63) == 0) prof_lds()[prof_cur_] += now_ - prof_t_;            \
+    prof_cur_ = (k);                                                                          \
+    prof_t_ = now_;                                                                           \
+  } while (0)
+#define PROF_MARK_DECL(k) long long prof_t_ = clock64(); int prof_cur_ = (k)
 #else
 #define PROF(slot)
 #define PROF_T0(slot)
@@ -297,6 +293,8 @@ struct ProfScope {
 #define PROF_COUNT(slot, G, value)
 #define PROF_INIT()
 #define PROF_FLUSH()
+#define PROF_MARK(k)
+#define PROF_MARK_DECL(k)
 #endif
 // finer sections of the fit itself (profiling builds of the fit kernel with -DFSDP_PROFILE_FIT_DETAIL: slots 1-6, which
 // belong to the path stage in the prep / finish profiles)
@@ -369,97 +367,5 @@ __device__ __forceinline__ int wave_min_int(int v) {
   }
   return v;
 }
-
-// ------------------------------------------------------------------------------------------
-// lane groups: G lanes per frame, WAVE / G frames per wavefront
-// ------------------------------------------------------------------------------------------
-// The sorting / matching kernels give a frame the whole wavefront (G = 64).  The path stage is dominated by
-// serial FP64 chains (spline QR) that keep 1-4 lanes busy, so it packs WAVE / G frames into one wavefront
-// (G = 16: four frames, one per DPP row): a serial instruction then advances four frames at once.  Groups are
-// aligned; control flow is uniform WITHIN a group and may diverge BETWEEN groups (the hardware runs the union of
-// the paths, masked).  Cross-lane traffic never leaves a group.  sync() orders LDS / scratch hand-offs between the
-// lanes of a group: with one wavefront per workgroup the lanes run in lock-step, so only the compiler and the memory
-// counters need a fence (no s_barrier, which must not sit in divergent code).
-template <int G>
-struct Grp {
-  static_assert(G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "group size");
-  static constexpr int SIZE = G;
-  static constexpr int PER_WAVE = WAVE / G;
-  static __device__ __forceinline__ int lane() { return (int)(threadIdx.x & (G - 1)); }
-  static __device__ __forceinline__ int index() { return (int)((threadIdx.x & 63) / G); }
-  static __device__ __forceinline__ void sync() {
-#ifdef FSDP_EMU
-    emu::gbarrier(G);
-#else
-    if constexpr (G == WAVE) {
-      __syncthreads();
-    } else {
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-    }
-#endif
-  }
-  // bit i = lane i of this group
-  static __device__ __forceinline__ unsigned long long ballot(bool p) {
-#ifdef FSDP_EMU
-    return emu::gballot(p, G);
-#else
-    unsigned long long m = __ballot(p);
-    if constexpr (G == WAVE)
-      return m;
-    else
-      return (m >> (index() * G)) & ((1ull << G) - 1ull);
-#endif
-  }
-  // value of group lane `src` (group-uniform src)
-  template <class T>
-  static __device__ __forceinline__ T bcast(T v, int src) {
-#ifdef FSDP_EMU
-    return emu::gexchange(v, (emu::B->cur & ~(G - 1)) | src, G);
-#else
-    return __shfl(v, (int)((threadIdx.x & 63) & ~(G - 1)) | src, WAVE);
-#endif
-  }
-  template <class T>
-  static __device__ __forceinline__ T shfl_xor(T v, int mask) {
-#ifdef FSDP_EMU
-    return emu::gexchange(v, emu::B->cur ^ mask, G);
-#else
-    return __shfl_xor(v, mask, WAVE);
-#endif
-  }
-  // value of the previous lane of the group (lane 0 keeps its own)
-  template <class T>
-  static __device__ __forceinline__ T shfl_up1(T v) {
-#ifdef FSDP_EMU
-    return emu::gexchange(v, lane() > 0 ? emu::B->cur - 1 : emu::B->cur, G);
-#else
-    int me = (int)(threadIdx.x & 63);
-    return __shfl(v, lane() > 0 ? me - 1 : me, WAVE);
-#endif
-  }
-  // value of the next lane of the group (the last lane keeps its own)
-  template <class T>
-  static __device__ __forceinline__ T shfl_down1(T v) {
-#ifdef FSDP_EMU
-    return emu::gexchange(v, lane() < G - 1 ? emu::B->cur + 1 : emu::B->cur, G);
-#else
-    int me = (int)(threadIdx.x & 63);
-    return __shfl(v, lane() < G - 1 ? me + 1 : me, WAVE);
-#endif
-  }
-  // argmin over (value, index) pairs with "first smallest" semantics; lanes holding no candidate pass idx = -1
-  static __device__ __forceinline__ void argmin(double& v, int& idx) {
-    for (int off = G / 2; off >= 1; off >>= 1) {
-      double ov = shfl_xor(v, off);
-      int oi = shfl_xor(idx, off);
-      bool take = (oi >= 0) && (idx < 0 || ov < v || (ov == v && oi < idx));
-      if (take) {
-        v = ov;
-        idx = oi;
-      }
-    }
-  }
-};
 
 }  // namespace fsdp

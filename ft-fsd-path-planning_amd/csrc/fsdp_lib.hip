@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -2635,6 +2636,37 @@ extern "C" int fsdp_debug_arena(fsdp_ctx* c, int frame, int offset, int count, d
 }
 
 // ---- device arithmetic self-test ------------------------------------------------------------------------------------------
+// One routine behind the five entry points: n elements, inputs of `per` doubles per element each, an output of out_per doubles
+// per element.  Device blocks for all of them, inputs in, launch(device inputs, device output) on the context's stream, output
+// back, wait — and every block freed again on every way out.
+struct SelftestIn {
+  const double* host;
+  int per;
+};
+static int run_selftest(fsdp_ctx* c, int n, std::initializer_list<SelftestIn> ins, int out_per, double* out,
+                        const std::function<void(double* const*, double*)>& launch) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = sizeof(double) * (size_t)n;
+  std::vector<double*> d(ins.size() + 1, nullptr);  // the inputs in order, then the output
+  hipError_t e = hipSuccess;
+  size_t k = 0;
+  for (const SelftestIn& in : ins)
+    if (e == hipSuccess) e = hipMalloc(&d[k++], in.per * bytes);
+  if (e == hipSuccess) e = hipMalloc(&d.back(), out_per * bytes);
+  k = 0;
+  for (const SelftestIn& in : ins) {
+    if (e == hipSuccess) e = hipMemcpyAsync(d[k], in.host, in.per * bytes, hipMemcpyHostToDevice, c->stream);
+    k++;
+  }
+  if (e == hipSuccess) {
+    launch(d.data(), d.back());
+    e = hipMemcpyAsync(out, d.back(), out_per * bytes, hipMemcpyDeviceToHost, c->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  for (double* p : d) (void)hipFree(p);
+  HIP_TRY(c, e);
+  return 0;
+}
 // The hand-rolled sequences of spline_device.h against the compiler's IEEE operations, element-wise on the device:
 // out[0][i] = sqrt_1_2(x[i]), out[1][i] = sqrt(x[i]) (x in [1, 2]); out[2][i] = div_rcp(a[i], b[i], rcp_refined(b[i])),
 // out[3][i] = a[i] / b[i]; out[4][i] = in_div_band(a[i]) && in_div_band(b[i]).
@@ -2657,49 +2689,16 @@ __global__ void absminmax_selftest_kernel(int n, const double* __restrict__ a, c
 }
 extern "C" int fsdp_selftest_absminmax(fsdp_ctx* c, int n, const double* a, const double* b, double* out2n) {
   if (!c || n <= 0 || !a || !b || !out2n) return 1;
-  HIP_TRY(c, hipSetDevice(c->device));
-  double *da = nullptr, *db = nullptr, *dout = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  HIP_TRY(c, hipMalloc(&da, bytes));
-  HIP_TRY(c, hipMalloc(&db, bytes));
-  HIP_TRY(c, hipMalloc(&dout, 2 * bytes));
-  hipError_t e = hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(absminmax_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, da, db, dout);
-    e = hipMemcpyAsync(out2n, dout, 2 * bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dout);
-  HIP_TRY(c, e);
-  return 0;
+  return run_selftest(c, n, {{a, 1}, {b, 1}}, 2, out2n, [&](double* const* in, double* dout) {
+    hipLaunchKernelGGL(absminmax_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, in[0], in[1], dout);
+  });
 }
 
 extern "C" int fsdp_selftest_math(fsdp_ctx* c, int n, const double* x, const double* a, const double* b, double* out5n) {
   if (!c || n <= 0 || !x || !a || !b || !out5n) return 1;
-  HIP_TRY(c, hipSetDevice(c->device));
-  double *dx = nullptr, *da = nullptr, *db = nullptr, *dout = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  HIP_TRY(c, hipMalloc(&dx, bytes));
-  HIP_TRY(c, hipMalloc(&da, bytes));
-  HIP_TRY(c, hipMalloc(&db, bytes));
-  HIP_TRY(c, hipMalloc(&dout, 5 * bytes));
-  hipError_t e = hipMemcpyAsync(dx, x, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(math_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dx, da, db, dout);
-    e = hipMemcpyAsync(out5n, dout, 5 * bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(dx);
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dout);
-  HIP_TRY(c, e);
-  return 0;
+  return run_selftest(c, n, {{x, 1}, {a, 1}, {b, 1}}, 5, out5n, [&](double* const* in, double* dout) {
+    hipLaunchKernelGGL(math_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, in[0], in[1], in[2], dout);
+  });
 }
 
 // The Givens step's arithmetic (spline_device.h fpgivs_guarded<true>: max / min, the first quotient, sqrt on [1, 2], the reciprocal of dd
@@ -2723,24 +2722,9 @@ __global__ void givens_selftest_kernel(int n, const double* __restrict__ piv, co
 }
 extern "C" int fsdp_selftest_givens(fsdp_ctx* c, int n, const double* piv, const double* ww, double* out7n) {
   if (!c || n <= 0 || !piv || !ww || !out7n) return 1;
-  HIP_TRY(c, hipSetDevice(c->device));
-  double *da = nullptr, *db = nullptr, *dout = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  HIP_TRY(c, hipMalloc(&da, bytes));
-  HIP_TRY(c, hipMalloc(&db, bytes));
-  HIP_TRY(c, hipMalloc(&dout, 7 * bytes));
-  hipError_t e = hipMemcpyAsync(da, piv, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(db, ww, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(givens_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, da, db, dout);
-    e = hipMemcpyAsync(out7n, dout, 7 * bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dout);
-  HIP_TRY(c, e);
-  return 0;
+  return run_selftest(c, n, {{piv, 1}, {ww, 1}}, 7, out7n, [&](double* const* in, double* dout) {
+    hipLaunchKernelGGL(givens_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, in[0], in[1], dout);
+  });
 }
 
 // det3_lu (path_kernel.h: the sign of numpy.linalg.det of three homogeneous points) element-wise on the device
@@ -2752,20 +2736,9 @@ __global__ void det3_selftest_kernel(int n, const double* __restrict__ xy6, doub
 }
 extern "C" int fsdp_selftest_det3(fsdp_ctx* c, int n, const double* xy6, double* out) {
   if (!c || n <= 0 || !xy6 || !out) return 1;
-  HIP_TRY(c, hipSetDevice(c->device));
-  double *dx = nullptr, *dout = nullptr;
-  HIP_TRY(c, hipMalloc(&dx, sizeof(double) * 6 * (size_t)n));
-  HIP_TRY(c, hipMalloc(&dout, sizeof(double) * (size_t)n));
-  hipError_t e = hipMemcpyAsync(dx, xy6, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(det3_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dx, dout);
-    e = hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(dx);
-  (void)hipFree(dout);
-  HIP_TRY(c, e);
-  return 0;
+  return run_selftest(c, n, {{xy6, 6}}, 1, out, [&](double* const* in, double* dout) {
+    hipLaunchKernelGGL(det3_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, in[0], dout);
+  });
 }
 
 // The device libm values the sorting stage's discrete decisions hang on (atan2 of the search predicates, start-cone bearings and
@@ -2780,23 +2753,9 @@ __global__ void libm_selftest_kernel(int n, const double* __restrict__ y, const 
 }
 extern "C" int fsdp_selftest_libm(fsdp_ctx* c, int n, const double* y, const double* x, const double* cs, double* out3n) {
   if (!c || n <= 0 || !y || !x || !cs || !out3n) return 1;
-  HIP_TRY(c, hipSetDevice(c->device));
-  double *din = nullptr, *dout = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  HIP_TRY(c, hipMalloc(&din, 3 * bytes));
-  HIP_TRY(c, hipMalloc(&dout, 3 * bytes));
-  hipError_t e = hipMemcpyAsync(din, y, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(din + n, x, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(din + 2 * (size_t)n, cs, bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(libm_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, din, din + n, din + 2 * (size_t)n, dout);
-    e = hipMemcpyAsync(out3n, dout, 3 * bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(din);
-  (void)hipFree(dout);
-  HIP_TRY(c, e);
-  return 0;
+  return run_selftest(c, n, {{y, 1}, {x, 1}, {cs, 1}}, 3, out3n, [&](double* const* in, double* dout) {
+    hipLaunchKernelGGL(libm_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, in[0], in[1], in[2], dout);
+  });
 }
 
 // ---- multi-GPU: RCCL over xGMI (see fsdp_comm.h) ----------------------------------------------------------------------

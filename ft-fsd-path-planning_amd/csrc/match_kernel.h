@@ -14,9 +14,6 @@
 #pragma once
 #include "fsdp_device.h"
 
-#ifndef FSDP_MATCH_WAVES
-#define FSDP_MATCH_WAVES 4
-#endif
 namespace fsdp {
 
 struct MatchShared {
@@ -313,8 +310,9 @@ __device__ __forceinline__ int cones_for_other_side(MatchShared& S, const Params
 constexpr int MATCH_G = (MAX_MATCH <= 32) ? 32 : 64;  // lanes per frame: the lists (<= MAX_MATCH cones incl. the virtual ones) are walked one cone per lane
 static_assert(MATCH_G >= MAX_MATCH, "matching walks its lists one cone per lane");
 // (four wavefronts per SIMD, 126 registers: measured +2 % frames/s over the two the allocator takes unasked)
+constexpr int MATCH_WAVES = 4;
 template <int G>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FSDP_MATCH_WAVES))) match_kernel(int n_frames, const int32_t* __restrict__ cone_offsets,
+__global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(MATCH_WAVES) match_kernel(int n_frames, const int32_t* __restrict__ cone_offsets,
                                                    const double* __restrict__ cones_xyt, const double* __restrict__ poses,
                                                    const SortOut* __restrict__ sorted, MatchOut* __restrict__ out,
                                                    const Params* __restrict__ prm) {

@@ -11,7 +11,7 @@
 // Every float that feeds the sample-count decision ceil(max_u / predict_every) is produced in the
 // reference's rounding order (see DESIGN.md "arithmetic contract").
 //
-// Lanes: the stage is templated on the group size G (lanes per frame, fsdp_device.h Grp<G>) and instantiated for
+// Lanes: the stage is templated on the group size G (lanes per frame, device_prims.h Grp<G>) and instantiated for
 // G = 8, 16 and 64 (eight, four, one frame per wavefront; the host picks per launch, see the end of this file): the
 // stage is dominated by serial FP64 chains, and a serial instruction then advances all frames of the wavefront.
 // Results do not depend on G (sums keep the reference's order).
@@ -582,15 +582,6 @@ __device__ __forceinline__ int parameterize_path(PS& S, const Arena& A, int off,
   }
   *n_dense = L;
   GR::sync();
-#ifdef FSDP_DEBUG_DENSE
-  // debug builds: the dense samples and the raw curvature where fsdp_debug_arena can read them (the polyline is dead here)
-  for (int i = lane; i < L; i += G) {
-    A.x[i] = DX[i];
-    A.y[i] = DY[i];
-    A.u[i] = curv[i];
-  }
-  GR::sync();
-#endif
   return 0;
 }
 
@@ -874,14 +865,9 @@ inline void default_chord_points(double (*chord)[2]) {
 }
 
 __device__ __forceinline__ Arena frame_arena(double* arena, int frame, const Params* prm) {
-#ifdef FSDP_ARENA_ALIAS
-  // experiment builds only (tools/build_variant.sh -DFSDP_ARENA_ALIAS=64 with a batch whose frames repeat with that
-  // period): frames share scratch arenas, so the path stage's scratch stream stays in the L2 — what the kernels would
-  // take if that stream cost nothing (profiles/r04_fit_memory_bound.txt)
-  double* b = arena + (size_t)(frame % FSDP_ARENA_ALIAS) * ARENA_DOUBLES;
-#else
+  // (an experiment build once let frames that repeat with period 64 share arenas, so that the path stage's scratch stream
+  // stayed in the L2 — what the kernels would take if that stream cost nothing: profiles/r04_fit_memory_bound.txt)
   double* b = arena + (size_t)frame * ARENA_DOUBLES;
-#endif
   Arena A;
   A.x = b;
   A.y = b + PATH_CAP;
@@ -1203,32 +1189,18 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) pa
   PROF_FLUSH_K(2);
 }
 
-#ifndef FSDP_FIT_WAVES
-#define FSDP_FIT_WAVES 3
-#endif
-#ifndef FSDP_FIT4_WAVES
-#define FSDP_FIT4_WAVES 2
-#endif
-#ifdef FSDP_EMU
-#define FSDP_WAVES_PER_EU(n)  // (the host emulator's compiler does not parse an expression in an attribute it does not know)
-#else
-#define FSDP_WAVES_PER_EU(n) __attribute__((amdgpu_waves_per_eu(n)))
-#endif
+constexpr int FIT_WAVES = 3, FIT4_WAVES = 2;  // wavefronts per SIMD of fit_kernel: 8 / 16 lanes per frame, 4 lanes per frame
 // the refit: utils/spline_fit.py:95-128 (splprep, k = 3, s = 0.2) of the arena polyline [off, off + n), G lanes per frame
 template <int G, int NKC>
 // (8 / 16 lanes per frame: three wavefronts per SIMD at 168 registers, measured +2 % frames/s over two; 4 lanes per frame:
 // sixteen frames' workspaces are 19.2 KB, i.e. two wavefronts per SIMD — a third one at 14.2 KB / 168 registers was measured
 // to change nothing, profiles/r04_ab_variants.txt 1)
-__global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(G == 4 ? FSDP_FIT4_WAVES : FSDP_FIT_WAVES) fit_kernel(int n_frames, double* __restrict__ arena, PathMid* __restrict__ mid,
+__global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(G == 4 ? FIT4_WAVES : FIT_WAVES) fit_kernel(int n_frames, double* __restrict__ arena, PathMid* __restrict__ mid,
                                                  int* __restrict__ retry, const Params* __restrict__ prm,
                                                  unsigned long long* __restrict__ clock_first, unsigned long long* __restrict__ clock_last) {
   using GR = Grp<G>;
   using WS = FitWS<G, NKC>;
-#ifndef FSDP_EMU
-  // optional (fsdp_time_runs): when did the launch's first wavefront start and its last one end, on the device's constant-rate
-  // clock — the kernel's duration as a kernel trace reports it, without the wait of its queue that an event bracket includes
-  if (clock_first && threadIdx.x == 0) atomicMin(clock_first, (unsigned long long)wall_clock64());
-#endif
+  note_clock_first(clock_first);  // (optional, fsdp_time_runs: device_prims.h)
   static_assert(7 * (NKC + 2) <= BAND_DOUBLES, "band region of the arena");
   __shared__ WS ws_all[WAVE / G];
   const int frame = blockIdx.x * (WAVE / G) + GR::index();
@@ -1263,9 +1235,7 @@ __global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(G == 4 ? FSDP_FIT4_WAVES
     }
   }
   PROF_FLUSH_K(1);
-#ifndef FSDP_EMU
-  if (clock_last && threadIdx.x == 0) atomicMax(clock_last, (unsigned long long)wall_clock64());
-#endif
+  note_clock_last(clock_last);
 }
 
 template <int G, int NKC = FIT_KNOTS>
@@ -1309,11 +1279,9 @@ __global__ void __launch_bounds__(64) path_finish_kernel(int n_frames, double* _
 // grid = ceil(n_frames / (64 / G)) workgroups of one wavefront; group g of block b plans frame b * (64 / G) + g.
 // retry (optional): [0] = counter, [1..] = frames that ended with ST_OVERFLOW_KNOTS (the packed kernels keep 32 knots per
 // fit); path_retry_kernel plans those again with the one-frame-per-wavefront instantiation (256 knots).
-#ifndef FSDP_PATH_WAVES
-#define FSDP_PATH_WAVES 1
-#endif
+constexpr int PATH_WAVES = 1;
 template <int G, bool FAST = true>
-__global__ void __launch_bounds__(64, FSDP_PATH_WAVES) path_kernel(int n_frames, const double* __restrict__ poses,
+__global__ void __launch_bounds__(64, PATH_WAVES) path_kernel(int n_frames, const double* __restrict__ poses,
                                                      const MatchOut* __restrict__ matched,
                                                      const double* __restrict__ default_path,
                                                      const double* __restrict__ prev_paths,
@@ -1338,10 +1306,8 @@ __global__ void __launch_bounds__(64, FSDP_PATH_WAVES) path_kernel(int n_frames,
 // wavefront at one wavefront per SIMD: 3 % of the frames of a noisy batch took 60 % of the chip's time); what that form
 // cannot finish (an exponent outside the fast division's band) is planned once more by the whole wavefront with plain IEEE
 // divisions.  The route never changes a result (tests: test_every_path_kernel_instantiation_equals_oracle).
-#ifndef FSDP_RETRY_WAVES
-#define FSDP_RETRY_WAVES 1  // (two per SIMD: 107 registers spilled to scratch, slower: profiles/r04_ab_variants.txt 4)
-#endif
-__global__ void __launch_bounds__(64, FSDP_RETRY_WAVES) path_retry_kernel(const double* __restrict__ poses, const MatchOut* __restrict__ matched,
+constexpr int RETRY_WAVES = 1;  // (two per SIMD: 107 registers spilled to scratch, slower: profiles/r04_ab_variants.txt 4)
+__global__ void __launch_bounds__(64, RETRY_WAVES) path_retry_kernel(const double* __restrict__ poses, const MatchOut* __restrict__ matched,
                                                            const double* __restrict__ default_path,
                                                            const double* __restrict__ prev_paths,
                                                            const double* __restrict__ gpath, int n_gpath,

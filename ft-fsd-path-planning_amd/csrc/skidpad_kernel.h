@@ -645,10 +645,8 @@ __device__ __forceinline__ void skid_finish_step(SkidState* st, const SkidTables
 // no wait can be for work that is not resident or finished.  With 1024 instances three steps put three wavefronts on every
 // SIMD, where one alone issues an FP64 instruction every 8.7 cycles and four together one every 4.6; the
 // kernel is held to 168 registers for that (144 spilled: 1 % slower alone, 8 % faster three to a SIMD than two at 256).
-#ifndef FSDP_SKID_PATH_WAVES
-#define FSDP_SKID_PATH_WAVES 2  // (3: 168 registers, 214 of them spilled, 384 B of scratch per lane; 2: 256 registers, 36 spilled, 112 B — same frames/s, profiles/r06_kernel_resources.txt)
-#endif
-__global__ void __launch_bounds__(64, FSDP_SKID_PATH_WAVES) skid_path_kernel(int n_inst, SkidGroup G, SkidState* states, SkidTables T,
+constexpr int SKID_PATH_WAVES = 2;  // (3: 168 registers, 214 of them spilled, 384 B of scratch per lane; 2: 256 registers, 36 spilled, 112 B — same frames/s, profiles/r06_kernel_resources.txt)
+__global__ void __launch_bounds__(64, SKID_PATH_WAVES) skid_path_kernel(int n_inst, SkidGroup G, SkidState* states, SkidTables T,
                                                           const double* __restrict__ chord, uint32_t* sync) {
   __shared__ PathShared<WAVE> S;
   __shared__ uint32_t s_ticket, s_spins;
@@ -697,7 +695,7 @@ __global__ void __launch_bounds__(64, FSDP_SKID_PATH_WAVES) skid_path_kernel(int
     if (lane == 0) {
       uint32_t spins = 0;
       while (__hip_atomic_load(&sync[1 + inst], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (uint32_t)g && ++spins < (1u << 24))
-        __builtin_amdgcn_s_sleep(8);
+        poll_pause();
       s_spins = spins;
     }
     __syncthreads();
@@ -731,8 +729,7 @@ __global__ void __launch_bounds__(64, FSDP_SKID_PATH_WAVES) skid_path_kernel(int
   __syncthreads();
   // the state above has left the wavefront (its stores are acknowledged) before the flag goes out; no cache write-back:
   // nothing else this wavefront wrote is anybody's before the launch ends
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
+  stores_acknowledged();
   if (lane == 0) __hip_atomic_store(&sync[1 + inst], (uint32_t)(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

@@ -22,21 +22,6 @@
 
 namespace fsdp {
 
-// section accounting of the profiling build: PROF_MARK(k) closes the running section and opens section k
-#if defined(FSDP_PROFILE) && !defined(FSDP_EMU)
-#define PROF_MARK(k)                                                                          \
-  do {                                                                                        \
-    long long now_ = clock64();                                                               \
-    if (g_prof && (threadIdx.x & 63) == 0) prof_lds()[prof_cur_] += now_ - prof_t_;            \
-    prof_cur_ = (k);                                                                          \
-    prof_t_ = now_;                                                                           \
-  } while (0)
-#define PROF_MARK_DECL(k) long long prof_t_ = clock64(); int prof_cur_ = (k)
-#else
-#define PROF_MARK(k)
-#define PROF_MARK_DECL(k)
-#endif
-
 // The frame state of the sorting stage.  Two instantiations: the product kernel keeps it in LDS (up to 255 cones with
 // one-byte indices, 64 raw end configurations per side); frames beyond either capacity are planned again by
 // sort_big_kernel with the same code over a state in global memory (8192 cones, 4096 raw end configurations) — the
@@ -161,24 +146,17 @@ __device__ inline bool inside_ellipse_at(double px, double py, double cx, double
 // are ex / |e| and ey / |e| up to a few ulp, and the criterion is compared with 1: it is formed from the normalised edge
 // (reciprocal square root with one Newton step, no libm call), which decides unless it lies within 1e-6 of the boundary —
 // ten orders of magnitude above the difference between the two formulations; only then the reference's own arithmetic
-// (cos / sin of the stored angle) is evaluated.  FSDP_EXACT_ELLIPSE: always the latter (A/B builds).
+// (cos / sin of the stored angle) is evaluated.
 __device__ inline bool inside_ellipse_of_edge(double px, double py, double cx, double cy, double ex, double ey, double ang, double major,
                                               double minor) {
-#ifndef FSDP_EXACT_ELLIPSE
   const double n2 = ex * ex + ey * ey;
-#ifdef FSDP_EMU
-  const double rn = 1.0 / sqrt(n2);
-#else
-  double rn = __builtin_amdgcn_rsq(n2);  // (n2 = 0: inf / NaN below -> the exact path)
-  rn = rn * (1.5 - 0.5 * n2 * rn * rn);
-#endif
+  const double rn = rsq_newton(n2);  // (n2 = 0: inf / NaN below -> the exact path)
   const double c = ex * rn, s = ey * rn;
   const double x = px - cx, y = py - cy;
   const double qx = x * c + y * s, qy = y * c - x * s;
   const double crit = (qx * qx) / (major * major) + (qy * qy) / (minor * minor);
   if (crit < 1.0 - 1e-6) return true;
   if (crit > 1.0 + 1e-6) return false;
-#endif
   return inside_ellipse_at(px, py, cx, cy, ang, major, minor);
 }
 
@@ -1512,15 +1490,13 @@ sort_kernel(int n_frames, const int32_t* __restrict__ cone_offsets, const double
 }
 // The same code over a state for up to 128 cones (the host launches it when no frame of the batch holds more): the cone
 // arrays, neighbour lists and bit masks are half as long, which makes a frame SORT128_LDS and lets a SIMD hold
-// SORT128_WAVES wavefronts.
-#ifndef SORT128_WAVES
+// SORT_WAVES_128 wavefronts.
 #ifdef FSDP_WIDE_SHAPES
-#define SORT128_WAVES 3  // (the wide shapes' frame state is 12.4 KB: three wavefronts per SIMD by LDS anyway — at four by registers it spilled 48 of them)
+constexpr int SORT_WAVES_128 = 3;  // (the wide shapes' frame state is 12.4 KB: three wavefronts per SIMD by LDS anyway — at four by registers it spilled 48 of them)
 #else
-#define SORT128_WAVES 4
+constexpr int SORT_WAVES_128 = 4;
 #endif
-#endif
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SORT128_WAVES)))
+__global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(SORT_WAVES_128)
 sort_kernel_128(int n_frames, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
                 const double* __restrict__ poses, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
                 StageIn stage = StageIn()) {
@@ -1550,7 +1526,7 @@ sort_kernel_cached(int n_frames, const int32_t* __restrict__ cone_offsets, const
   __shared__ SortShared S;
   sort_kernel_body<SortShared, true>(S, n_frames, cone_offsets, cones_xyt, poses, out, big, prm, stage, &cache);
 }
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SORT128_WAVES)))
+__global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(SORT_WAVES_128)
 sort_kernel_128_cached(int n_frames, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
                        const double* __restrict__ poses, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
                        StageIn stage, SortCacheView cache) {

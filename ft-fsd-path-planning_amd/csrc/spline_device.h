@@ -10,7 +10,7 @@
 //     evaluation) runs one point per lane, staged through LDS in chunks of CH rows;
 //   * the row-by-row Givens rotations, back-substitution, knot bookkeeping and all running sums
 //     are group-uniform (every lane carries the same scalars; LDS reads broadcast).
-// Everything is templated on the group size G (fsdp_device.h Grp<G>): G = 64 is one frame per wavefront,
+// Everything is templated on the group size G (device_prims.h Grp<G>): G = 64 is one frame per wavefront,
 // G = 16 packs four frames into a wavefront so that the serial sections advance four fits per instruction.
 // Arrays are 1-based like the published algorithm.  idim = 2, unit weights, iopt = 0.
 #pragma once
@@ -95,17 +95,12 @@ struct SplineWS {
 // wavefronts fit a SIMD's share of the LDS.  The band triangle and its right-hand sides are not here: during an
 // observation pass they live in the registers of the Givens quad, between passes in the frame's scratch (`band`:
 // (NK + 2) x 4 rows, then 2 (NK + 2) right-hand sides), where back-substitution and the smoothing iteration fetch them.
-#ifndef FSDP_FIT_CH8
-#define FSDP_FIT_CH8 16
-#endif
+constexpr int FIT_CH8 = 16, FIT_CH4 = 4;  // data rows per chunk at 8 / 4 lanes per frame
 template <int G, int NKC>
 struct FitWS {
   static constexpr int GRP = G;
   static constexpr int NK = NKC;
-#ifndef FSDP_FIT_CH4
-#define FSDP_FIT_CH4 4
-#endif
-  static constexpr int CH = (G >= 32) ? G : (G >= 16 ? 32 : (G >= 8 ? FSDP_FIT_CH8 : FSDP_FIT_CH4));
+  static constexpr int CH = (G >= 32) ? G : (G >= 16 ? 32 : (G >= 8 ? FIT_CH8 : FIT_CH4));
   static constexpr bool BAND_GLOBAL = true;
   // 1-based arrays sized for what a fit of NK knots touches: t(1..n), c(1..2n), nrdata(1..n), and the rows 1..n-4 of the
   // extended triangle.  At four lanes per frame (CH = 4) a frame is 928 bytes: sixteen of them are 14 848 bytes, eleven
@@ -295,125 +290,10 @@ __device__ __forceinline__ void fpback(EL el, const double* z, int n, int k, dou
 }
 
 // ---- exact division without the range scaling ---------------------------------------------------------
-// An IEEE double division on gfx950 is a software sequence: v_div_scale (x2), v_rcp_f64, two Newton steps, a quotient
-// with one correction (v_div_fmas) and v_div_fixup.  The scaling and the fix-up only act when an exponent sits near the
-// limits of the format; for operands in a safe band the sequence below is the same arithmetic on the same operands and
-// returns the same (correctly rounded) bits with 8 instead of 11 instructions — and two quotients over one denominator
-// share the refined reciprocal (11 instead of 22).  The guard: callers flag operands outside [2^-255, 2^255]
-// (float compares on the operands; the knot differences once per knot set) and such a frame is re-planned with plain
-// divisions (ST_RETRY, path_kernel.h).
+// max_abs_nn / min_abs_nn, rcp_refined / div_rcp, sqrt_1_2 and givens_dd_rd (the shortened FP64 sequences and what guards them)
+// are in device_prims.h.
 // the exponent band the guards of the scaling-free division accept (what fsdp_selftest_math checks the sequence on)
 __device__ __forceinline__ bool in_div_band(double v) { return fabs(v) >= 0x1p-255 && fabs(v) <= 0x1p255; }
-// max(|a|, b) / min(|a|, b) of numbers that are never NaN: one v_max_f64 / v_min_f64 each (the absolute value is a source
-// modifier; fmax() would first quiet both operands)
-__device__ __forceinline__ double max_abs_nn(double a, double b) {
-#ifdef FSDP_EMU
-  return fabs(a) >= b ? fabs(a) : b;
-#else
-  double r;
-  asm("v_max_f64 %0, |%1|, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-#endif
-}
-__device__ __forceinline__ double min_abs_nn(double a, double b) {
-#ifdef FSDP_EMU
-  return fabs(a) >= b ? b : fabs(a);
-#else
-  double r;
-  asm("v_min_f64 %0, |%1|, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-#endif
-}
-__device__ __forceinline__ double rcp_refined(double d) {
-#ifdef FSDP_EMU
-  return d;  // (the emulator divides directly, see div_rcp)
-#else
-  double r = __builtin_amdgcn_rcp(d);
-  double e = fma(-d, r, 1.0);
-  r = fma(r, e, r);
-  e = fma(-d, r, 1.0);
-  r = fma(r, e, r);
-  return r;
-#endif
-}
-// n / d given r = rcp_refined(d)
-__device__ __forceinline__ double div_rcp(double n, double d, double r) {
-#ifdef FSDP_EMU
-  (void)r;
-  return n / d;
-#else
-  const double q = n * r;
-  const double rem = fma(-d, q, n);
-  return fma(rem, r, q);
-#endif
-}
-
-// sqrt for arguments in [1, 2] (1 + r^2 with |r| <= 1): the correctly rounded result, i.e. what sqrt() returns; on the
-// device this is the compiler's own v_rsq_f64 + Goldschmidt sequence without the range scaling that [1, 2] never needs
-// (checked against sqrt() on the GPU: tests/test_gpu_parity.py::test_device_math_helpers)
-__device__ __forceinline__ double sqrt_1_2(double x) {
-#ifdef FSDP_EMU
-  return sqrt(x);
-#else
-  double y = __builtin_amdgcn_rsq(x);
-  double g = x * y;
-  double h = y * 0.5;
-  double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  g = fma(d, h, g);
-  return g;
-#endif
-}
-
-// The middle of fpgivs for operands in the divisions' safe band: den = max(|piv|, ww), num = min(|piv|, ww) ->
-//   dd = den * sqrt(1 + (num / den)^2)   and   rd = a refined reciprocal of dd for the two quotients cs = ww / dd, sn = piv / dd.
-// The reciprocal is the head of the second half of the step's dependent chain (rcp_refined(dd): v_rcp_f64 and two Newton steps, five
-// links after dd is known).  Its seed need not wait for dd: 1 / dd = (1 / den) * (1 / sqrt(x)), and both factors exist while the square
-// root is still being corrected — rq = rcp_refined(den) from the first quotient, and h, the half reciprocal square root the
-// Goldschmidt iteration refines next to g (relative error ~2^-45 after its coupled step, what v_rcp_f64 + ONE Newton step gives).
-// r0 = (2 rq) h is formed in the shadow of sqrt's last two corrections, and ONE Newton step against dd itself (error^2 ~ 2^-90, then
-// the rounding of the fma) makes it the reciprocal rcp_refined returns for all the quotients care: two links after dd instead of
-// five, three instructions less per step.  The quotients are div_rcp's (product, exact remainder, correction): correctly rounded
-// with either reciprocal (fsdp_selftest_givens holds cs / sn / dd against the IEEE operations on the device: tests/test_gpu_parity.py).
-// FSDP_GIVENS_RSQ_SEED=0 (A/B builds): the reciprocal from v_rcp_f64 again.
-#ifndef FSDP_GIVENS_RSQ_SEED
-#define FSDP_GIVENS_RSQ_SEED 1
-#endif
-__device__ __forceinline__ void givens_dd_rd(double den, double num, double& dd, double& rd) {
-#ifdef FSDP_EMU
-  const double q = num / den;
-  dd = den * sqrt(1.0 + q * q);
-  rd = dd;  // (the emulator's div_rcp divides directly)
-#else
-  const double rq = rcp_refined(den);
-  const double q = div_rcp(num, den, rq);
-#if FSDP_GIVENS_RSQ_SEED
-  const double x = 1.0 + q * q;
-  // sqrt_1_2(x), keeping h
-  double y = __builtin_amdgcn_rsq(x);
-  double g = x * y;
-  double h = y * 0.5;
-  double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  const double r0 = (rq + rq) * h;  // ~ 1 / (den sqrt(x)), off the chain
-  double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  g = fma(d, h, g);
-  dd = den * g;
-  const double e = fma(-dd, r0, 1.0);
-  rd = fma(r0, e, r0);
-#else
-  dd = den * sqrt_1_2(1.0 + q * q);
-  rd = rcp_refined(dd);
-#endif
-#endif
-}
 
 // fpgivs with the scaling-free divisions (the arithmetic of giv_step<true>: max / min instead of the branch, two refined reciprocals,
 // sqrt_1_2) for the rotations of the smoothing rows; operands outside the divisions' exponent band set `bad` (the frame is then
@@ -667,18 +547,7 @@ __device__ __forceinline__ void giv_flush(WS& ws, const GivLane& st, int lane, i
   }
 }
 
-__device__ __forceinline__ double quad_prev(double d) {  // value of the previous lane of the quad (lane 0 <- lane 3)
-#ifdef FSDP_EMU
-  int l = emu::B->cur;
-  return emu::gexchange(d, (l & ~3) | ((l + 3) & 3), 4);
-#else
-  int lo = __double2loint(d), hi = __double2hiint(d);
-  lo = __builtin_amdgcn_mov_dpp(lo, 0x93, 0xf, 0xf, true);  // quad_perm:[3,0,1,2]
-  hi = __builtin_amdgcn_mov_dpp(hi, 0x93, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-#endif
-}
-
+// (quad_prev, the value of the previous lane of the quad, lane 0 <- lane 3: device_prims.h)
 // One pipeline step on every lane.  feed: the stage-1 lane takes the data row (h0..h3, x, y); otherwise nothing enters.
 template <bool FAST>
 __device__ __forceinline__ void giv_step(GivLane& st, bool feed, double h0, double h1, double h2, double h3, double dx, double dy) {
@@ -845,27 +714,7 @@ __device__ __forceinline__ void giv_flush(WS& ws, const GivGridLane& st, int lan
     }
   }
 }
-// DPP moves of a double inside a row of 16 lanes.  CTRL: 0x124 = row_ror:4 (lane i <- lane i - 4 mod 16), 0x00 = quad_perm
-// [0,0,0,0], 0xE9 = quad_perm [1,2,2,3]
-template <int CTRL>
-__device__ __forceinline__ double dpp_row16(double d) {
-#ifdef FSDP_EMU
-  const int l = emu::B->cur, r = l & 15, base = l & ~15;
-  int src;
-  if (CTRL == 0x124)
-    src = base | ((r + 12) & 15);
-  else if (CTRL == 0x00)
-    src = l & ~3;
-  else
-    src = (l & ~3) | ((l & 3) == 0 ? 1 : ((l & 3) == 3 ? 3 : 2));
-  return emu::gexchange(d, src, 16);
-#else
-  int lo = __double2loint(d), hi = __double2hiint(d);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-#endif
-}
+// (dpp_row16<CTRL>, the DPP moves of a double inside a row of 16 lanes: device_prims.h)
 // One pipeline step.  feed: the stage-1 quad takes the data row: h0 = its first element (pivot), fA / fB = this lane's element(s)
 // of it (e = 0..2: h1 / h2 / h3, 0; e = 3: x, y).
 template <bool FAST>
@@ -976,16 +825,11 @@ struct GivState<true> {
 // does the arithmetic and writes the terms to tbuf[0..cnt) (the chunk's basis buffer, idle here) and, when FLAGS, the
 // "a new knot interval starts at this point" flags to fbuf.  The caller issues the next super-chunk's load() before
 // the serial accumulation of the current one, so the scratch round trip hides behind it.
-#ifndef RB_MAX_ROUNDS
-#define RB_MAX_ROUNDS 2  // rounds of a residual super-chunk held in registers (2: fit_kernel fits three wavefronts per SIMD)
-#endif
+constexpr int RB_ROUNDS = 2;  // rounds of a residual super-chunk held in registers (2: fit_kernel fits three wavefronts per SIMD)
+constexpr int RB_ROUNDS_G4 = 2 * RB_ROUNDS;  // (4 lanes per frame: fit_kernel<4> runs at two wavefronts per SIMD and has the registers for four rounds in flight)
 template <int K, int G, bool FLAGS, int CHV, bool RC = false>  // RC: basis values from the parameter value and the workspace's reciprocal table
 struct ResidualBatch {
-  // (4 lanes per frame: fit_kernel<4> runs at two wavefronts per SIMD and has the registers for four rounds in flight)
-#ifndef FSDP_RB_G4
-#define FSDP_RB_G4 (2 * RB_MAX_ROUNDS)
-#endif
-  static constexpr int RB_CAP = (G == 4) ? FSDP_RB_G4 : RB_MAX_ROUNDS;
+  static constexpr int RB_CAP = (G == 4) ? RB_ROUNDS_G4 : RB_ROUNDS;
   static constexpr int ROUNDS = (4 * CHV / G > RB_CAP) ? RB_CAP : 4 * CHV / G;
   static constexpr int k1 = K + 1, k2 = K + 2;
   double hv[ROUNDS][RC ? 1 : K + 1], xv[ROUNDS], yv[ROUNDS];
@@ -1018,12 +862,8 @@ struct ResidualBatch {
       }
       xv[q] = X[it];
       yv[q] = Y[it];
-#ifdef FSDP_PAD_LOADS
-      {  // experiment: 32 more bytes per point and pass from lines nobody else touches (is the kernel bound by its scratch stream?)
-        const D2 e0 = bc.rec[it + 704].h01, e1 = bc.rec[it + 704].h23;
-        asm volatile("" ::"v"(e0.a), "v"(e0.b), "v"(e1.a), "v"(e1.b));
-      }
-#endif
+      // (is the kernel bound by its scratch stream?  An experiment read 32 more bytes per point and pass here, from lines nobody
+      // else touches: +47 % bytes, +31 % kernel time — profiles/NOTES.md, profiles/r04_ab_variants.txt)
     }
   }
 
@@ -1146,11 +986,7 @@ __device__ __forceinline__ SplineFit spline_fit_k(WS& ws, const BasisCache& bc, 
       GR::sync();
       fp = 0.0;
       // (groups of 16 lanes and more: the step on a 4 x 4 lane grid, two rotation slots per lane instead of five)
-#ifndef FSDP_NO_GIV_GRID
       typename GivState<(G >= 16)>::type gst;
-#else
-      GivLane gst;
-#endif
       giv_init(gst);
       if constexpr (WS::RECOMPUTE) {
         static_assert(!WS::RECOMPUTE || (FAST && K == 3), "the reciprocal table serves the scaling-free cubic fit only");
