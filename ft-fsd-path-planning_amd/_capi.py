@@ -229,8 +229,24 @@ EXPORTED_SYMBOLS = [
     "fsdp_host_alloc", "fsdp_host_free", "fsdp_host_register", "fsdp_host_unregister", "fsdp_host_is_pinned", "fsdp_submit", "fsdp_collect", "fsdp_ticket_done",
     "fsdp_submit_compact", "fsdp_plan_batch_compact", "fsdp_set_option", "fsdp_pcie_probe",
     "fsdp_skidpad_submit", "fsdp_route_stats", "fsdp_ticket_capacity", "fsdp_selftest_det3", "fsdp_debug_arena", "fsdp_selftest_absminmax", "fsdp_selftest_libm", "fsdp_selftest_givens",
-    "fsdp_sort_cache_reset", "fsdp_sort_cache_hits",
+    "fsdp_sort_cache_reset", "fsdp_sort_cache_hits", "fsdp_sort_batch_ranked",
 ]
+RANK_MAX, COST_TERMS = 64, 7  # include/fsdp.h FSDP_RANK_MAX, FSDP_COST_TERMS
+COST_TERM_NAMES = ("angle", "residual_distance", "number_of_cones", "initial_direction", "change_of_direction", "cones_on_either",
+                   "wrong_direction")  # cost_function.py:287-296
+
+
+def decision_margin(costs) -> np.ndarray:
+    """(c1 - c0) / max(|c0|, 1e-300) over the last axis of ranked costs (..., top_k): how far the runner-up of a side is from its
+    winner, relative to the winner's cost; inf where the side has fewer than two candidates (NaN rows)."""
+    costs = np.asarray(costs, dtype=np.float64)
+    out = np.full(costs.shape[:-1], np.inf)
+    if costs.shape[-1] >= 2:
+        c0, c1 = costs[..., 0], costs[..., 1]
+        two = ~np.isnan(c0) & ~np.isnan(c1)
+        out[two] = (c1[two] - c0[two]) / np.maximum(np.abs(c0[two]), 1e-300)
+    return out
+
 
 
 def host_lib() -> ctypes.CDLL:
@@ -456,6 +472,23 @@ class Context:
         out = np.zeros(n, dtype=self.result_dtype)
         self._check(self._lib.fsdp_sort_batch(self._h, n, _ip(offsets), _dp(cones), _dp(poses), ctypes.c_void_p(out.ctypes.data)), "fsdp_sort_batch")
         return out
+
+    def sort_batch_ranked(self, offsets, cones, poses, top_k: int = 8, terms: bool = True):
+        """fsdp_sort_batch_ranked: sort_batch plus, per frame and side (0 left, 1 right), the end configurations after the post
+        filters ranked by cost -> (results, counts (n,2), configs (n,2,top_k,max_len) -1 padded, costs (n,2,top_k), terms
+        (n,2,top_k,7) weighted cost columns or None).  counts is never truncated; rows beyond min(counts, top_k) hold -1 / NaN."""
+        offsets, cones, poses, n = self._prep(offsets, cones, poses)
+        k = max(1, min(int(top_k), RANK_MAX))  # (array shapes only: the library refuses a top_k outside 1..RANK_MAX)
+        out = np.zeros(n, dtype=self.result_dtype)
+        counts = np.zeros((n, 2), np.int32)
+        configs = np.full((n, 2, k, self.shapes.max_len), -1, np.int32)
+        costs = np.full((n, 2, k), np.nan)
+        tm = np.full((n, 2, k, COST_TERMS), np.nan) if terms else None
+        self._check(self._lib.fsdp_sort_batch_ranked(self._h, n, _ip(offsets), _dp(cones), _dp(poses), ctypes.c_void_p(out.ctypes.data), int(top_k),
+                                                     ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(configs.ctypes.data),
+                                                     ctypes.c_void_p(costs.ctypes.data), ctypes.c_void_p(tm.ctypes.data) if terms else None),
+                    "fsdp_sort_batch_ranked")
+        return out, counts, configs, costs, tm
 
     def match_batch(self, sorted_left, n_left, sorted_right, n_right, poses) -> np.ndarray:
         sorted_left = np.ascontiguousarray(sorted_left, np.float64).reshape(-1, self.shapes.max_len, 2)

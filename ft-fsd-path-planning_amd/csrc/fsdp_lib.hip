@@ -27,6 +27,7 @@
 #include "assemble_kernel.h"
 #include "filter_kernel.h"
 #include "fsdp_comm.h"
+#include "sort_rank_kernels.h"  // (last: the kernels in front of it keep their order in the code object)
 
 using namespace fsdp;
 
@@ -2005,14 +2006,51 @@ static Work& stage_slot(fsdp_ctx* c) {
   return c->slot[0];
 }
 
-int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
-                    fsdp_frame_result* results) {
+// The ranked outputs of fsdp_sort_batch_ranked on the device for the duration of one call (a diagnostic route: allocated per call)
+struct RankCall {
+  int top_k = 0;
+  int32_t* counts = nullptr;   // caller's arrays
+  int32_t* configs = nullptr;
+  double* costs = nullptr;
+  double* terms = nullptr;
+  int32_t* d_counts = nullptr;
+  int32_t* d_configs = nullptr;
+  double* d_costs = nullptr;
+  double* d_terms = nullptr;
+  SortRankScratchBig* d_scratch = nullptr;
+  ~RankCall() {
+    (void)hipFree(d_counts);
+    (void)hipFree(d_configs);
+    (void)hipFree(d_costs);
+    (void)hipFree(d_terms);
+    (void)hipFree(d_scratch);
+  }
+};
+
+// fsdp_sort_batch, and with rk fsdp_sort_batch_ranked (the ranked kernels instead of the plain ones, never the sorting cache)
+static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
+                           fsdp_frame_result* results, RankCall* rk) {
+  const char* who = rk ? "fsdp_sort_batch_ranked" : "fsdp_sort_batch";
   if (!c) return 1;
-  if (c->outstanding) return busy_error(c, "fsdp_sort_batch");
+  if (rk) {
+    if (c->mission == 2) {
+      c->err = "fsdp_sort_batch_ranked: a skidpad context never sorts cones";
+      return 1;
+    }
+    if (rk->top_k < 1 || rk->top_k > FSDP_RANK_MAX) {
+      c->err = "fsdp_sort_batch_ranked: top_k must be in 1.." FSDP_STR(FSDP_RANK_MAX);
+      return 1;
+    }
+    if (n_frames > 0 && (!rk->counts || !rk->configs || !rk->costs)) {
+      c->err = "fsdp_sort_batch_ranked: NULL counts / configs / costs";
+      return 1;
+    }
+  }
+  if (c->outstanding) return busy_error(c, who);
   HIP_TRY(c, hipSetDevice(c->device));
   Batch b;
   if (int rc = check_batch(c, n_frames, off, cones, poses, nullptr, &b)) return rc;
-  const bool cached = c->n_cache > 0;
+  const bool cached = !rk && c->n_cache > 0;
   if (cached && n_frames != c->n_cache) return cache_prepare(c, n_frames, off, "fsdp_sort_batch");
   if (n_frames == 0) return 0;
   if (int rc = sync_all(c)) return rc;
@@ -2027,12 +2065,53 @@ int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double*
   if (filtered)
     if (int rc = launch_filter(c, q, q.in, &fin)) return rc;
   const Inputs& in = filtered ? fin : q.in;
-  launch_sort(c, q, in, StageIn());
-  if (int rc = launch_sort_big(c, q, in)) return rc;
+  const size_t rows = rk ? (size_t)n_frames * 2 * (size_t)rk->top_k : 0;
+  if (rk) {
+    HIP_TRY(c, hipMalloc(&rk->d_counts, sizeof(int32_t) * 2 * (size_t)n_frames));
+    HIP_TRY(c, hipMalloc(&rk->d_configs, sizeof(int32_t) * rows * MAX_LEN));
+    HIP_TRY(c, hipMalloc(&rk->d_costs, sizeof(double) * rows));
+    if (rk->terms) HIP_TRY(c, hipMalloc(&rk->d_terms, sizeof(double) * rows * COST_TERMS));
+    HIP_TRY(c, hipMalloc(&rk->d_scratch, sizeof(SortRankScratchBig) * SORT_BIG_BLOCKS));
+    // unused rows: -1 indices, NaN costs and terms; a side without a result writes nothing
+    HIP_TRY(c, hipMemsetAsync(rk->d_counts, 0, sizeof(int32_t) * 2 * (size_t)n_frames, q.stream));
+    HIP_TRY(c, hipMemsetAsync(rk->d_configs, 0xff, sizeof(int32_t) * rows * MAX_LEN, q.stream));
+    HIP_TRY(c, hipMemsetAsync(rk->d_costs, 0xff, sizeof(double) * rows, q.stream));
+    if (rk->terms) HIP_TRY(c, hipMemsetAsync(rk->d_terms, 0xff, sizeof(double) * rows * COST_TERMS, q.stream));
+    if (c->poison) {
+      HIP_TRY(c, hipMemsetAsync(q.d_sort, 0xff, sizeof(SortOut) * (size_t)n_frames, q.stream));
+      HIP_TRY(c, hipMemsetAsync(rk->d_scratch, 0xff, sizeof(SortRankScratchBig) * SORT_BIG_BLOCKS, q.stream));
+    }
+    SortRankView v;
+    v.top_k = rk->top_k;
+    v.counts = rk->d_counts;
+    v.configs = rk->d_configs;
+    v.costs = rk->d_costs;
+    v.terms = rk->d_terms;
+    const bool small = sort128(c, in);
+    if (small)
+      hipLaunchKernelGGL(sort_kernel_128_ranked, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
+                         q.d_sort, q.d_big, c->d_params, v);
+    else
+      hipLaunchKernelGGL(sort_kernel_ranked, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses, q.d_sort,
+                         q.d_big, c->d_params, v);
+    if (!q.d_sort_big) HIP_TRY(c, hipMalloc(&q.d_sort_big, sizeof(SortSharedBig) * SORT_BIG_BLOCKS));
+    hipLaunchKernelGGL(sort_big_kernel_ranked, dim3(SORT_BIG_BLOCKS), dim3(WAVE), 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big,
+                       q.d_sort_big, c->d_params, v, rk->d_scratch);
+    c->stage_names = std::string(small ? "sort_kernel_128_ranked" : "sort_kernel_ranked") + ",sort_big_kernel_ranked";
+  } else {
+    launch_sort(c, q, in, StageIn());
+    if (int rc = launch_sort_big(c, q, in)) return rc;
+  }
   HIP_TRY(c, hipMemsetAsync(q.d_big, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
   HIP_TRY(c, grow_pinned(c->h_sort, c->cap_sort, (size_t)n_frames, hipHostMallocDefault, 64));
   HIP_TRY(c, hipMemcpyAsync(c->h_sort, q.d_sort, sizeof(SortOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
   std::vector<int32_t> map, moff;
+  if (rk) {
+    HIP_TRY(c, hipMemcpyAsync(rk->counts, rk->d_counts, sizeof(int32_t) * 2 * (size_t)n_frames, hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(rk->configs, rk->d_configs, sizeof(int32_t) * rows * MAX_LEN, hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(rk->costs, rk->d_costs, sizeof(double) * rows, hipMemcpyDeviceToHost, q.stream));
+    if (rk->terms) HIP_TRY(c, hipMemcpyAsync(rk->terms, rk->d_terms, sizeof(double) * rows * COST_TERMS, hipMemcpyDeviceToHost, q.stream));
+  }
   if (filtered) {  // indices back into the caller's index space (what assemble_kernel does for a full pass)
     map.resize(b.total ? b.total : 1);
     moff.resize((size_t)n_frames + 1);
@@ -2057,9 +2136,29 @@ int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double*
         back(results[i].first_k_left[k]);
         back(results[i].first_k_right[k]);
       }
+      if (rk) {
+        int32_t* rows_i = rk->configs + (size_t)i * 2 * (size_t)rk->top_k * MAX_LEN;
+        for (size_t k = 0; k < 2 * (size_t)rk->top_k * MAX_LEN; k++) back(rows_i[k]);
+      }
     }
   }
   return 0;
+}
+
+int fsdp_sort_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
+                    fsdp_frame_result* results) {
+  return sort_batch_impl(c, n_frames, off, cones, poses, results, nullptr);
+}
+
+int fsdp_sort_batch_ranked(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
+                           fsdp_frame_result* results, int top_k, int32_t* counts, int32_t* configs, double* costs, double* terms) {
+  RankCall rk;
+  rk.top_k = top_k;
+  rk.counts = counts;
+  rk.configs = configs;
+  rk.costs = costs;
+  rk.terms = terms;
+  return sort_batch_impl(c, n_frames, off, cones, poses, results, &rk);
 }
 
 int fsdp_match_batch(fsdp_ctx* c, int n_frames, const double* sorted_left, const int32_t* n_left, const double* sorted_right,

@@ -19,6 +19,7 @@
 
 #include "fsdp_device.h"
 #include "sort_cache.h"
+#include "sort_rank.h"
 
 namespace fsdp {
 
@@ -163,8 +164,9 @@ __device__ inline bool inside_ellipse_of_edge(double px, double py, double cx, d
 // end_configurations.py:108-223 for ONE candidate neighbour `cand` of the popped node.
 // check_if_neighbor_lies_between_last_in_attempt_and_candidate (:226-257) for one (candidate, neighbour) pair
 // (CACHE, here and below: the cache-enabled kernels get their own copies of the stage's functions, so that the kernels without the cache
-// keep the inlining decisions — and hence the code — they had before; the argument changes nothing else)
-template <class SH, bool CACHE = false>
+// keep the inlining decisions — and hence the code — they had before; the argument changes nothing else.  RANKED: the same for the
+// kernels that report the ranked end configurations, sort_rank.h)
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ __forceinline__ bool neighbour_lies_between(const SH& S, int node, int cand, int nb) {  // (cone indices only)
   if (nb == cand) return false;
   const double lx = S.x[node], ly = S.y[node];
@@ -180,7 +182,7 @@ __device__ __forceinline__ bool neighbour_lies_between(const SH& S, int node, in
 // two edges of the attempt (ang_sl: attempt[pos-1] -> node, ang_tl: attempt[pos-2] -> attempt[pos-1]) are the atan2
 // values computed when those cones were candidates themselves (same operands, same bits); ang_cand returns the direction
 // of the edge node -> candidate for the candidate's own children.
-template <class SH, bool CACHE = false>
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ inline bool candidate_can_be_added(const SH& S, const Params& P, int side, int cone_type, int pos, int node, int cand, bool between,
                                               double px, double py, double dx, double dy, double dnx, double dny, double a_car,
                                               double ang_sl, double ang_tl, double& ang_cand) {
@@ -257,7 +259,7 @@ __device__ __forceinline__ double np_sum_reg(const double (&a)[MAX_LEN], int n) 
 // colour, so they are the same for this side (no-colour mode builds them once per frame).
 // CACHE: the sorting cache's check follows the start cones (core_trace_sorter.py:293-300); a side that reuses the cached
 // result loads it into S.best / best_len / n_configs / best_cost and stays inactive (no adjacency, search or costing).
-template <class SH, bool CACHE = false>
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ __forceinline__ void sort_side_prepare(SH& S, const Params& P, int n, int cone_type, int side, double px, double py, double dx,
                                          double dy, bool reuse_adjacency, SortCacheFrame* cf = nullptr) {
   const int lane = lane_id();
@@ -574,7 +576,7 @@ struct PairMask<true> {
 // Phase 2 (S8): DFS over the cost tree (end_configurations.py:320-431) of BOTH sides at once, one half-wavefront per
 // side.  A pop keeps at most 5 candidate lanes and 25 (candidate, neighbour) lanes busy, so the two independent searches
 // share every instruction; the loop runs until both stacks are empty.
-template <class SH, bool CACHE = false>
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double py, double dx, double dy) {
   const int lane = lane_id();
   const int side = lane >> 5, sl = lane & 31;
@@ -639,7 +641,7 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
     for (int r = 0; r < PAIR_ROUNDS; r++) {
       const int pr = sl + 32 * r;
       bool btw = false;
-      if (pr < n_nb * n_nb) btw = neighbour_lies_between<SH, CACHE>(S, node, S.nbr[adj][node][pr / n_nb], S.nbr[adj][node][pr % n_nb]);
+      if (pr < n_nb * n_nb) btw = neighbour_lies_between<SH, CACHE, RANKED>(S, node, S.nbr[adj][node][pr / n_nb], S.nbr[adj][node][pr % n_nb]);
       bm |= (pair_mask_t)(unsigned)(__ballot(btw) >> (32 * side)) << (32 * r);
     }
     bool can = false;
@@ -647,7 +649,7 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
     if (sl < n_nb) {
       const bool between = ((bm >> (sl * n_nb)) & (((pair_mask_t)1 << n_nb) - 1u)) != 0u;
       const double ang_tl = (pos >= 2) ? S.attempt_ang[side][pos - 1] : 0.0;
-      can = candidate_can_be_added<SH, CACHE>(S, P, side, cone_type, pos, node, S.nbr[adj][node][sl], between, px, py, dx, dy, dnx, dny, a_car,
+      can = candidate_can_be_added<SH, CACHE, RANKED>(S, P, side, cone_type, pos, node, S.nbr[adj][node][sl], between, px, py, dx, dy, dnx, dny, a_car,
                                    node_ang, ang_tl, cand_ang);
     }
     const unsigned m = (unsigned)(__ballot(can) >> (32 * side));
@@ -679,9 +681,9 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
 }
 
 // Phase 3 of a side (S10-S12): post filters, side counting, costs, pick.  Returns the frame status of this side.
-template <class SH, bool CACHE = false>
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ __forceinline__ int sort_side_finish(SH& S, int n, int cone_type, int side, double px, double py, double dx,
-                                       double dy) {
+                                       double dy, const SortRankFrame* rk = nullptr) {
   const int lane = lane_id();
   const int other_type = (cone_type == T_LEFT) ? T_RIGHT : T_LEFT;
   if (S.ctl[side].status != ST_OK) return S.ctl[side].status;
@@ -1100,6 +1102,17 @@ __device__ __forceinline__ int sort_side_finish(SH& S, int n, int cone_type, int
         my_cost += either_cost * f3;
         my_cost += wrong_cost * f3;
         S.cost[cid] = my_cost;
+        if constexpr (RANKED) {
+          // the seven addends above (cost_function.py:287-296 column order) wait for the ranking outside the frame state
+          double* t = rk->terms + (size_t)cid * COST_TERMS;
+          t[0] = angle_cost * f0;
+          t[1] = dist_cost * f1;
+          t[2] = ncones_cost * f2;
+          t[3] = init_cost * f3;
+          t[4] = 0.0 * f4;
+          t[5] = either_cost * f3;
+          t[6] = wrong_cost * f3;
+        }
       }
     }
   }
@@ -1139,11 +1152,12 @@ __device__ __forceinline__ int sort_side_finish(SH& S, int n, int cone_type, int
   }
   __syncthreads();
   PROF_MARK(7);  // closes section 6 (slot 7 unused)
+  if constexpr (RANKED) sort_rank_side(S, *rk, side, n_ends, C);
   return ST_OK;
 }
 
 // combine_traces.py:115-275 (wave-uniform; every lane computes the same scalars)
-template <class SH, bool CACHE = false>
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ inline void combine_sides(SH& S, int& nl, int& nr) {
   nl = S.best_len[0];
   nr = S.best_len[1];
@@ -1327,10 +1341,10 @@ __device__ inline void sort_cache_commit(const SH& S, const SortCacheFrame& cf, 
 
 // The sorting stage of one frame on one wavefront; S = the frame state (LDS or global memory).  CACHE: the sorting cache of
 // planner cache->base + frame is read and its next entry written (sort_cache.h).
-template <class SH, bool CACHE = false>
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
                                   const double* __restrict__ poses, SortOut* __restrict__ out, const StageIn& stage = StageIn(),
-                                  const SortCacheView* cache = nullptr) {
+                                  const SortCacheView* cache = nullptr, const SortRankFrame* rank = nullptr) {
   const int lane = lane_id();
   const bool staging = stage.src_off != nullptr;
   const int32_t* offs = staging ? stage.src_off : cone_offsets;
@@ -1354,6 +1368,11 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
   }
   SortOut* o = &out[frame];
   int status = ST_OK;
+  SortRankFrame rk;
+  if constexpr (RANKED) {
+    rk = *rank;
+    rk.frame = frame;
+  }
   if (n > SH::MAX_N) {
     status = ST_OVERFLOW_CONES;
     n = 0;
@@ -1427,20 +1446,20 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
 #define FSDP_SORT_STOP 9  // (instruction accounting builds stop the stage after phase 1..4: tools/sort_phase_insts.sh)
 #endif
   if (status == ST_OK && FSDP_SORT_STOP > 1) {
-    sort_side_prepare<SH, CACHE>(S, P, n, T_LEFT, 0, px, py, dx, dy, false, &cf);
+    sort_side_prepare<SH, CACHE, RANKED>(S, P, n, T_LEFT, 0, px, py, dx, dy, false, &cf);
     // (the left call returns before building the adjacency when it finds no start cone or n < 3, or reuses the cached result)
     const bool left_built = S.adj_built != 0;
-    sort_side_prepare<SH, CACHE>(S, P, n, T_RIGHT, 1, px, py, dx, dy, colourless && left_built, &cf);
-    if (FSDP_SORT_STOP > 2) sort_dfs_both<SH, CACHE>(S, P, px, py, dx, dy);
+    sort_side_prepare<SH, CACHE, RANKED>(S, P, n, T_RIGHT, 1, px, py, dx, dy, colourless && left_built, &cf);
+    if (FSDP_SORT_STOP > 2) sort_dfs_both<SH, CACHE, RANKED>(S, P, px, py, dx, dy);
     if (FSDP_SORT_STOP > 3) {
-      status = sort_side_finish<SH, CACHE>(S, n, T_LEFT, 0, px, py, dx, dy);
+      status = sort_side_finish<SH, CACHE, RANKED>(S, n, T_LEFT, 0, px, py, dx, dy, &rk);
       __syncthreads();
-      if (status == ST_OK) status = sort_side_finish<SH, CACHE>(S, n, T_RIGHT, 1, px, py, dx, dy);
+      if (status == ST_OK) status = sort_side_finish<SH, CACHE, RANKED>(S, n, T_RIGHT, 1, px, py, dx, dy, &rk);
     }
   }
   __syncthreads();
   int nl = 0, nr = 0;
-  if (status == ST_OK && FSDP_SORT_STOP > 4) combine_sides<SH, CACHE>(S, nl, nr);
+  if (status == ST_OK && FSDP_SORT_STOP > 4) combine_sides<SH, CACHE, RANKED>(S, nl, nr);
   if (lane == 0) {
     o->status = status;
     o->n_left = nl;
@@ -1459,21 +1478,23 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
     o->right_idx[lane] = (status == ST_OK && lane < nr) ? (int32_t)S.best[1][lane] : -1;
   }
   if constexpr (CACHE) sort_cache_commit(S, cf, n, status);
+  if constexpr (RANKED) sort_rank_close(rk, status, S.n_configs[0], S.n_configs[1]);
   __syncthreads();
 }
 
 // One workgroup (= one wavefront) per frame, frame state in LDS.  big (optional): [0] = counter, [1..] = frames beyond
 // the LDS capacities (more cones than the state holds, more than 64 raw end configurations), planned again by
 // sort_big_kernel.
-template <class SH, bool CACHE = false>
+template <class SH, bool CACHE = false, bool RANKED = false>
 __device__ __forceinline__ void sort_kernel_body(SH& S, int n_frames, const int32_t* __restrict__ cone_offsets,
                                                  const double* __restrict__ cones_xyt, const double* __restrict__ poses,
                                                  SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
-                                                 const StageIn& stage, const SortCacheView* cache = nullptr) {
+                                                 const StageIn& stage, const SortCacheView* cache = nullptr,
+                                                 const SortRankFrame* rank = nullptr) {
   const int frame = blockIdx.x;
   if (frame >= n_frames) return;
   PROF_INIT();
-  sort_frame<SH, CACHE>(S, *prm, frame, cone_offsets, cones_xyt, poses, out, stage, cache);
+  sort_frame<SH, CACHE, RANKED>(S, *prm, frame, cone_offsets, cones_xyt, poses, out, stage, cache, rank);
   if (big != nullptr && lane_id() == 0 && (out[frame].status == ST_OVERFLOW_CONES || out[frame].status == ST_OVERFLOW_ENDS))
     big[1 + atomicAdd(&big[0], 1)] = frame;
   PROF_FLUSH();

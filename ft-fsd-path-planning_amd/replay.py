@@ -4,6 +4,7 @@ loop :103-131).  Same file schema: a list of {"car_position":[x,y], "car_directi
 
   python -m fsd_path_planning_amd.replay --data-path fsg_19_2_laps.json [--remove-color-info] [--batched] [--output-path out.npz]
                                           [--experimental-performance-improvements]  (per-frame mode only)
+                                          [--ranked K]  (per frame: decision margins and deciding cost terms of the sorting stage)
 
 Two replay modes:
   per-frame : one PathPlanner, one calculate_path_in_global_frame call per frame, wall-clock per call (what the
@@ -157,6 +158,33 @@ def replay_batched(mission, positions, directions, observations, device=None, re
     return res, sec
 
 
+def replay_ranked(mission, positions, directions, observations, top_k: int, device=None, batch_frames: int = 4096):
+    """The recording's frames as independent frames through fsdp_sort_batch_ranked: per frame and side (left, right) the
+    decision margin (c1 - c0) / max(|c0|, 1e-300) of the sorting stage's choice (inf: fewer than two candidates) and the
+    deciding term — the column of the seven weighted costs (cost_function.py:287-296) in which the runner-up differs most from
+    the winner, -1 without a runner-up.  Returns (status (F,), counts (F, 2), margins (F, 2), deciding (F, 2))."""
+    from . import _capi
+
+    planner = PathPlanner(mission, device=device)
+    ctx = planner._ctx
+    frames = list(zip(observations, positions, directions))
+    k = max(2, int(top_k))
+    status, counts, margins, deciding = [], [], [], []
+    for lo in range(0, len(frames), batch_frames):
+        off, cones, poses = pack_frames(frames[lo:lo + batch_frames])
+        res, cnt, _cfg, costs, terms = ctx.sort_batch_ranked(off, cones, poses, top_k=k)
+        m = _capi.decision_margin(costs)
+        with np.errstate(invalid="ignore"):
+            diff = terms[:, :, 1, :] - terms[:, :, 0, :]
+        d = np.where(np.isfinite(m), np.argmax(np.nan_to_num(diff, nan=-np.inf), axis=-1), -1)
+        status.append(res["status"].copy())
+        counts.append(cnt)
+        margins.append(m)
+        deciding.append(d)
+    cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)  # noqa: E731
+    return cat(status, 0, np.int32), cat(counts, (0, 2), np.int32), cat(margins, (0, 2), np.float64), cat(deciding, (0, 2), np.int64)
+
+
 FB_READ_PREVIOUS = 1 | 2 | 4 | 8  # path_fallback bits of the branches that read previous_paths[-1] (include/fsdp.h)
 
 
@@ -195,7 +223,25 @@ def main(argv=None):
     ap.add_argument("--depth", type=int, default=4, help="--batched: batches in flight")
     ap.add_argument("--experimental-performance-improvements", action="store_true",
                     help="per-frame replay: the reference's sorting cache (PathPlanner(mission, True))")
+    ap.add_argument("--ranked", type=int, default=None, metavar="K",
+                    help="instead of a timed replay: rank the K best end configurations of every frame and side and print, per frame, the "
+                         "decision margins (left, right) and the deciding cost terms (trackdrive / autocross recordings)")
     a = ap.parse_args(argv)
+    if a.ranked is not None:
+        from ._capi import COST_TERM_NAMES
+
+        mission = select_mission_by_filename(a.data_path.name)
+        positions, directions, observations = load_data_json(a.data_path, a.remove_color_info)
+        status, counts, margins, deciding = replay_ranked(mission, positions, directions, observations, a.ranked, a.device, a.batch_frames)
+        for f in range(len(status)):
+            print(json.dumps({"frame": f, "status": int(status[f]), "candidates": [int(c) for c in counts[f]],
+                              "margin": [float(m) if np.isfinite(m) else None for m in margins[f]],
+                              "deciding_term": [int(d) for d in deciding[f]],
+                              "deciding_term_name": [COST_TERM_NAMES[d] if d >= 0 else None for d in deciding[f]]}))
+        fin = margins[np.isfinite(margins)]
+        print(json.dumps({"file": str(a.data_path), "mission": mission.name, "frames": len(status), "mode": "ranked", "top_k": max(2, a.ranked),
+                          "sides_with_a_runner_up": int(fin.size), "smallest_margin": float(fin.min()) if fin.size else None}))
+        return
     if a.batched and a.experimental_performance_improvements:
         ap.error("--experimental-performance-improvements is state of one planner: per-frame replay only (not with --batched)")
     mission = select_mission_by_filename(a.data_path.name)

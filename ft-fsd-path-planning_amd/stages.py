@@ -93,6 +93,25 @@ class ConeSorting:
         self.last_result = r
         return xyt[r["left_idx"][: r["n_left"]], :2], xyt[r["right_idx"][: r["n_right"]], :2]
 
+    def ranked_configurations(self, top_k=None):
+        """The candidates behind run_cone_sorting's choice for the current input, per side (left, right): ``(costs,
+        configurations, individual_costs)`` — the sorted pair calc_scores_and_end_configurations returns
+        (find_configs_and_scores.py:108-112: costs (C,), configurations (C, max_length) of indices into the flattened cones,
+        -1 padded) and the matrix of cost_configurations(..., return_individual_costs=True) (cost_function.py:283-302: (C, 7)
+        weighted columns) with its rows in that order.  top_k None: as many as one call returns (64 per side); a side without a
+        result gives None.  Plans the frame afresh: it neither uses nor advances the sorting cache."""
+        xyt = flatten_cones_by_type_array(self.input.slam_cones)
+        pose = np.concatenate([np.asarray(self.input.slam_position, float).reshape(2), np.asarray(self.input.slam_direction, float).reshape(2)])
+        ctx = self._own_ctx or _ctx(self._device, self._params)
+        k = _capi.RANK_MAX if top_k is None else int(top_k)
+        res, counts, configs, costs, terms = ctx.sort_batch_ranked(np.array([0, len(xyt)], np.int32), xyt, pose[None], top_k=k)
+        _check(res[0]["status"])
+        out = []
+        for s in range(2):
+            m = min(int(counts[0, s]), k)
+            out.append(None if m == 0 else (costs[0, s, :m].copy(), configs[0, s, :m].astype(np.int64), terms[0, s, :m].copy()))
+        return tuple(out)
+
 
 @dataclass
 class ConeMatchingInput:

@@ -220,7 +220,7 @@ int fsdp_set_previous_paths(fsdp_ctx* ctx, const double* prev_paths);
  *   with another n_frames returns an error and leaves the cache as it was, and so does any failed call.  The chunked form of
  *   the blocking call (16 384+ frames) gives the same results.
  *   No other entry point reads or writes the cache: fsdp_plan_batch[_compact], fsdp_submit* / fsdp_collect, fsdp_upload /
- *   fsdp_run, the match / path stage calls and the skidpad calls plan as if it were off.  Like every call on a context, the
+ *   fsdp_run, fsdp_sort_batch_ranked, the match / path stage calls and the skidpad calls plan as if it were off.  Like every call on a context, the
  *   cache calls are not to be made from two threads at once.
  *   fsdp_sort_cache_hits(ctx, out): per planner and side (left, right) of the most recent cache call, int8 (n, 2):
  *   1 = the cached result was reused, 0 = checked and searched, -1 = the side returned before the check (fewer than 3 cones,
@@ -364,6 +364,27 @@ int fsdp_stage_names(fsdp_ctx* ctx, char* out, int cap);
 /* ConeSorting.run_cone_sorting — fills status, n_left/right, left/right_idx and the sorting diagnostics. */
 int fsdp_sort_batch(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt,
                     const double* poses, fsdp_frame_result* results);
+/* The same call with every side's end configurations ranked by cost — what calc_scores_and_end_configurations
+ * (sorting_cones/trace_sorter/find_configs_and_scores.py:29-112) returns to its callers, sorted costs and configurations, and
+ * what cost_configurations(..., return_individual_costs=True) (cost_function.py:283-302) returns, the seven weighted cost
+ * columns [angle, residual distance, number of cones, initial direction, change of direction (weight 0), cones on either
+ * side, wrong direction] (:287-296).  `results` is filled exactly as fsdp_sort_batch fills it.
+ *   counts  (n_frames,2)                     configurations of the side after the post filters (end_configurations.py:434-520) =
+ *                                            n_configs_left / right; 0 where the side has no result or the frame's status is not 0
+ *   configs (n_frames,2,top_k,FSDP_MAX_LEN)  the first min(counts, top_k) of them, -1 padded, indices into the frame's cones
+ *   costs   (n_frames,2,top_k)               their costs, ascending; equal costs in the lexicographic order of the -1 padded rows
+ *                                            (np.unique's order, kept by the stable argsort): row 0 is the side's winner before
+ *                                            combine_traces, costs[..][0] == best_cost_left / right bit for bit
+ *   terms   (n_frames,2,top_k,FSDP_COST_TERMS)  the weighted columns; their sum in column order is the row's cost bit for bit.
+ *                                            NULL: not wanted.
+ * Side 0 = left, 1 = right.  Unused rows hold -1 (configs) and NaN (costs, terms).  top_k must be in 1..FSDP_RANK_MAX.  With
+ * use_unknown_cones = 0 the indices are mapped back to the caller's array like those of `results`.  A skidpad context returns
+ * an error.  The call plans every frame afresh: it neither reads nor writes the sorting cache (a reused side has no candidates). */
+#define FSDP_RANK_MAX 64    /* = the LDS route's raw end-configuration capacity */
+#define FSDP_COST_TERMS 7   /* cost_function.py:287-296 column order */
+int fsdp_sort_batch_ranked(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt,
+                           const double* poses, fsdp_frame_result* results, int top_k, int32_t* counts, int32_t* configs,
+                           double* costs, double* terms);
 /* ConeMatching.run_cone_matching — sorted_left/right: (n_frames,FSDP_MAX_LEN,2) padded, counts (n_frames,). */
 int fsdp_match_batch(fsdp_ctx* ctx, int n_frames, const double* sorted_left, const int32_t* n_left,
                      const double* sorted_right, const int32_t* n_right, const double* poses,

@@ -1,0 +1,191 @@
+"""Ranked sorting candidates on the GPU (include/fsdp.h fsdp_sort_batch_ranked, Context.sort_batch_ranked): order, costs and
+counts against the oracle's side_configs, the seven cost terms against the reference capture tests/golden/sort_ranked.npz
+(costs and terms within rtol 1e-12: they hold the device libm's atan2 / acos, tests/test_gpu_parity.py:82), the invariants
+that tie the call to fsdp_sort_batch, the index mapping without UNKNOWN cones, and what the call refuses."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import oracle_lib
+import oracle_lib_wide
+import sort_ranked_support as sup
+
+pytestmark = pytest.mark.gpu
+
+GPU_RTOL = 1e-12
+RAN = set()  # the ranked kernels behind the calls of this module (fsdp_stage_names)
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import importlib
+
+    return importlib.import_module("ft-fsd-path-planning_amd")
+
+
+def stage_names(ctx):
+    buf = ctypes.create_string_buffer(512)
+    assert ctx._lib.fsdp_stage_names(ctx._h, buf, 512) == 0
+    return buf.value.decode().split(",")
+
+
+def gpu_run(ctx):
+    def run(off, cones, poses, top_k=64, terms=True):
+        out = ctx.sort_batch_ranked(off, cones, poses, top_k=top_k, terms=terms)
+        RAN.update(stage_names(ctx))
+        return out
+
+    return run
+
+
+def check_batch(pkg, ctx, oracle, off, cones, poses, oracle_cones=None):
+    run = gpu_run(ctx)
+    got = run(off, cones, poses)
+    with oracle.math_mode(1):
+        stats = sup.check_against_oracle(oracle, off, cones, poses, got, GPU_RTOL, oracle_cones=oracle_cones)
+    sup.check_call_invariants(run, ctx.sort_batch, off, cones, poses, got)
+    ctx.set_option("poison", 1)  # whatever the buffers held before: the outputs do not depend on it
+    try:
+        again = run(off, cones, poses)
+    finally:
+        ctx.set_option("poison", 0)
+    assert sup.same_records(again[0], got[0]) and all(sup.same_bits(a, b) for a, b in zip(again[1:], got[1:]))
+    return got, stats
+
+
+@pytest.mark.parametrize("no_sort128", [0, 1])
+def test_ranking_equals_oracle_and_reference_terms(pkg, golden_dir, no_sort128):
+    """items 1-3 on the frames of sort_ranked.npz; no_sort128 = 1 selects the 255-cone state for every frame"""
+    g, batches = sup.fixture_batches(golden_dir)
+    ctx = pkg._capi.Context(device=0, options={"no_sort128": no_sort128})
+    multi = rows = left_out = 0
+    for frames, off, cones, poses in batches:
+        got, (m, _ties) = check_batch(pkg, ctx, oracle_lib, off, cones, poses)
+        multi += m
+        for level in ("", "_libm"):
+            r, o = sup.check_terms_against_fixture(g, frames, got, GPU_RTOL, level)
+        rows, left_out = rows + r, left_out + o
+    assert multi >= 8 and rows >= 300 and left_out <= 2
+    assert "sort_kernel_ranked" in RAN and ("sort_kernel_128_ranked" in RAN or no_sort128)
+    ctx.close()
+
+
+def test_big_route(pkg, golden_dir):
+    """two frames of big_frames.npz (300 cones) and a lattice frame with more than 64 raw end configurations: planned by
+    sort_big_kernel_ranked, where a side can hold more candidates than a call stores"""
+    ctx = pkg._capi.Context(device=0)
+    _, off, cones, poses = sup.npz_batch(golden_dir, "big_frames", (0, 1))
+    got, _ = check_batch(pkg, ctx, oracle_lib, off, cones, poses)
+    assert (got[0]["status"] == 0).all() and (np.diff(off) > 255).all() and "sort_big_kernel_ranked" in stage_names(ctx)
+    _, off, cones, poses = sup.npz_batch(golden_dir, "lattice", (5,))
+    got, (multi, _) = check_batch(pkg, ctx, oracle_lib, off, cones, poses)
+    assert got[1].max() > 64 and multi == 2  # the count is never truncated
+    ctx.close()
+
+
+def test_wide_build(pkg, golden_dir):
+    g, off, cones, poses = sup.npz_batch(golden_dir, "params_wide_sort", range(8))
+    prm = dict(zip(g["param_names"].tolist(), g["param_values"].tolist()))
+    ctx = pkg._capi.Context(device=0, params=prm)
+    assert ctx.shapes is pkg._capi.WIDE
+    with oracle_lib_wide.params(prm):
+        got, _ = check_batch(pkg, ctx, oracle_lib_wide, off, cones, poses)
+    assert got[2].shape[-1] == 16
+    ctx.close()
+
+
+def test_every_ranked_kernel_ran():
+    """(after the tests above) each of the three ranked kernels really ran"""
+    assert {"sort_kernel_128_ranked", "sort_kernel_ranked", "sort_big_kernel_ranked"} <= RAN, RAN
+
+
+def test_without_unknown_cones(pkg, golden_dir):
+    """item 4: every stored index points at a cone of the caller's array that is not UNKNOWN, and the rows are the oracle's on
+    the filtered array, as coordinates"""
+    off, cones, poses = sup.retyped_unknown(golden_dir)
+    views = sup.filtered_views(off, cones)
+    prm = dict(use_unknown_cones=False)
+    ctx = pkg._capi.Context(device=0, params=prm)
+    with oracle_lib.params(dict(use_unknown_cones=0)):
+        got, _ = check_batch(pkg, ctx, oracle_lib, off, cones, poses, oracle_cones=views)
+        _res, counts, configs, _costs, _terms = got
+        stored = 0
+        for f in range(len(poses)):
+            xyt = cones[off[f] : off[f + 1]]
+            for s, t in enumerate(sup.SIDE_TYPES):
+                _c, ocfg, _oc, _fk = oracle_lib.side_configs(views[f][0], poses[f], t, 64)
+                for r in range(min(int(counts[f, s]), 64)):
+                    idx = configs[f, s, r][configs[f, s, r] >= 0]
+                    assert (xyt[idx, 2] != 0).all()
+                    assert np.array_equal(xyt[idx], views[f][0][ocfg[r][ocfg[r] >= 0]])
+                    stored += 1
+    assert stored >= 8
+    ctx.close()
+
+
+def test_refusals(pkg, golden_dir):
+    _, off, cones, poses = sup.npz_batch(golden_dir, "cfg2_color", range(4))
+    ctx = pkg._capi.Context(device=0)
+    for k in (0, 65):
+        with pytest.raises(pkg._capi.FsdpError):
+            ctx.sort_batch_ranked(off, cones, poses, top_k=k)
+    skid = pkg._capi.Context(device=0, mission=int(pkg.MissionTypes.skidpad))
+    with pytest.raises(pkg._capi.FsdpError):
+        skid.sort_batch_ranked(off, cones, poses)
+    skid.close()
+    t = ctx.submit(off, cones, poses)
+    with pytest.raises(pkg._capi.FsdpError):
+        ctx.sort_batch_ranked(off, cones, poses)
+    ctx.collect(t)
+    ctx.sort_batch_ranked(off, cones, poses)  # and afterwards it works
+    ctx.close()
+
+
+def test_sorting_cache_is_left_alone(pkg, golden_dir):
+    """after sort_cache_reset(n) a ranked call leaves the hit codes and the next cached call's results as they would have been"""
+    g = dict(np.load(golden_dir / "sort_cache_lockstep.npz"))
+    n = int(g["n_planners"])
+    steps = []
+    for s0 in range(0, 3 * n, n):
+        xs = [g["cones"][g["offsets"][k] : g["offsets"][k + 1]] for k in range(s0, s0 + n)]
+        off = np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int32)
+        steps.append((off, np.concatenate(xs), g["poses"][s0 : s0 + n]))
+    with_call, without = pkg._capi.Context(device=0), pkg._capi.Context(device=0)
+    for c in (with_call, without):
+        c.sort_cache_reset(n)
+        c.sort_batch(*steps[0])
+        c.sort_batch(*steps[1])
+    h = with_call.sort_cache_hits()
+    assert np.array_equal(h, without.sort_cache_hits())
+    plain = pkg._capi.Context(device=0)
+    ranked = with_call.sort_batch_ranked(*steps[2], top_k=4)
+    assert sup.same_records(ranked[0], plain.sort_batch(*steps[2]))  # planned as if the cache were off
+    assert np.array_equal(with_call.sort_cache_hits(), h)
+    a, b = with_call.sort_batch(*steps[2]), without.sort_batch(*steps[2])
+    assert sup.same_records(a, b) and np.array_equal(with_call.sort_cache_hits(), without.sort_cache_hits())
+    assert (with_call.sort_cache_hits() == 1).any()
+    for c in (with_call, without, plain):
+        c.close()
+
+
+def test_stage_class_and_margin(pkg, golden_dir):
+    """ConeSorting.ranked_configurations: the reference-shaped triple per side, trimmed to the stored rows"""
+    g = np.load(golden_dir / "sort_ranked.npz")
+    k = int(np.flatnonzero((g["source"] == "lattice") & (g["n_rows"].min(axis=1) > 1) & ~g["knn_tie"])[0])
+    xyt, pose = g["cones"][g["offsets"][k] : g["offsets"][k + 1]], g["poses"][k]
+    cs = pkg.ConeSorting(device=0)
+    cs.set_new_input(pkg.ConeSortingInput([xyt[xyt[:, 2] == t, :2] for t in range(5)], pose[:2], pose[2:]))
+    cs.run_cone_sorting()
+    sides = cs.ranked_configurations()
+    flat = pkg.planner.flatten_cones_by_type_array(cs.input.slam_cones)
+    for s, side in enumerate(sides):
+        n, at = int(g["n_rows"][k, s]), int(g["row_off"][k, s])
+        costs, configs, ind = side
+        assert costs.shape == (n,) and configs.shape == (n, 12) and ind.shape == (n, 7)
+        assert sup.close(costs, g["costs"][at : at + n], GPU_RTOL)
+        # (the capture's indices are the flattened array's, like these: same cones)
+        assert np.array_equal(flat[configs[0][configs[0] >= 0], :2], xyt[g["configs"][at][g["configs"][at] >= 0], :2])
+        m = pkg.decision_margin(costs)
+        assert m == (costs[1] - costs[0]) / max(abs(costs[0]), 1e-300)
+    assert cs.ranked_configurations(top_k=1)[0][0].shape == (1,)
