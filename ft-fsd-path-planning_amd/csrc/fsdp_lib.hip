@@ -441,34 +441,43 @@ static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
   return v;
 }
 
-// st: the batch's stage-in (src_off != NULL: the kernel brings it onto the device itself)
-static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& st) {
-  if (c->cache_call) {
-    const SortCacheView v = cache_view(c, q);
-    if (sort128(c, in))
-      hipLaunchKernelGGL(sort_kernel_128_cached, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones,
-                         in.d_poses, q.d_sort, q.d_big, c->d_params, st, v);
-    else
-      hipLaunchKernelGGL(sort_kernel_cached, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones,
-                         in.d_poses, q.d_sort, q.d_big, c->d_params, st, v);
-    return;
-  }
-  if (sort128(c, in))
-    hipLaunchKernelGGL(sort_kernel_128, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones,
-                       in.d_poses, q.d_sort, q.d_big, c->d_params, st);
+// Which instantiation of the three sorting kernels (sort_kernel_128 | sort_kernel, sort_big_kernel) a launch takes: the ranked one
+// for fsdp_sort_batch_ranked, else the cached one while a call advances the sorting cache (c->cache_call), else the plain one
+struct SortVariant {
+  const SortRankView* rank = nullptr;     // ranked: where the rows go ...
+  SortRankScratchBig* scratch = nullptr;  // ... and sort_big_kernel_ranked's block for the cost terms (SORT_BIG_BLOCKS of them)
+  const char* suffix(const fsdp_ctx* c) const { return rank ? "_ranked" : (c->cache_call ? "_cached" : ""); }
+};
+
+// Both launches append the name of the kernel they took to `names` (fsdp_stage_names).
+// st: the batch's stage-in (src_off != NULL: the kernel brings it onto the device itself; the ranked kernels have none)
+static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& st, std::string& names, const SortVariant& var = SortVariant()) {
+  const bool small = sort128(c, in);
+  const dim3 grid(in.n_frames), block(WAVE);
+  if (var.rank)
+    hipLaunchKernelGGL((small ? sort_kernel_128_ranked : sort_kernel_ranked), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
+                       in.d_poses, q.d_sort, q.d_big, c->d_params, *var.rank);
+  else if (c->cache_call)
+    hipLaunchKernelGGL((small ? sort_kernel_128_cached : sort_kernel_cached), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
+                       in.d_poses, q.d_sort, q.d_big, c->d_params, st, cache_view(c, q));
   else
-    hipLaunchKernelGGL(sort_kernel, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
+    hipLaunchKernelGGL((small ? sort_kernel_128 : sort_kernel), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
                        q.d_sort, q.d_big, c->d_params, st);
+  names += std::string(small ? "sort_kernel_128" : "sort_kernel") + var.suffix(c);
 }
-static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in) {
+static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in, std::string& names, const SortVariant& var = SortVariant()) {
   if (!q.d_sort_big) HIP_TRY(c, hipMalloc(&q.d_sort_big, sizeof(SortSharedBig) * SORT_BIG_BLOCKS));
-  if (c->cache_call) {
-    hipLaunchKernelGGL(sort_big_kernel_cached, dim3(SORT_BIG_BLOCKS), dim3(WAVE), 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort,
-                       q.d_big, q.d_sort_big, c->d_params, cache_view(c, q));
-    return 0;
-  }
-  hipLaunchKernelGGL(sort_big_kernel, dim3(SORT_BIG_BLOCKS), dim3(WAVE), 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big,
-                     q.d_sort_big, c->d_params);
+  const dim3 grid(SORT_BIG_BLOCKS), block(WAVE);
+  if (var.rank)
+    hipLaunchKernelGGL(sort_big_kernel_ranked, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
+                       c->d_params, *var.rank, var.scratch);
+  else if (c->cache_call)
+    hipLaunchKernelGGL(sort_big_kernel_cached, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
+                       c->d_params, cache_view(c, q));
+  else
+    hipLaunchKernelGGL(sort_big_kernel, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
+                       c->d_params);
+  names += std::string("sort_big_kernel") + var.suffix(c);
   return 0;
 }
 static void launch_match(fsdp_ctx* c, Work& q, const Inputs& in) {
@@ -684,7 +693,7 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io
   if (filtered)
     if (int rc = launch_filter(c, q, in_, &fin)) return rc;
   const Inputs& in = filtered ? fin : in_;
-  std::string names = std::string(sort128(c, in) ? "sort_kernel_128" : "sort_kernel") + (c->cache_call ? "_cached," : ",");
+  std::string names;
   if (c->poison) {
     // (tests) whatever a previous pass, another batch or the allocator left in the slot's buffers is gone: 0xFF bytes = NaNs, -1 indices
     const size_t m = (size_t)in.n_frames;
@@ -698,11 +707,12 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io
     (void)hipMemsetAsync(q.d_retry + 1, 0xff, sizeof(int) * m, q.stream);
   }
   mark(q, t);
-  launch_sort(c, q, in, io.stage);
+  launch_sort(c, q, in, io.stage, names);
+  names += ',';
   if (with_big) {
     mark(q, t);
-    if (int rc = launch_sort_big(c, q, in)) return rc;
-    names += c->cache_call ? "sort_big_kernel_cached," : "sort_big_kernel,";
+    if (int rc = launch_sort_big(c, q, in, names)) return rc;
+    names += ',';
   }
   mark(q, t);
   launch_match(c, q, in);
@@ -2027,6 +2037,13 @@ struct RankCall {
   }
 };
 
+// indices of a frame planned without its UNKNOWN cones back into the caller's cone list (what assemble_kernel does for a full
+// pass); map: the frame's part of launch_filter's map
+static void map_back(int32_t* idx, size_t n, const int32_t* map) {
+  for (size_t k = 0; k < n; k++)
+    if (idx[k] >= 0) idx[k] = map[idx[k]];
+}
+
 // fsdp_sort_batch, and with rk fsdp_sort_batch_ranked (the ranked kernels instead of the plain ones, never the sorting cache)
 static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
                            fsdp_frame_result* results, RankCall* rk) {
@@ -2066,6 +2083,8 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
     if (int rc = launch_filter(c, q, q.in, &fin)) return rc;
   const Inputs& in = filtered ? fin : q.in;
   const size_t rows = rk ? (size_t)n_frames * 2 * (size_t)rk->top_k : 0;
+  SortRankView v;
+  SortVariant var;
   if (rk) {
     HIP_TRY(c, hipMalloc(&rk->d_counts, sizeof(int32_t) * 2 * (size_t)n_frames));
     HIP_TRY(c, hipMalloc(&rk->d_configs, sizeof(int32_t) * rows * MAX_LEN));
@@ -2081,27 +2100,19 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
       HIP_TRY(c, hipMemsetAsync(q.d_sort, 0xff, sizeof(SortOut) * (size_t)n_frames, q.stream));
       HIP_TRY(c, hipMemsetAsync(rk->d_scratch, 0xff, sizeof(SortRankScratchBig) * SORT_BIG_BLOCKS, q.stream));
     }
-    SortRankView v;
     v.top_k = rk->top_k;
     v.counts = rk->d_counts;
     v.configs = rk->d_configs;
     v.costs = rk->d_costs;
     v.terms = rk->d_terms;
-    const bool small = sort128(c, in);
-    if (small)
-      hipLaunchKernelGGL(sort_kernel_128_ranked, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
-                         q.d_sort, q.d_big, c->d_params, v);
-    else
-      hipLaunchKernelGGL(sort_kernel_ranked, dim3(in.n_frames), dim3(WAVE), 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses, q.d_sort,
-                         q.d_big, c->d_params, v);
-    if (!q.d_sort_big) HIP_TRY(c, hipMalloc(&q.d_sort_big, sizeof(SortSharedBig) * SORT_BIG_BLOCKS));
-    hipLaunchKernelGGL(sort_big_kernel_ranked, dim3(SORT_BIG_BLOCKS), dim3(WAVE), 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big,
-                       q.d_sort_big, c->d_params, v, rk->d_scratch);
-    c->stage_names = std::string(small ? "sort_kernel_128_ranked" : "sort_kernel_ranked") + ",sort_big_kernel_ranked";
-  } else {
-    launch_sort(c, q, in, StageIn());
-    if (int rc = launch_sort_big(c, q, in)) return rc;
+    var.rank = &v;
+    var.scratch = rk->d_scratch;
   }
+  std::string names;
+  launch_sort(c, q, in, StageIn(), names, var);
+  names += ',';
+  if (int rc = launch_sort_big(c, q, in, names, var)) return rc;
+  if (rk) c->stage_names = names;  // (fsdp_sort_batch leaves the names of the most recent pass in place)
   HIP_TRY(c, hipMemsetAsync(q.d_big, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
   HIP_TRY(c, grow_pinned(c->h_sort, c->cap_sort, (size_t)n_frames, hipHostMallocDefault, 64));
   HIP_TRY(c, hipMemcpyAsync(c->h_sort, q.d_sort, sizeof(SortOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
@@ -2125,20 +2136,14 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
     memset(&results[i], 0, sizeof(fsdp_frame_result));
     assemble(&c->h_sort[i], nullptr, nullptr, &results[i]);
     if (filtered) {
-      auto back = [&](int32_t& v) {
-        if (v >= 0) v = map[(size_t)moff[i] + v];
-      };
-      for (int k = 0; k < MAX_LEN; k++) {
-        back(results[i].left_idx[k]);
-        back(results[i].right_idx[k]);
-      }
-      for (int k = 0; k < 2; k++) {
-        back(results[i].first_k_left[k]);
-        back(results[i].first_k_right[k]);
-      }
+      const int32_t* fmap = map.data() + moff[i];
+      map_back(results[i].left_idx, MAX_LEN, fmap);
+      map_back(results[i].right_idx, MAX_LEN, fmap);
+      map_back(results[i].first_k_left, 2, fmap);
+      map_back(results[i].first_k_right, 2, fmap);
       if (rk) {
-        int32_t* rows_i = rk->configs + (size_t)i * 2 * (size_t)rk->top_k * MAX_LEN;
-        for (size_t k = 0; k < 2 * (size_t)rk->top_k * MAX_LEN; k++) back(rows_i[k]);
+        const size_t per_frame = 2 * (size_t)rk->top_k * MAX_LEN;
+        map_back(rk->configs + (size_t)i * per_frame, per_frame, fmap);
       }
     }
   }
@@ -2318,7 +2323,7 @@ int fsdp_profile_path(fsdp_ctx* c, long long* out32_per_frame) {
   Work& q = c->slot[0];
   std::string names;
   if (c->profile_sort)
-    launch_sort(c, q, c->res, StageIn());
+    launch_sort(c, q, c->res, StageIn(), names);
   else
     launch_path(c, q, c->res, nullptr, names, frames_in_flight(c, c->res.n_frames, false));
   HIP_TRY(c, hipMemsetAsync(q.d_big, 0, sizeof(int), q.stream));

@@ -1,8 +1,7 @@
 // TEST INFRASTRUCTURE — builds the product's kernel *sources* for the host SIMT emulator
 // (tests/emu/hip_emu.h).  Never loaded by the package.
-#include "hip_emu.h"
+#include "emu_shared.h"
 
-#include "../../ft-fsd-path-planning_amd/csrc/sort_kernel.h"
 #include "../../ft-fsd-path-planning_amd/csrc/match_kernel.h"
 #include "../../ft-fsd-path-planning_amd/csrc/path_kernel.h"
 #include "../../ft-fsd-path-planning_amd/csrc/skidpad_kernel.h"
@@ -20,16 +19,38 @@ struct AlignedArena {
 };
 
 // configuration constants handed to the kernels (emu_set_params; defaults = fsd_path_planning/config.py)
-static fsdp::Params g_prm = {5, 12, 6.5, 6.0, 40 * FSDP_DEG, 65 * FSDP_DEG, 3.0, 5.0, 50 * FSDP_DEG, 0.2, 0.1, 5.0, 20.0, 3, 40, 0, 1};
+fsdp::Params g_prm = {5, 12, 6.5, 6.0, 40 * FSDP_DEG, 65 * FSDP_DEG, 3.0, 5.0, 50 * FSDP_DEG, 0.2, 0.1, 5.0, 20.0, 3, 40, 0, 1};
 static double g_default_path[fsdp::PATH_POINTS * 4];
 static const double* g_prev_paths = nullptr;
 static const double* g_gpath = nullptr;
 static int g_n_gpath = 0;
 static std::once_flag g_once;
 static int g_last_retries = 0;
-static int g_last_big = 0;
+int g_last_big = 0;
 static bool g_no_sort128 = false;  // emu_set_no_sort128: the 255-cone state also for small frames (the library's option "no_sort128")
 static std::vector<double> g_refit;  // FitRec per frame of the last three-kernel path launch
+bool emu_sort128(int n_frames, const int32_t* offsets) {
+  int max_cones = 0;
+  for (int f = 0; f < n_frames; f++) max_cones = std::max(max_cones, (int)(offsets[f + 1] - offsets[f]));
+  return max_cones <= fsdp::SortShared128::MAX_N && !g_no_sort128;
+}
+std::vector<int32_t> g_f_off;
+static std::vector<int32_t> g_f_map;
+std::vector<double> g_f_cones;
+void emu_filter(int n_frames, const int32_t* offsets, const double* cones) {
+  std::vector<int32_t> cnt((size_t)n_frames + 1, 0);
+  g_f_off.assign((size_t)n_frames + 1, 0);
+  const size_t total = (size_t)offsets[n_frames];
+  g_f_cones.assign(3 * total + 3, 0.0);
+  g_f_map.assign(total + 1, 0);
+  emu::launch((unsigned)n_frames, 64, [&]() { fsdp::filter_count_kernel(n_frames, offsets, cones, cnt.data()); });
+  emu::launch(1, 64, [&]() { fsdp::filter_scan_kernel(n_frames, cnt.data(), g_f_off.data()); });
+  emu::launch((unsigned)n_frames, 64, [&]() { fsdp::filter_scatter_kernel(n_frames, offsets, cones, g_f_off.data(), g_f_cones.data(), g_f_map.data()); });
+}
+void emu_map_back(int f, int32_t* idx, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if (idx[k] >= 0) idx[k] = g_f_map[(size_t)g_f_off[f] + idx[k]];
+}
 static void build_default() {
   double chord[fsdp::CHORD_POINTS][2];
   fsdp::default_chord_points(chord);
@@ -141,10 +162,7 @@ int emu_sizeof_path_out() { return (int)sizeof(fsdp::PathOut); }
 
 static void emu_sort_plain(int n_frames, const int32_t* offsets, const double* cones, const double* poses, fsdp::SortOut* out) {
   std::vector<int> big((size_t)n_frames + 1, 0);
-  // the host library's choice (fsdp_lib.hip launch_sort): the 128-cone state when no frame of the batch holds more
-  int max_cones = 0;
-  for (int f = 0; f < n_frames; f++) max_cones = std::max(max_cones, (int)(offsets[f + 1] - offsets[f]));
-  if (max_cones <= fsdp::SortShared128::MAX_N && !g_no_sort128)
+  if (emu_sort128(n_frames, offsets))
     emu::launch((unsigned)n_frames, 64, [&]() { fsdp::sort_kernel_128(n_frames, offsets, cones, poses, out, big.data(), &g_prm); });
   else
     emu::launch((unsigned)n_frames, 64, [&]() { fsdp::sort_kernel(n_frames, offsets, cones, poses, out, big.data(), &g_prm); });
@@ -153,20 +171,6 @@ static void emu_sort_plain(int n_frames, const int32_t* offsets, const double* c
     std::vector<fsdp::SortSharedBig> state(2);
     emu::launch(2, 64, [&]() { fsdp::sort_big_kernel(offsets, cones, poses, out, big.data(), state.data(), &g_prm); });
   }
-}
-// use_unknown_cones = False: the filter kernels in front (fsdp_lib.hip launch_filter); f_off / f_cones describe the batch
-// the other kernels plan, f_map the way back for indices
-static std::vector<int32_t> g_f_off, g_f_map;
-static std::vector<double> g_f_cones;
-static void emu_filter(int n_frames, const int32_t* offsets, const double* cones) {
-  std::vector<int32_t> cnt((size_t)n_frames + 1, 0);
-  g_f_off.assign((size_t)n_frames + 1, 0);
-  const size_t total = (size_t)offsets[n_frames];
-  g_f_cones.assign(3 * total + 3, 0.0);
-  g_f_map.assign(total + 1, 0);
-  emu::launch((unsigned)n_frames, 64, [&]() { fsdp::filter_count_kernel(n_frames, offsets, cones, cnt.data()); });
-  emu::launch(1, 64, [&]() { fsdp::filter_scan_kernel(n_frames, cnt.data(), g_f_off.data()); });
-  emu::launch((unsigned)n_frames, 64, [&]() { fsdp::filter_scatter_kernel(n_frames, offsets, cones, g_f_off.data(), g_f_cones.data(), g_f_map.data()); });
 }
 void emu_sort(int n_frames, const int32_t* offsets, const double* cones, const double* poses, fsdp::SortOut* out) {
   if (g_prm.use_unknown_cones) {
@@ -180,17 +184,10 @@ void emu_sort(int n_frames, const int32_t* offsets, const double* cones, const d
 void emu_sort_remap(int n_frames, fsdp::SortOut* out) {
   if (g_prm.use_unknown_cones) return;
   for (int f = 0; f < n_frames; f++) {
-    auto back = [&](int32_t& v) {
-      if (v >= 0) v = g_f_map[(size_t)g_f_off[f] + v];
-    };
-    for (int k = 0; k < fsdp::MAX_LEN; k++) {
-      back(out[f].left_idx[k]);
-      back(out[f].right_idx[k]);
-    }
-    for (int k = 0; k < 2; k++) {
-      back(out[f].first_k_left[k]);
-      back(out[f].first_k_right[k]);
-    }
+    emu_map_back(f, out[f].left_idx, fsdp::MAX_LEN);
+    emu_map_back(f, out[f].right_idx, fsdp::MAX_LEN);
+    emu_map_back(f, out[f].first_k_left, 2);
+    emu_map_back(f, out[f].first_k_right, 2);
   }
 }
 void emu_match(int n_frames, const int32_t* offsets, const double* cones, const double* poses, const fsdp::SortOut* sorted,

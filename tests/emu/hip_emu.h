@@ -240,7 +240,10 @@ inline unsigned long long ballot(int pred) { return gballot(pred, WAVE); }
 
 }  // namespace emu
 
-#define __global__
+// a kernel is an ordinary function here, and two translation units of a library include its header: weak, so that the linker
+// keeps one.  (Not `inline`: the __shared__ block of an inline function is a process-wide unique symbol, which the standard and
+// the wide library would then share although their shapes differ.)
+#define __global__ __attribute__((weak))
 #define __device__
 #define __host__
 #define __forceinline__ inline

@@ -67,6 +67,36 @@ def sort(offsets, cones, poses):
     return out
 
 
+RANK_MAX, COST_TERMS = 64, 7
+
+
+def last_kernels():
+    """bit 0 / 1 / 2: sort_kernel_128_ranked / sort_kernel_ranked / sort_big_kernel_ranked ran in the last sort_ranked call"""
+    return int(lib().emu_ranked_last_kernels())
+
+
+def sort_ranked(offsets, cones, poses, top_k=8, terms=True):
+    """The ranked sorting kernels, wrapped like the library's fsdp_sort_batch_ranked (tests/emu/emu_ranked.cpp) -> (sort records,
+    counts (n,2), configs (n,2,top_k,MAX_LEN), costs (n,2,top_k), terms (n,2,top_k,7) or None); raises ValueError for a top_k
+    the kernels refuse"""
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    cones = np.ascontiguousarray(cones, np.float64)
+    poses = np.ascontiguousarray(poses, np.float64)
+    n = len(offsets) - 1
+    k = max(1, min(int(top_k), RANK_MAX))
+    out = np.zeros(n, SORT_DTYPE)
+    counts = np.zeros((n, 2), np.int32)
+    configs = np.zeros((n, 2, k, MAX_LEN), np.int32)
+    costs = np.zeros((n, 2, k))
+    tm = np.zeros((n, 2, k, COST_TERMS)) if terms else None
+    rc = lib().emu_sort_ranked(ctypes.c_int(n), _p(offsets, ctypes.c_int32), _p(cones), _p(poses), ctypes.c_void_p(out.ctypes.data),
+                               ctypes.c_int(int(top_k)), _p(counts, ctypes.c_int32), _p(configs, ctypes.c_int32), _p(costs),
+                               _p(tm) if terms else None)
+    if rc != 0:
+        raise ValueError(f"top_k = {top_k} refused")
+    return out, counts, configs, costs, tm
+
+
 def match(offsets, cones, poses, sorted_out):
     offsets = np.ascontiguousarray(offsets, np.int32)
     cones = np.ascontiguousarray(cones, np.float64)

@@ -1,5 +1,5 @@
 """Ranked sorting candidates (include/fsdp.h fsdp_sort_batch_ranked) without a GPU: the ranked kernel sources under the host
-SIMT emulator (tests/emu_ranked/) against the oracle's side_configs and the reference capture tests/golden/sort_ranked.npz,
+SIMT emulator (tests/emu/emu_ranked.cpp) against the oracle's side_configs and the reference capture tests/golden/sort_ranked.npz,
 bit for bit (same libm: the equality tests/test_kernel_logic_emulated.py applies to best_cost_*); the fixture; the exported
 symbol and the host-side helpers."""
 import ctypes
@@ -11,7 +11,6 @@ import pytest
 
 import emu_lib
 import emu_lib_wide
-import emu_ranked_lib
 import oracle_lib
 import oracle_lib_wide
 import sort_ranked_support as sup
@@ -21,8 +20,8 @@ EMU_RTOL = 0.0  # parity.assert_intermediates_equal's default: bit-equal costs u
 GPU_RTOL = 1e-12  # tests/test_gpu_parity.py:82
 
 
-def emu_run(e):
-    return lambda off, cones, poses, top_k=64, terms=True: e.sort_ranked(off, cones, poses, top_k, terms)
+def emu_run(lib):
+    return lambda off, cones, poses, top_k=64, terms=True: lib.sort_ranked(off, cones, poses, top_k, terms)
 
 
 def emu_plain(lib):
@@ -59,9 +58,8 @@ def test_fixture_holds_what_it_was_made_for(fixture):
 def test_emulated_ranking_equals_oracle_and_reference_terms(fixture, no_sort128):
     """items 1-3 on the frames of sort_ranked.npz; no_sort128: the 255-cone state for every frame"""
     g, batches = fixture
-    e = emu_ranked_lib.emu()
-    e.set_no_sort128(no_sort128)
-    emu_lib.lib().emu_set_no_sort128(ctypes.c_int(int(no_sort128)))
+    e = emu_lib
+    e.lib().emu_set_no_sort128(ctypes.c_int(int(no_sort128)))
     kernels, multi, ties, rows, left_out = 0, 0, 0, 0, 0
     try:
         for frames, off, cones, poses in batches:
@@ -75,10 +73,9 @@ def test_emulated_ranking_equals_oracle_and_reference_terms(fixture, no_sort128)
             r, o = sup.check_terms_against_fixture(g, frames, got, EMU_RTOL, "_libm")
             rows, left_out = rows + r, left_out + o
             assert sup.check_terms_against_fixture(g, frames, got, GPU_RTOL) == (r, o)
-            sup.check_call_invariants(emu_run(e), emu_plain(emu_lib), off, cones, poses, got)
+            sup.check_call_invariants(emu_run(e), emu_plain(e), off, cones, poses, got)
     finally:
-        e.set_no_sort128(False)
-        emu_lib.lib().emu_set_no_sort128(ctypes.c_int(0))
+        e.lib().emu_set_no_sort128(ctypes.c_int(0))
     assert multi >= 8 and rows >= 300 and left_out <= 2  # (two sides of the hairpin scenarios' colourless variants: knn_tie)
     assert kernels & 2 and bool(kernels & 1) != no_sort128  # sort_kernel_ranked ran; sort_kernel_128_ranked unless switched off
 
@@ -86,37 +83,33 @@ def test_emulated_ranking_equals_oracle_and_reference_terms(fixture, no_sort128)
 def test_emulated_big_route(golden_dir):
     """two frames of big_frames.npz (300 cones) and a lattice frame with more than 64 raw end configurations:
     sort_big_kernel_ranked, where a side can hold more candidates than the 64 rows a call stores"""
-    e = emu_ranked_lib.emu()
+    e = emu_lib
     _, off, cones, poses = sup.npz_batch(golden_dir, "big_frames", (0, 1))
     got = e.sort_ranked(off, cones, poses, 64, True)
-    assert e.last_kernels() & 4 and e.last_big() == 2
+    assert e.last_kernels() & 4 and e.lib().emu_last_big() == 2
     with oracle_lib.math_mode(1):
         sup.check_against_oracle(oracle_lib, off, cones, poses, got, EMU_RTOL)
-    sup.check_call_invariants(emu_run(e), emu_plain(emu_lib), off, cones, poses, got)
+    sup.check_call_invariants(emu_run(e), emu_plain(e), off, cones, poses, got)
     _, off, cones, poses = sup.npz_batch(golden_dir, "lattice", (5,))
     got = e.sort_ranked(off, cones, poses, 64, True)
-    assert e.last_big() == 1 and got[1].max() > 64  # the count is never truncated
+    assert e.lib().emu_last_big() == 1 and got[1].max() > 64  # the count is never truncated
     with oracle_lib.math_mode(1):
         multi, _ = sup.check_against_oracle(oracle_lib, off, cones, poses, got, EMU_RTOL)
     assert multi == 2
-    sup.check_call_invariants(emu_run(e), emu_plain(emu_lib), off, cones, poses, got)
+    sup.check_call_invariants(emu_run(e), emu_plain(e), off, cones, poses, got)
 
 
 def test_emulated_wide_build(golden_dir):
     """the first 8 frames of params_wide_sort.npz on the wide shapes against the oracle's wide build"""
     g, off, cones, poses = sup.npz_batch(golden_dir, "params_wide_sort", range(8))
     prm = dict(zip(g["param_names"].tolist(), g["param_values"].tolist()))
-    e = emu_ranked_lib.emu(wide=True)
-    e.set_params(prm)
-    try:
+    e = emu_lib_wide
+    with e.params(prm):
         got = e.sort_ranked(off, cones, poses, 64, True)
         assert got[2].shape[-1] == 16
         with oracle_lib_wide.params(prm), oracle_lib_wide.math_mode(1):
             sup.check_against_oracle(oracle_lib_wide, off, cones, poses, got, EMU_RTOL)
-        with emu_lib_wide.params(prm):
-            sup.check_call_invariants(emu_run(e), emu_plain(emu_lib_wide), off, cones, poses, got)
-    finally:
-        e.set_params(None)
+        sup.check_call_invariants(emu_run(e), emu_plain(e), off, cones, poses, got)
 
 
 def test_emulated_without_unknown_cones(golden_dir):
@@ -125,17 +118,13 @@ def test_emulated_without_unknown_cones(golden_dir):
     off, cones, poses = sup.retyped_unknown(golden_dir)
     views = sup.filtered_views(off, cones)
     prm = dict(use_unknown_cones=0)
-    e = emu_ranked_lib.emu()
-    e.set_params(prm)
-    try:
+    e = emu_lib
+    with e.params(prm):
         got = e.sort_ranked(off, cones, poses, 64, True)
         with oracle_lib.params(prm), oracle_lib.math_mode(1):
             sup.check_against_oracle(oracle_lib, off, cones, poses, got, EMU_RTOL, oracle_cones=views)
             check_filtered_coordinates(oracle_lib, off, cones, poses, got, views)
-        with emu_lib.params(prm):
-            sup.check_call_invariants(emu_run(e), emu_plain(emu_lib), off, cones, poses, got)
-    finally:
-        e.set_params(None)
+        sup.check_call_invariants(emu_run(e), emu_plain(e), off, cones, poses, got)
 
 
 def check_filtered_coordinates(oracle, off, cones, poses, got, views):
@@ -157,7 +146,7 @@ def test_emulated_refuses_top_k_outside_the_range(golden_dir):
     _, off, cones, poses = sup.npz_batch(golden_dir, "cfg2_color", (0,))
     for k in (0, 65, -1):
         with pytest.raises(ValueError):
-            emu_ranked_lib.emu().sort_ranked(off, cones, poses, k)
+            emu_lib.sort_ranked(off, cones, poses, k)
 
 
 def test_decision_margin_and_symbols():

@@ -24,10 +24,57 @@ def pkg():
     return importlib.import_module("ft-fsd-path-planning_amd")
 
 
-def stage_names(ctx):
+def stage_string(ctx):
     buf = ctypes.create_string_buffer(512)
     assert ctx._lib.fsdp_stage_names(ctx._h, buf, 512) == 0
-    return buf.value.decode().split(",")
+    return buf.value.decode()
+
+
+def stage_names(ctx):
+    return stage_string(ctx).split(",")
+
+
+def sort_entries(ctx):
+    """fsdp_stage_names up to the matching kernel's entry: the sorting kernels of a pass, commas included"""
+    s = stage_string(ctx)
+    return s[: s.index("match_kernel")]
+
+
+def test_stage_names_of_the_nine_sorting_kernels(pkg):
+    """fsdp_stage_names character for character for every way a sorting kernel is chosen: plain, cached and ranked, the 128- and
+    the 255-cone state, with and without the big route.  The names depend only on the largest frame and the options: two 8-cone
+    frames, and a batch in which one frame holds 130 cones."""
+    small = pkg.synth.make_replay_batch(2, 4, 0.15, seed=1, color=True)
+    one = pkg.synth.make_replay_batch(1, 65, 0.15, seed=33, color=True)
+    assert np.diff(small[0]).tolist() == [8, 8] and np.diff(one[0]).tolist() == [130]
+    large = (np.array([0, 130, 138], np.int32), np.concatenate([one[1], small[1][:8]]), np.concatenate([one[2], small[2][:1]]))
+    ctx = pkg._capi.Context(device=0)
+    no128 = pkg._capi.Context(device=0, options={"no_sort128": 1})
+    routed = pkg._capi.Context(device=0, options={"always_route": 1})
+    # fsdp_sort_batch_ranked: the whole string
+    ctx.sort_batch_ranked(*small)
+    assert stage_string(ctx) == "sort_kernel_128_ranked,sort_big_kernel_ranked"
+    no128.sort_batch_ranked(*small)
+    assert stage_string(no128) == "sort_kernel_ranked,sort_big_kernel_ranked"
+    ctx.sort_batch_ranked(*large)
+    assert stage_string(ctx) == "sort_kernel_ranked,sort_big_kernel_ranked"
+    # a pass over the resident batch: the entries in front of the matching kernel's
+    for c, want in ((ctx, "sort_kernel_128,"), (routed, "sort_kernel_128,sort_big_kernel,"), (no128, "sort_kernel,")):
+        c.upload(*small)
+        c.time_runs(1)
+        assert sort_entries(c) == want
+    ctx.upload(*large)
+    ctx.time_runs(1)
+    assert sort_entries(ctx) == "sort_kernel,"
+    # the sorting cache: fsdp_plan_batch_sequential's pass reports the cached kernels
+    for c, want in ((ctx, "sort_kernel_128_cached,"), (routed, "sort_kernel_128_cached,sort_big_kernel_cached,"), (no128, "sort_kernel_cached,")):
+        c.sort_cache_reset(2)
+        c.plan_batch_sequential(*small, None)
+        assert sort_entries(c) == want
+    ctx.plan_batch_sequential(*large, None)
+    assert sort_entries(ctx) == "sort_kernel_cached,"
+    for c in (ctx, no128, routed):
+        c.close()
 
 
 def gpu_run(ctx):
