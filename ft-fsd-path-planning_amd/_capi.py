@@ -195,6 +195,9 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     lib.fsdp_plan_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fsdp_plan_batch_sequential.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fsdp_plan_batch_compact.argtypes = lib.fsdp_plan_batch_sequential.argtypes
+    lib.fsdp_plan_sequence.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+    lib.fsdp_plan_sequence_compact.argtypes = lib.fsdp_plan_sequence.argtypes
     lib.fsdp_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_longlong]
     lib.fsdp_pcie_probe.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                     ctypes.POINTER(ctypes.c_double)]
@@ -229,7 +232,7 @@ EXPORTED_SYMBOLS = [
     "fsdp_host_alloc", "fsdp_host_free", "fsdp_host_register", "fsdp_host_unregister", "fsdp_host_is_pinned", "fsdp_submit", "fsdp_collect", "fsdp_ticket_done",
     "fsdp_submit_compact", "fsdp_plan_batch_compact", "fsdp_set_option", "fsdp_pcie_probe",
     "fsdp_skidpad_submit", "fsdp_route_stats", "fsdp_ticket_capacity", "fsdp_selftest_det3", "fsdp_debug_arena", "fsdp_selftest_absminmax", "fsdp_selftest_libm", "fsdp_selftest_givens",
-    "fsdp_sort_cache_reset", "fsdp_sort_cache_hits", "fsdp_sort_batch_ranked",
+    "fsdp_sort_cache_reset", "fsdp_sort_cache_hits", "fsdp_sort_batch_ranked", "fsdp_plan_sequence", "fsdp_plan_sequence_compact",
 ]
 RANK_MAX, COST_TERMS = 64, 7  # include/fsdp.h FSDP_RANK_MAX, FSDP_COST_TERMS
 COST_TERM_NAMES = ("angle", "residual_distance", "number_of_cones", "initial_direction", "change_of_direction", "cones_on_either",
@@ -466,6 +469,42 @@ class Context:
         """plan_batch with a per-frame previous path (n_frames,40,4): the stateful fallbacks of the reference.  With the sorting
         cache on (sort_cache_reset) frame i is planner i, and prev_paths may be None (fresh path-stage history)."""
         return self.plan_batch(offsets, cones, poses, prev_paths=prev_paths, _sequential=self.n_cache > 0)
+
+    def plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False):
+        """fsdp_plan_sequence: n_planners planners x T consecutive steps in one call, frame = step * n_planners + planner (T =
+        frames / n_planners) — the bytes of T plan_batch_sequential calls whose prev_paths rows are the planners' most recent
+        successful paths.  initial_prev: (n_planners, <= path_points, 4) or None, a row starting with NaN = none (the fresh
+        planner's initial path).  -> (results, final_prev (n_planners, path_points, 4) with NaN rows for planners that have no
+        path yet, n_replanned = frames planned a second time on the device)."""
+        offsets, cones, poses, n = self._prep_any_base(cone_offsets, cones_xyt, poses)
+        n_planners = int(n_planners)
+        if n_planners < 1 or n < 1 or n % n_planners:
+            raise ValueError(f"plan_sequence: {n} frames are not a whole number (>= 1) of steps of {n_planners} planners")
+        init = None
+        if initial_prev is not None:
+            init = self.pad_paths(initial_prev)
+            assert len(init) == n_planners
+        out = np.zeros(n, dtype=self.compact_dtype if compact else self.result_dtype)
+        final = np.zeros((n_planners, self.shapes.path_points, 4))
+        again = ctypes.c_longlong(0)
+        fn = self._lib.fsdp_plan_sequence_compact if compact else self._lib.fsdp_plan_sequence
+        self._check(fn(self._h, n_planners, n // n_planners, offsets.ctypes.data, cones.ctypes.data if len(cones) else None, poses.ctypes.data,
+                       None if init is None else init.ctypes.data, out.ctypes.data, final.ctypes.data, ctypes.byref(again)), "fsdp_plan_sequence")
+        self.n_frames = n
+        return out, final, int(again.value)
+
+    @staticmethod
+    def _prep_any_base(offsets, cones, poses):
+        """_prep for the entry points that document cone_offsets[0] >= 0 (rows [offsets[0], offsets[-1]) of cones)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        cones = np.ascontiguousarray(cones, dtype=np.float64).reshape(-1, 3)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
+        n = len(offsets) - 1
+        if n < 0 or len(poses) != n or (n > 0 and (int(offsets[0]) < 0 or int(offsets[-1]) > len(cones))):
+            raise ValueError("inconsistent batch: offsets / cones / poses")
+        if n > 0 and np.any(np.diff(offsets) < 0):
+            raise ValueError("cone_offsets must be non-decreasing")
+        return offsets, cones, poses, n
 
     def sort_batch(self, offsets, cones, poses) -> np.ndarray:
         offsets, cones, poses, n = self._prep(offsets, cones, poses)

@@ -50,6 +50,7 @@ constexpr int ST_OVERFLOW_CONES = 201;
 constexpr int ST_OVERFLOW_ENDS = 202;
 constexpr int ST_OVERFLOW_PATH = 203;
 constexpr int ST_OVERFLOW_KNOTS = 204;
+constexpr int FB_READ_PREVIOUS = 1 | 2 | 4 | 8;  // path_fallback bits whose branch reads previous_paths[-1] (16, 32: how the path was extended)
 constexpr int ST_RETRY = 299;  // internal: the fast kernels hand the frame to the exact one-frame-per-wavefront kernel (never leaves the library)
 
 // The reference's configuration constants (fsd_path_planning/config.py:33-41,48,55-59,124-129), one device copy per

@@ -27,7 +27,8 @@
 #include "assemble_kernel.h"
 #include "filter_kernel.h"
 #include "fsdp_comm.h"
-#include "sort_rank_kernels.h"  // (last: the kernels in front of it keep their order in the code object)
+#include "sort_rank_kernels.h"  // (behind the pass kernels: the kernels in front of it keep their order in the code object)
+#include "sequence_launch.h"    // (the chain kernels of fsdp_plan_sequence are a translation unit of their own: sequence_lib.hip)
 
 using namespace fsdp;
 
@@ -96,6 +97,11 @@ struct Work {
   bool skid_attempted = true;             // ... which ran for that step (not once every planner is relocalized)
   SortSharedBig* d_sort_big = nullptr;    // frame states of sort_big_kernel, allocated when the route is first needed
   int cache_base = 0;                     // sorting cache: planner of the slot's frame 0 (a chunk of a blocking call)
+  // fsdp_plan_sequence (sequence_kernel.h): the run-head list of a sequence pass, the planners' initial and final previous paths
+  int* d_seq = nullptr;                   // [0] heads, [1] frames planned again, then (frame, predecessor) per head
+  double* d_seq_init = nullptr;           // (planners, 40, 4)
+  double* d_seq_final = nullptr;
+  size_t seq_cap_frames = 0, seq_cap_planners = 0;
   int cap_frames = 0;
   // use_unknown_cones = False (filter_kernel.h): the batch without its UNKNOWN cones, and the way back for the indices
   int32_t* f_cnt = nullptr;
@@ -239,6 +245,13 @@ struct fsdp_ctx {
   int8_t* d_cache_hits = nullptr;
   std::vector<int8_t> cache_hits;             // codes of the most recent call
   bool cache_call = false;                    // the call in progress advances the cached planners
+  // fsdp_plan_sequence: set for the duration of the call — its pass (and the rerun of a pass that lacked a route) resolves the
+  // planners' previous-path chains between the path stage and the assembly
+  struct Sequence {
+    int n_planners = 0, n_steps = 0;
+    bool with_init = false;  // the slot's d_seq_init holds the caller's initial_prev
+  };
+  const Sequence* sequence = nullptr;
 };
 // (an empty route launch costs a stream ~1 % of a pass; a pass repeated because the kernel was missing costs a whole pass and
 // stalls the caller's collect: once needed, a route stays for a long time)
@@ -339,6 +352,9 @@ static void free_work(Work& w) {
   (void)hipFree(w.d_skid_info);
   (void)hipFree(w.d_skid_status);
   (void)hipFree(w.d_sort_big);
+  (void)hipFree(w.d_seq);
+  (void)hipFree(w.d_seq_init);
+  (void)hipFree(w.d_seq_final);
   (void)hipFree(w.f_cnt);
   (void)hipFree(w.f_off);
   (void)hipFree(w.f_cones);
@@ -621,6 +637,8 @@ static void launch_path_retry(fsdp_ctx* c, Work& q, const Inputs& in, bool sized
                      c->n_gpath, q.d_arena, q.d_path, q.d_retry, c->d_params);
 }
 // What a pass writes where, and where its sorting kernel finds the batch
+struct PassIO;
+static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const PassIO& io);
 struct PassIO {
   fsdp_frame_result* host = nullptr;  // NULL: results into the slot's result block; else the device view of a page-locked host buffer
                                       // that assemble_kernel writes straight over PCIe (a ticket: no copy command at all)
@@ -653,6 +671,28 @@ static void launch_assemble(fsdp_ctx* c, Work& q, int n, const PassIO& io, bool 
                      skid ? (const MatchOut*)nullptr : q.d_match, q.d_path, io.host ? io.host : q.d_result, q.d_big, q.d_retry, q.d_trailer + io.trailer,
                      q.seq, (const int32_t*)(io.info ? q.d_skid_info : nullptr), (int32_t*)io.info, io.info ? (int)(sizeof(SkidInfo) / 4) * n : 0,
                      remap, remap_off);
+}
+
+// The chain kernels of a sequence pass (sequence_kernel.h, launched by sequence_lib.hip), behind the path stage and its retry route:
+// every frame was planned with the constant initial path; the runs of frames that read it are planned again in order, a wavefront
+// per run.
+static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const PassIO& io) {
+  const fsdp_ctx::Sequence& sq = *c->sequence;
+  fsdp_seq_launch_args a;
+  a.n_planners = sq.n_planners;
+  a.n_steps = sq.n_steps;
+  a.poses = in.d_poses;
+  a.matched = q.d_match;
+  a.initial_prev = sq.with_init ? q.d_seq_init : nullptr;
+  a.gpath = c->d_gpath;
+  a.n_gpath = c->n_gpath;
+  a.arena = q.d_arena;
+  a.out = q.d_path;
+  a.seq = q.d_seq;
+  a.final_prev = q.d_seq_final;
+  a.replanned_out = &(q.d_trailer + io.trailer)->pad;
+  a.prm = c->d_params;
+  fsdp_seq_launch(q.stream, &a);
 }
 
 // use_unknown_cones = False: the batch without its UNKNOWN cones into the slot's filter buffers; returns the view the
@@ -724,6 +764,10 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io
     after_path = MARK_PLAIN;
     launch_path_retry(c, q, in, !force_routes || c->retry_hint > 0);
     names += "path_retry_kernel,";
+  }
+  if (c->sequence) {  // (fsdp_plan_sequence: never timed)
+    launch_sequence(c, q, in, io);
+    names += "seq_mark_kernel,seq_chain_kernel,seq_final_kernel,";
   }
   mark(q, t, after_path);
   launch_assemble(c, q, in.n_frames, io, false);
@@ -1690,6 +1734,114 @@ int fsdp_plan_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const double*
 int fsdp_plan_batch_compact(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev_paths,
                             fsdp_compact_result* results) {
   return plan_blocking(c, n_frames, off, cones, poses, prev_paths, (fsdp_frame_result*)results, true);
+}
+
+// n_steps consecutive steps of n_planners planners as ONE pass (frame = step * n_planners + planner): never cut into chunks —
+// a chunk border would cut every planner's chain.  The pass is a ticket on slot 0 like a chunk of plan_blocking, with the
+// chain kernels in front of its assembly (launch_pass, c->sequence).
+static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                         const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev, long long* n_replanned) {
+  if (!c) return 1;
+  if (n_replanned) *n_replanned = 0;
+  if (c->mission == 2) {
+    c->err = "fsdp_plan_sequence: a skidpad context plans through fsdp_skidpad_step";
+    return 1;
+  }
+  if (c->n_cache > 0) {
+    c->err = "fsdp_plan_sequence: the sorting cache is on (fsdp_sort_cache_reset): it is state of lock-step calls (fsdp_plan_batch_sequential)";
+    return 1;
+  }
+  if (!fsdp_seq_launch) {
+    c->err = "fsdp_plan_sequence: this library was built without csrc/sequence_lib.hip";
+    return 1;
+  }
+  if (c->outstanding) return busy_error(c, "fsdp_plan_sequence");
+  if (n_planners < 1 || n_steps < 1) {
+    c->err = "fsdp_plan_sequence: n_planners and n_steps must be >= 1";
+    return 1;
+  }
+  const long long frames = (long long)n_planners * n_steps;
+  if (frames > (0x7fffffff - SEQ_LIST) / 2) {  // (the head list holds two ints per frame behind its header, indexed by int)
+    c->err = "fsdp_plan_sequence: " + std::to_string(frames) + " frames in one pass (at most 2^30 - 3)";
+    return 1;
+  }
+  if (!results) {
+    c->err = "fsdp_plan_sequence: results is NULL";
+    return 1;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int n = (int)frames;
+  Batch b;
+  if (int rc = check_batch(c, n, off, cones, poses, nullptr, &b)) return rc;
+  if (int rc = sync_all(c)) return rc;
+  c->last = fsdp_ctx::LastPass();
+  Work& q = c->slot[0];
+  Work::Ticket& t = q.tk[0];
+  // a frame count the device has no room for is an error code: whatever was replaced on the way is replaced again next time
+  auto no_room = [&](int rc) {
+    q.cap_frames = q.in.cap_frames = q.in.cap_prev = 0;
+    q.seq_cap_frames = q.seq_cap_planners = 0;
+    (void)hipGetLastError();
+    return rc;
+  };
+  if (int rc = ensure_work(c, q, n)) return no_room(rc);
+  if ((size_t)n > q.seq_cap_frames) {
+    if (hipError_t e = regrow(q.d_seq, (size_t)SEQ_LIST + 2 * (size_t)n)) {
+      c->err = std::string("fsdp_plan_sequence: ") + hipGetErrorString(e);
+      return no_room(2);
+    }
+    q.seq_cap_frames = (size_t)n;
+  }
+  if ((size_t)n_planners > q.seq_cap_planners) {
+    hipError_t e = regrow(q.d_seq_init, (size_t)PATH_POINTS * 4 * (size_t)n_planners);
+    if (e == hipSuccess) e = regrow(q.d_seq_final, (size_t)PATH_POINTS * 4 * (size_t)n_planners);
+    if (e != hipSuccess) {
+      c->err = std::string("fsdp_plan_sequence: ") + hipGetErrorString(e);
+      return no_room(2);
+    }
+    q.seq_cap_planners = (size_t)n_planners;
+  }
+  const size_t prev_bytes = sizeof(double) * PATH_POINTS * 4 * (size_t)n_planners;
+  if (initial_prev) HIP_TRY(c, hipMemcpyAsync(q.d_seq_init, initial_prev, prev_bytes, hipMemcpyHostToDevice, q.stream));
+  fsdp_ctx::Sequence sq;
+  sq.n_planners = n_planners;
+  sq.n_steps = n_steps;
+  sq.with_init = initial_prev != nullptr;
+  struct Scope {
+    fsdp_ctx* c;
+    ~Scope() { c->sequence = nullptr; }
+  } scope{c};
+  c->sequence = &sq;
+  t.batch = b;
+  t.skid = false;
+  t.in_flight = n;
+  t.user_results = results;
+  t.user_info = nullptr;
+  t.compact = compact;
+  if (int rc = enqueue_ticket(c, q, t, false)) {
+    (void)hipStreamSynchronize(q.stream);
+    t.user_results = nullptr;
+    t.compact = false;
+    return no_room(rc);
+  }
+  t.id = c->next_ticket++;
+  c->outstanding++;
+  int rc = fsdp_collect(c, t.id);  // (waits; runs the pass again, chain kernels included, if it lacked a route)
+  c->next_ticket--;                // (the number was internal, like plan_blocking's)
+  if (rc != 0) return rc;
+  if (n_replanned) *n_replanned = __atomic_load_n(&q.h_trailer[0].pad, __ATOMIC_RELAXED);
+  if (final_prev) HIP_TRY(c, copy_sync(c, final_prev, q.d_seq_final, prev_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int fsdp_plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                       const double* initial_prev, fsdp_frame_result* results, double* final_prev, long long* n_replanned) {
+  return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, results, false, final_prev, n_replanned);
+}
+
+int fsdp_plan_sequence_compact(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                               const double* initial_prev, fsdp_compact_result* results, double* final_prev, long long* n_replanned) {
+  return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true, final_prev, n_replanned);
 }
 
 int fsdp_sort_cache_reset(fsdp_ctx* c, int n_planners) {

@@ -884,6 +884,9 @@ __device__ __forceinline__ Arena frame_arena(double* arena, int frame, const Par
   return A;
 }
 
+// (FSDP_SEQUENCE_UNIT: csrc/sequence_lib.hip compiles this header for the chain kernels alone — the kernels that are no templates
+// belong to fsdp_lib.hip's code object only)
+#ifndef FSDP_SEQUENCE_UNIT
 // core_calculate_path.py:103-121: previous_paths[0] = parameterize_path(fit(chord).predict())
 __global__ void __launch_bounds__(64) default_path_kernel(const double* __restrict__ chord, double* __restrict__ arena,
                                                           double* __restrict__ out, const Params* __restrict__ prm) {
@@ -910,6 +913,8 @@ __global__ void __launch_bounds__(64) default_path_kernel(const double* __restri
   if (rc != 0 && lane < PATH_POINTS)
     for (int q = 0; q < 4; q++) out[4 * lane + q] = NAN;
 }
+
+#endif
 
 // Lanes per frame of the product path kernel (see the header comment).  Three instantiations, chosen per launch by the
 // host (fsdp_lib.hip launch_path): G = 8 (eight frames per wavefront) when passes overlap or a pass has more than
@@ -1134,6 +1139,27 @@ __device__ __forceinline__ int path_frame(PS& S, int frame, const double* __rest
   return status;
 }
 
+// The same with previous_paths[-1] by pointer instead of by (base, frame): (PATH_POINTS, 4) rows [s, x, y, curvature]
+// anywhere — the row of another frame of `out` included (sequence_kernel.h: a frame the launch has already planned; no
+// __restrict__ on either).  Every read of it is indexed by the lane, i.e. a vector load.
+// KEEP THE TWO BODIES THE SAME: this one is the one above without its choice of `prev`, statement for statement — the results of
+// fsdp_plan_sequence equal those of fsdp_plan_batch_sequential byte for byte only as long as they are (tests/test_sequence_gpu.py
+// holds them together).  It is a body of its own because the one above calling it moved the register allocation of
+// path_kernel<64> (674 -> 676 SGPR spills), and the earlier kernels are to compile to exactly what they were.
+template <int G, bool FAST, class PS>
+__device__ __forceinline__ int path_frame(PS& S, int frame, const double* __restrict__ poses, const MatchOut* __restrict__ matched,
+                                          const double* prev, const double* __restrict__ gpath, int n_gpath, double* arena, PathOut* out,
+                                          const Params* __restrict__ prm) {
+  const Arena A = frame_arena(arena, frame, prm);
+  PathOut* o = &out[frame];
+  const double px = poses[4 * frame + 0], py = poses[4 * frame + 1], dx = poses[4 * frame + 2], dy = poses[4 * frame + 3];
+  int fallback = 0, n_dense = 0, n1 = 0;
+  int status = path_front<G, FAST>(S, A, &matched[frame], px, py, prev, gpath, n_gpath, &fallback, &n1);
+  if (status == ST_OK) status = finish_path<G, FAST>(S, A, n1, px, py, dx, dy, prev, o->path, &fallback, &n_dense);
+  write_path_status<G>(o, status, fallback, n_dense);
+  return status;
+}
+
 // ---- the path stage as three kernels (large batches) --------------------------------------------------------------------
 // 72 % of the one-kernel stage is the refit of the dense path update (fit #2: 450-500 points, ~10 knots, 2-5 observation
 // passes, 3-19 smoothing iterations).  Split off, it becomes a kernel that holds nothing but one degree-3 fit — few enough
@@ -1306,6 +1332,7 @@ __global__ void __launch_bounds__(64, PATH_WAVES) path_kernel(int n_frames, cons
 // wavefront at one wavefront per SIMD: 3 % of the frames of a noisy batch took 60 % of the chip's time); what that form
 // cannot finish (an exponent outside the fast division's band) is planned once more by the whole wavefront with plain IEEE
 // divisions.  The route never changes a result (tests: test_every_path_kernel_instantiation_equals_oracle).
+#ifndef FSDP_SEQUENCE_UNIT
 constexpr int RETRY_WAVES = 1;  // (two per SIMD: 107 registers spilled to scratch, slower: profiles/r04_ab_variants.txt 4)
 __global__ void __launch_bounds__(64, RETRY_WAVES) path_retry_kernel(const double* __restrict__ poses, const MatchOut* __restrict__ matched,
                                                            const double* __restrict__ default_path,
@@ -1347,5 +1374,7 @@ __global__ void __launch_bounds__(64, RETRY_WAVES) path_retry_kernel(const doubl
     }
   }
 }
+
+#endif  // FSDP_SEQUENCE_UNIT
 
 }  // namespace fsdp

@@ -1,0 +1,159 @@
+// Sequences of consecutive steps in one pass (fsdp_plan_sequence): frame f = step * n_planners + planner, planner i's
+// steps chained through previous_paths[-1] (core_calculate_path.py:572-573) exactly as n_steps calls of
+// fsdp_plan_batch_sequential chain them.
+//
+// The reference reads the previous path in its fallbacks only (:203, 218-221, 235-236, 531-536, 564-570), and each of those
+// reads sets one of the four FB_READ_PREVIOUS bits of PathOut.fallback (path_kernel.h: path_front bits 1 and 2,
+// overwrite_if_too_far bit 4, finish_path bit 8 — mpc_finish's "previous array handed on" return is that retry, bit 8).
+// So the pass first plans every frame with the constant initial path (prev_paths == nullptr, like fsdp_plan_batch); a frame
+// without such a bit never looked at its previous path and its result is final.  Then
+//
+//   seq_mark_kernel   lanes = frames: the heads of the runs of flagged frames, appended to a device list,
+//   seq_chain_kernel  one wavefront per run: the path stage of the run's flagged frames once more, in order, each with the
+//                     path its planner's most recent successful step really left,
+//   seq_final_kernel  one wavefront per planner: the path the planner hands to the step after the sequence; the re-plan
+//                     count into the pass trailer.
+//
+// A frame is one of three things to its planner's chain (seq_class):
+//   SETTLED      not flagged, status 0: final, and the previous path of what follows,
+//   TRANSPARENT  not flagged, status != 0: the reference raised, the chain is left untouched (planner.py:271-274) — and a frame
+//                still carrying ST_RETRY: the pass lacked its retry route and is about to run again,
+//   FLAGGED      read the previous path, whatever its status (a frame that failed on the constant path may succeed on the true
+//                one): final only once everything flagged directly before it is.
+// These kernels are a translation unit of their own (sequence_lib.hip), i.e. a code object of their own inside the library: the
+// kernels of fsdp_lib.hip compile to exactly what they were (a second user of the whole-wavefront path stage in their module
+// moved path_retry_kernel's register allocation).
+// A run is a maximal sequence of one planner's flagged frames with nothing but transparent frames between them; only runs
+// serialize, and every run has a wavefront of its own.
+#pragma once
+
+#include "path_kernel.h"
+#include "sequence_launch.h"
+
+namespace fsdp {
+
+enum { SEQ_SETTLED = 0, SEQ_TRANSPARENT = 1, SEQ_FLAGGED = 2 };
+
+
+__device__ __forceinline__ int seq_class(int status, int fallback) {
+  if (status == ST_RETRY) return SEQ_TRANSPARENT;
+  if (fallback & FB_READ_PREVIOUS) return SEQ_FLAGGED;
+  return status == ST_OK ? SEQ_SETTLED : SEQ_TRANSPARENT;
+}
+
+// Status and flags of a frame another kernel — or this wavefront, a moment ago — wrote: loads that stay vector loads whatever
+// the compiler knows about the address (the scalar cache is not coherent with vector stores)
+__device__ __forceinline__ int seq_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ int seq_class_of(const PathOut* out, size_t frame) {
+  return seq_class(seq_load(&out[frame].status), seq_load(&out[frame].fallback));
+}
+
+// Where the chain of `planner` stands in front of step `step`: walks back over the transparent frames.  Returns the class of
+// the frame the walk stops at (SEQ_TRANSPARENT: it ran off the start) and that frame in *at (-1: none).
+__device__ __forceinline__ int seq_walk_back(const PathOut* out, int n_planners, int planner, int step, int* at) {
+  for (int s = step - 1; s >= 0; s--) {
+    const size_t f = (size_t)s * n_planners + planner;
+    const int c = seq_class_of(out, f);
+    if (c != SEQ_TRANSPARENT) {
+      *at = (int)f;
+      return c;
+    }
+  }
+  *at = -1;
+  return SEQ_TRANSPARENT;
+}
+
+// grid = ceil(n_frames / 64).  A flagged frame is a run head when the walk back from it stops at a settled frame or runs off
+// the start; not when it stops at a flagged frame, whose result is not final yet.
+__global__ void __launch_bounds__(64) seq_mark_kernel(int n_planners, int n_steps, const PathOut* __restrict__ out, int* __restrict__ seq) {
+  const long long n_frames = (long long)n_planners * n_steps;
+  const long long frame = (long long)blockIdx.x * WAVE + lane_id();
+  bool head = false;
+  int pred = -1;
+  if (frame < n_frames && seq_class_of(out, (size_t)frame) == SEQ_FLAGGED) {
+    const int step = (int)(frame / n_planners), planner = (int)(frame % n_planners);
+    head = seq_walk_back(out, n_planners, planner, step, &pred) != SEQ_FLAGGED;
+  }
+  // one atomic per wavefront (ballot + prefix count), like the retry list's push
+  const unsigned long long m = __ballot(head);
+  if (m == 0) return;
+  const int lane = lane_id();
+  int base = 0;
+  if (lane == __ffsll((long long)m) - 1) base = atomicAdd(&seq[SEQ_HEADS], __popcll(m));
+  base = __shfl(base, __ffsll((long long)m) - 1, WAVE);
+  if (head) {
+    const int k = base + __popcll(m & ((1ull << lane) - 1ull));
+    seq[SEQ_LIST + 2 * (size_t)k] = (int)frame;
+    seq[SEQ_LIST + 2 * (size_t)k + 1] = pred;
+  }
+}
+
+// One wavefront per run (grid-stride over the head list, one wavefront per SIMD like path_retry_kernel's whole-wavefront form):
+// the path stage of the run's flagged frames from their MatchOut, in their own arenas, by the exact form path_frame<WAVE, false>
+// (256 knots, all degrees, plain divisions: results do not depend on the route a frame took).
+// initial_prev (optional): (n_planners, PATH_POINTS, 4), a row whose [0][0] is NaN = none.
+__global__ void __launch_bounds__(64, 1) seq_chain_kernel(int n_planners, int n_steps, const double* __restrict__ poses,
+                                                          const MatchOut* __restrict__ matched, const double* __restrict__ initial_prev,
+                                                          const double* __restrict__ gpath, int n_gpath, double* arena, PathOut* out,
+                                                          int* seq, const Params* __restrict__ prm) {
+  __shared__ PathShared<WAVE, false, NK_BIG> S;
+  const int n_heads = wave_uniform(seq_load(&seq[SEQ_HEADS]));
+  int replanned = 0;
+#pragma unroll 1
+  for (int k = blockIdx.x; k < n_heads; k += gridDim.x) {
+    const int head = wave_uniform(seq_load(&seq[SEQ_LIST + 2 * (size_t)k])), pred = wave_uniform(seq_load(&seq[SEQ_LIST + 2 * (size_t)k + 1]));
+    const int planner = head % n_planners;
+    // the path in front of the run: the settled frame's, the caller's row, or none (the run's frames then stand as they are
+    // until one of them succeeds: the constant initial path they were planned with is what a fresh planner reads)
+    const double* prev = nullptr;
+    if (pred >= 0) {
+      prev = &out[pred].path[0][0];
+    } else if (initial_prev != nullptr) {
+      const double* row = initial_prev + (size_t)planner * (PATH_POINTS * 4);
+      if (!isnan(row[0])) prev = row;
+    }
+#pragma unroll 1
+    for (int s = head / n_planners; s < n_steps; s++) {
+      const size_t frame = (size_t)s * n_planners + planner;
+      const int c = wave_uniform(seq_class_of(out, frame));
+      if (c == SEQ_TRANSPARENT) continue;
+      if (c == SEQ_SETTLED) break;
+      int status;
+      if (prev != nullptr) {
+        status = wave_uniform(path_frame<WAVE, false>(S, (int)frame, poses, matched, prev, gpath, n_gpath, arena, out, prm));
+        replanned++;
+        // the frame's path has left the wavefront before the next frame of the run loads it as its previous path
+        __syncthreads();
+        stores_acknowledged();
+      } else {
+        status = wave_uniform(seq_load(&out[frame].status));
+      }
+      if (status == ST_OK) prev = &out[frame].path[0][0];
+    }
+  }
+  if (replanned > 0 && lane_id() == 0) atomicAdd(&seq[SEQ_REPLANNED], replanned);
+}
+
+// grid = n_planners.  final_prev[planner] = the path of the planner's last successful step, else its initial_prev row, else NaN
+// (none yet: the next call starts it as a fresh planner).  Block 0 hands the re-plan count to the host: replanned_out is the
+// spare word of the pass trailer (assemble_kernel.h PassTrailer::pad, which assemble_kernel leaves alone; the trailer's seq,
+// written last and in stream order behind this kernel, publishes it).
+__global__ void __launch_bounds__(64) seq_final_kernel(int n_planners, int n_steps, const PathOut* __restrict__ out,
+                                                       const double* __restrict__ initial_prev, double* __restrict__ final_prev,
+                                                       const int* __restrict__ seq, int32_t* __restrict__ replanned_out) {
+  const int planner = blockIdx.x, lane = lane_id();
+  if (planner == 0 && lane == 0 && replanned_out != nullptr)
+    __hip_atomic_store(replanned_out, seq[SEQ_REPLANNED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (planner >= n_planners || final_prev == nullptr) return;
+  const double* src = nullptr;
+  for (int s = n_steps - 1; s >= 0 && src == nullptr; s--) {
+    const PathOut* o = &out[(size_t)s * n_planners + planner];
+    if (o->status == ST_OK) src = &o->path[0][0];
+  }
+  if (src == nullptr && initial_prev != nullptr && !isnan(initial_prev[(size_t)planner * (PATH_POINTS * 4)]))
+    src = initial_prev + (size_t)planner * (PATH_POINTS * 4);
+  double* dst = final_prev + (size_t)planner * (PATH_POINTS * 4);
+  for (int i = lane; i < PATH_POINTS * 4; i += WAVE) dst[i] = src ? src[i] : NAN;
+}
+
+}  // namespace fsdp

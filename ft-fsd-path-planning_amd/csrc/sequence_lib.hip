@@ -1,0 +1,22 @@
+// The chain kernels of fsdp_plan_sequence (sequence_kernel.h) and their launches: a translation unit, and so a code object, of
+// their own next to fsdp_lib.hip, built into the same shared library (__graft_entry__.py).  As part of fsdp_lib.hip's module a
+// second user of the whole-wavefront path stage moved path_retry_kernel's register allocation; here nothing the earlier kernels
+// are compiled from changes.  The code object holds the three chain kernels and nothing else: path_kernel.h leaves out its kernels
+// that are no templates (FSDP_SEQUENCE_UNIT), which belong to fsdp_lib.hip.
+#include <hip/hip_runtime.h>
+
+#define FSDP_SEQUENCE_UNIT 1
+#include "sequence_kernel.h"
+
+// The grid of seq_chain_kernel follows its list like path_retry_kernel's (grid-stride, one wavefront per SIMD at most).
+extern "C" void fsdp_seq_launch(hipStream_t stream, const fsdp_seq_launch_args* a) {
+  using namespace fsdp;
+  const long long n = (long long)a->n_planners * a->n_steps;
+  (void)hipMemsetAsync(a->seq, 0, sizeof(int) * SEQ_LIST, stream);
+  hipLaunchKernelGGL(seq_mark_kernel, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, a->n_planners, a->n_steps,
+                     (const PathOut*)a->out, a->seq);
+  hipLaunchKernelGGL(seq_chain_kernel, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(WAVE), 0, stream, a->n_planners, a->n_steps, a->poses, a->matched,
+                     a->initial_prev, a->gpath, a->n_gpath, a->arena, a->out, a->seq, a->prm);
+  hipLaunchKernelGGL(seq_final_kernel, dim3((unsigned)a->n_planners), dim3(WAVE), 0, stream, a->n_planners, a->n_steps, (const PathOut*)a->out,
+                     a->initial_prev, a->final_prev, (const int*)a->seq, a->replanned_out);
+}

@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(64) skid_reloc_kernel(int n_inst, const int32_
 
 // ---- the path step of a planner: pieces shared by the kernels below -------------------------------------------------------
 constexpr int SKID_GROUP_MAX = 16;  // steps of one planner that may share a launch
-constexpr int FB_READ_PREVIOUS = 1 | 2 | 4 | 8;  // path_fallback bits whose branch reads previous_paths[-1] (16, 32: how the path was extended)
+// (FB_READ_PREVIOUS: fsdp_device.h)
 constexpr int ST_SERIAL = 298;      // internal (PathMid::status): the step is planned by its planner's own wavefront, behind its predecessor
 
 struct SkidStep {

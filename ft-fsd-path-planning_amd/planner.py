@@ -238,6 +238,34 @@ class PathPlanner:
             return self._multi.plan_batch(cone_offsets, cones_xyt, poses)
         return self._ctx.plan_batch(cone_offsets, cones_xyt, poses)
 
+    def plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int = 1, initial_prev=None, compact: bool = False,
+                      continue_state: bool = False):
+        """Whole stateful sequences in one call (fsdp_plan_sequence): n_planners planners x T consecutive steps, frame = step *
+        n_planners + planner — for every planner the results its own stateful planner object would give step by step (a step the
+        reference raises on leaves the chain untouched; its record carries the status instead of an exception).  Returns
+        (results, final_prev (n_planners, path_points, 4): the path each planner hands to the next step, NaN rows = none yet,
+        n_replanned: frames the device planned a second time).
+
+        The call neither reads nor updates this object's own previous path: every planner of the sequence starts from
+        initial_prev (None or NaN rows: fresh planners).  continue_state=True (one planner, no initial_prev) makes the sequence the
+        continuation of this object's single-frame calls instead: its previous path goes in, and the path the sequence leaves
+        becomes the object's.  Not for skidpad, acceleration / ebs_test planners, experimental_performance_improvements (the
+        sorting cache is state of lock-step calls) or devices=."""
+        if self._skid is not None or self._accel is not None:
+            raise RuntimeError("plan_sequence: the skidpad, acceleration and ebs_test missions keep their own per-planner state")
+        if self._sort_cache:
+            raise RuntimeError("plan_sequence: experimental_performance_improvements (the sorting cache) is state of lock-step calls")
+        if self._multi is not None:
+            raise RuntimeError("plan_sequence: one GPU (a planner with devices= has no sequence form)")
+        if continue_state:
+            if n_planners != 1 or initial_prev is not None or not self.stateful:
+                raise ValueError("continue_state: one stateful planner, and no initial_prev next to the object's own previous path")
+            initial_prev = None if self._prev is None else self._prev[None]
+        res, final, again = self._ctx.plan_sequence(cone_offsets, cones_xyt, poses, n_planners, initial_prev=initial_prev, compact=compact)
+        if continue_state and not np.isnan(final[0, 0, 0]):
+            self._prev = np.array(final[0, : self._ctx.horizon])
+        return res, final, again
+
     # ---- reference-shaped single-frame call ---------------------------------------------
     def calculate_path_in_global_frame(
         self,

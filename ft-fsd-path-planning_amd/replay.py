@@ -185,28 +185,37 @@ def replay_ranked(mission, positions, directions, observations, top_k: int, devi
     return cat(status, 0, np.int32), cat(counts, (0, 2), np.int32), cat(margins, (0, 2), np.float64), cat(deciding, (0, 2), np.int64)
 
 
-FB_READ_PREVIOUS = 1 | 2 | 4 | 8  # path_fallback bits of the branches that read previous_paths[-1] (include/fsdp.h)
+FB_READ_PREVIOUS = 1 | 2 | 4 | 8  # path_fallback bits of the branches that read previous_paths[-1] (include/fsdp.h; the frames fsdp_plan_sequence plans again)
 
 
 def replay_stateful_batched(mission, positions, directions, observations, device=None, batch_frames: int = 4096, depth: int = 4):
     """The recording as ONE planner sees it — consecutive frames chain through previous_paths[-1] (core_calculate_path.py:
     572-573), which the reference reads in its fallbacks only (:202-203, 218-221, 235-236, 531-536, 564-570) — at the speed
-    of the batched replay: all frames as independent frames first (every one with the fresh planner's previous path), then
-    the frames that did read the previous path (their path_fallback bits say so), in recording order, once more with the
-    path their predecessor really left (a frame the reference raises on leaves none).  Returns the results in recording
-    order, the seconds of the batched replay and the number of frames planned again."""
-    res, sec = replay_batched(mission, positions, directions, observations, device, repeats=1, batch_frames=batch_frames, depth=depth)
-    res = res.copy()
+    of a batched replay: the recording cut into consecutive calls of `batch_frames` steps of fsdp_plan_sequence (one planner),
+    each handing the path it leaves to the next (final_prev -> initial_prev).  A call plans all its frames as independent
+    frames first and then, on the device, the frames that did read the previous path once more, in order, with the path
+    their predecessor really left (a frame the reference raises on leaves none).  Returns the results in recording order, the
+    seconds of the replay and the number of frames planned again.  (depth: kept for callers of the earlier form, which
+    streamed the independent frames; a sequence call is one pass.)"""
     planner = PathPlanner(mission, device=device)
     ctx = planner._ctx
-    prev, again = None, 0
-    for k in range(len(res)):
-        if (res["path_fallback"][k] & FB_READ_PREVIOUS) and prev is not None:
-            off, cones, poses = pack_frames([(observations[k], positions[k], directions[k])])
-            res[k] = ctx.plan_batch_sequential(off, cones, poses, prev[None])[0]
-            again += 1
-        if res["status"][k] == 0:
-            prev = np.array(res["path"][k][: ctx.horizon])
+    frames = list(zip(observations, positions, directions))
+    chunks = [pack_frames(frames[lo:lo + batch_frames]) for lo in range(0, len(frames), batch_frames)]
+
+    def one_replay():
+        parts, prev, again = [], None, 0
+        for off, cones, poses in chunks:
+            res, prev, k = ctx.plan_sequence(off, cones, poses, 1, initial_prev=prev)
+            parts.append(res)
+            again += k
+        return parts, again
+
+    if chunks:
+        ctx.plan_sequence(*chunks[0], 1)  # warm-up, like replay_batched's
+    t0 = time.perf_counter()
+    parts, again = one_replay()
+    sec = time.perf_counter() - t0
+    res = np.concatenate(parts) if parts else np.zeros(0, ctx.result_dtype)
     return res, sec, again
 
 

@@ -209,6 +209,33 @@ int fsdp_plan_batch_sequential(fsdp_ctx* ctx, int n_frames, const int32_t* cone_
 /* the resident form of the above: applies to the next fsdp_run calls until reset with NULL */
 int fsdp_set_previous_paths(fsdp_ctx* ctx, const double* prev_paths);
 
+/* Whole stateful sequences in one call: n_planners planners x n_steps consecutive steps, frame f = step * n_planners + planner
+ * (cone_offsets: n_steps * n_planners + 1 CSR offsets, any base; poses and results in the same order) — the results of n_steps
+ * calls of fsdp_plan_batch_sequential with n_planners frames each, planner i's prev_paths row being the path of its most
+ * recent earlier step with status 0; the step-major layout is the concatenation of those batches.  Byte for byte.
+ *   A step the reference raises on (status != 0) leaves the chain untouched, as the planner object does.
+ *   initial_prev: (n_planners, FSDP_PATH_POINTS, 4) or NULL — what a planner without an earlier successful step reads; a NULL
+ *   pointer or a row whose [0][0] is NaN means the fresh planner's constant initial path.
+ *   final_prev (or NULL): (n_planners, FSDP_PATH_POINTS, 4), the path each planner would hand to step n_steps, in the same
+ *   encoding (a NaN row: none yet) — a recording cut into consecutive calls joined by final_prev -> initial_prev gives the
+ *   bytes of one call.
+ *   n_replanned (or NULL): frames planned a second time (below).
+ * It is ONE pass of the kernels whatever its size (never chunked: a chunk border would cut the chains): every frame is planned
+ * as an independent frame first, and the frames whose path_fallback has one of FSDP_FB_PREVIOUS_CENTER | SPLINE_ERROR | TOO_FAR
+ * | MPC_RETRY — the only branches in which the reference reads previous_paths[-1] — are planned again on the device, in
+ * order, with the path their predecessor really left (csrc/sequence_kernel.h); consecutive flagged steps of a planner
+ * serialize, everything else runs in parallel.  A flagged frame with neither a predecessor path nor an initial_prev row
+ * stands as it is and is not counted.
+ * Returns an error, with nothing planned: a skidpad context; a context whose sorting cache is on (the cache stays a
+ * lock-step feature); uncollected tickets; n_planners or n_steps < 1; a frame count beyond 2^30 - 3 or one the device has no
+ * memory for (the context stays usable). */
+int fsdp_plan_sequence(fsdp_ctx* ctx, int n_planners, int n_steps, const int32_t* cone_offsets, const double* cones_xyt,
+                       const double* poses, const double* initial_prev, fsdp_frame_result* results, double* final_prev,
+                       long long* n_replanned);
+int fsdp_plan_sequence_compact(fsdp_ctx* ctx, int n_planners, int n_steps, const int32_t* cone_offsets, const double* cones_xyt,
+                               const double* poses, const double* initial_prev, fsdp_compact_result* results, double* final_prev,
+                               long long* n_replanned);
+
 /* The reference's experimental sorting cache (PathPlanner(mission, experimental_performance_improvements=True),
  * core_trace_sorter.py:57-327): a side whose starting cones and whole cone list both lie within 0.1 m (same types) of the
  * planner's previous call reuses that call's configurations instead of searching again — applied to the CURRENT cones, as
