@@ -198,6 +198,8 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     lib.fsdp_plan_sequence.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
     lib.fsdp_plan_sequence_compact.argtypes = lib.fsdp_plan_sequence.argtypes
+    lib.fsdp_plan_sequence_cached.argtypes = lib.fsdp_plan_sequence.argtypes + [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+    lib.fsdp_plan_sequence_cached_compact.argtypes = lib.fsdp_plan_sequence_cached.argtypes
     lib.fsdp_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_longlong]
     lib.fsdp_pcie_probe.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                     ctypes.POINTER(ctypes.c_double)]
@@ -233,6 +235,7 @@ EXPORTED_SYMBOLS = [
     "fsdp_submit_compact", "fsdp_plan_batch_compact", "fsdp_set_option", "fsdp_pcie_probe",
     "fsdp_skidpad_submit", "fsdp_route_stats", "fsdp_ticket_capacity", "fsdp_selftest_det3", "fsdp_debug_arena", "fsdp_selftest_absminmax", "fsdp_selftest_libm", "fsdp_selftest_givens",
     "fsdp_sort_cache_reset", "fsdp_sort_cache_hits", "fsdp_sort_batch_ranked", "fsdp_plan_sequence", "fsdp_plan_sequence_compact",
+    "fsdp_plan_sequence_cached", "fsdp_plan_sequence_cached_compact",
 ]
 RANK_MAX, COST_TERMS = 64, 7  # include/fsdp.h FSDP_RANK_MAX, FSDP_COST_TERMS
 COST_TERM_NAMES = ("angle", "residual_distance", "number_of_cones", "initial_direction", "change_of_direction", "cones_on_either",
@@ -492,6 +495,33 @@ class Context:
                        None if init is None else init.ctypes.data, out.ctypes.data, final.ctypes.data, ctypes.byref(again)), "fsdp_plan_sequence")
         self.n_frames = n
         return out, final, int(again.value)
+
+    def plan_sequence_cached(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False):
+        """fsdp_plan_sequence_cached: plan_sequence on a context whose sorting cache is on for exactly n_planners planners
+        (sort_cache_reset) — the bytes of T plan_batch_sequential calls on this context, the planners' cache entries chained on the
+        device, read at the start and left as the T calls would leave them.  -> (results, final_prev, n_replanned, hits (frames, 2)
+        int8 as sort_cache_hits codes them, n_resorted = frames whose similarity check ran inside the in-order chain)."""
+        n_planners = int(n_planners)
+        if getattr(self, "n_cache", 0) != n_planners or n_planners < 1:
+            raise RuntimeError(f"plan_sequence_cached: the sorting cache is on for {getattr(self, 'n_cache', 0)} planners, the call holds "
+                               f"{n_planners} (sort_cache_reset(n_planners) turns it on)")
+        offsets, cones, poses, n = self._prep_any_base(cone_offsets, cones_xyt, poses)
+        if n < 1 or n % n_planners:
+            raise ValueError(f"plan_sequence_cached: {n} frames are not a whole number (>= 1) of steps of {n_planners} planners")
+        init = None
+        if initial_prev is not None:
+            init = self.pad_paths(initial_prev)
+            assert len(init) == n_planners
+        out = np.zeros(n, dtype=self.compact_dtype if compact else self.result_dtype)
+        final = np.zeros((n_planners, self.shapes.path_points, 4))
+        hits = np.zeros((n, 2), dtype=np.int8)
+        again, resorted = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        fn = self._lib.fsdp_plan_sequence_cached_compact if compact else self._lib.fsdp_plan_sequence_cached
+        self._check(fn(self._h, n_planners, n // n_planners, offsets.ctypes.data, cones.ctypes.data if len(cones) else None, poses.ctypes.data,
+                       None if init is None else init.ctypes.data, out.ctypes.data, final.ctypes.data, ctypes.byref(again), hits.ctypes.data,
+                       ctypes.byref(resorted)), "fsdp_plan_sequence_cached")
+        self.n_frames = n
+        return out, final, int(again.value), hits, int(resorted.value)
 
     @staticmethod
     def _prep_any_base(offsets, cones, poses):

@@ -102,6 +102,11 @@ struct Work {
   double* d_seq_init = nullptr;           // (planners, 40, 4)
   double* d_seq_final = nullptr;
   size_t seq_cap_frames = 0, seq_cap_planners = 0;
+  // fsdp_plan_sequence_cached (sequence_cache_kernel.h): the per-frame records of the speculative sort, hit codes, irregular frames per planner
+  SeqSpecRec* d_seqc_rec = nullptr;
+  int8_t* d_seqc_hits = nullptr;
+  int32_t* d_seqc_resorted = nullptr;
+  size_t seqc_cap_frames = 0, seqc_cap_planners = 0;
   int cap_frames = 0;
   // use_unknown_cones = False (filter_kernel.h): the batch without its UNKNOWN cones, and the way back for the indices
   int32_t* f_cnt = nullptr;
@@ -250,6 +255,7 @@ struct fsdp_ctx {
   struct Sequence {
     int n_planners = 0, n_steps = 0;
     bool with_init = false;  // the slot's d_seq_init holds the caller's initial_prev
+    bool cached = false;     // fsdp_plan_sequence_cached: the speculative sorting kernels and the cache chain (never cache_call)
   };
   const Sequence* sequence = nullptr;
 };
@@ -355,6 +361,9 @@ static void free_work(Work& w) {
   (void)hipFree(w.d_seq);
   (void)hipFree(w.d_seq_init);
   (void)hipFree(w.d_seq_final);
+  (void)hipFree(w.d_seqc_rec);
+  (void)hipFree(w.d_seqc_hits);
+  (void)hipFree(w.d_seqc_resorted);
   (void)hipFree(w.f_cnt);
   (void)hipFree(w.f_off);
   (void)hipFree(w.f_cones);
@@ -457,12 +466,41 @@ static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
   return v;
 }
 
+// fsdp_plan_sequence_cached: what sequence_cache_lib.hip's launches need (the kernels read cache buffer cache_cur, write the other)
+static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs& in, bool small) {
+  const int p = c->cache_cur, x = 1 - p;
+  fsdp_seqc_launch_args a;
+  a.n_planners = c->sequence->n_planners;
+  a.n_steps = c->sequence->n_steps;
+  a.off = in.d_off;
+  a.cones = in.d_cones;
+  a.poses = in.d_poses;
+  a.sorted = q.d_sort;
+  a.big = q.d_big;
+  a.big_state = q.d_sort_big;
+  a.big_blocks = SORT_BIG_BLOCKS;
+  a.small = small;
+  a.prm = c->d_params;
+  a.rec = q.d_seqc_rec;
+  a.prev = c->d_cache_hdr[p];
+  a.next = c->d_cache_hdr[x];
+  a.prev_xyt = c->d_cache_xyt[p];
+  a.prev_off = c->d_cache_off[p];
+  a.next_xyt = c->d_cache_xyt[x];
+  a.next_off = c->d_cache_off[x];
+  a.last_hits = c->d_cache_hits;
+  a.hits = q.d_seqc_hits;
+  a.resorted = q.d_seqc_resorted;
+  return a;
+}
+static bool seq_cached(const fsdp_ctx* c) { return c->sequence && c->sequence->cached; }
+
 // Which instantiation of the three sorting kernels (sort_kernel_128 | sort_kernel, sort_big_kernel) a launch takes: the ranked one
 // for fsdp_sort_batch_ranked, else the cached one while a call advances the sorting cache (c->cache_call), else the plain one
 struct SortVariant {
   const SortRankView* rank = nullptr;     // ranked: where the rows go ...
   SortRankScratchBig* scratch = nullptr;  // ... and sort_big_kernel_ranked's block for the cost terms (SORT_BIG_BLOCKS of them)
-  const char* suffix(const fsdp_ctx* c) const { return rank ? "_ranked" : (c->cache_call ? "_cached" : ""); }
+  const char* suffix(const fsdp_ctx* c) const { return rank ? "_ranked" : (c->cache_call ? "_cached" : (seq_cached(c) ? "_spec" : "")); }
 };
 
 // Both launches append the name of the kernel they took to `names` (fsdp_stage_names).
@@ -476,7 +514,10 @@ static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& s
   else if (c->cache_call)
     hipLaunchKernelGGL((small ? sort_kernel_128_cached : sort_kernel_cached), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
                        in.d_poses, q.d_sort, q.d_big, c->d_params, st, cache_view(c, q));
-  else
+  else if (seq_cached(c)) {
+    const fsdp_seqc_launch_args a = seqc_args(c, q, in, small);
+    fsdp_seqc_launch_sort(q.stream, &a);
+  } else
     hipLaunchKernelGGL((small ? sort_kernel_128 : sort_kernel), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
                        q.d_sort, q.d_big, c->d_params, st);
   names += std::string(small ? "sort_kernel_128" : "sort_kernel") + var.suffix(c);
@@ -490,7 +531,10 @@ static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in, std::string& 
   else if (c->cache_call)
     hipLaunchKernelGGL(sort_big_kernel_cached, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
                        c->d_params, cache_view(c, q));
-  else
+  else if (seq_cached(c)) {
+    const fsdp_seqc_launch_args a = seqc_args(c, q, in, false);
+    fsdp_seqc_launch_sort_big(q.stream, &a);
+  } else
     hipLaunchKernelGGL(sort_big_kernel, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
                        c->d_params);
   names += std::string("sort_big_kernel") + var.suffix(c);
@@ -753,6 +797,11 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io
     mark(q, t);
     if (int rc = launch_sort_big(c, q, in, names)) return rc;
     names += ',';
+  }
+  if (seq_cached(c)) {  // (fsdp_plan_sequence_cached: the sorting results become those of the cache-on lock-step calls)
+    const fsdp_seqc_launch_args a = seqc_args(c, q, in, false);
+    fsdp_seqc_launch_chain(q.stream, &a);
+    names += "seq_cache_mark_kernel,seq_cache_resolve_kernel,";
   }
   mark(q, t);
   launch_match(c, q, in);
@@ -1442,7 +1491,7 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     in_pinned = true;
   }
   PassIO io;
-  if (in_pinned && c->params.use_unknown_cones) {
+  if (in_pinned && c->params.use_unknown_cones && !seq_cached(c)) {  // (the speculative kernels read their predecessors' cones: device copies first)
     // the pass's sorting kernel reads the batch from the page-locked buffers and leaves the device copies (StageIn)
     if (int rc = take_batch(c, q.in, b)) return rc;
     StageIn& st = io.stage;
@@ -1739,34 +1788,53 @@ int fsdp_plan_batch_compact(fsdp_ctx* c, int n_frames, const int32_t* off, const
 // n_steps consecutive steps of n_planners planners as ONE pass (frame = step * n_planners + planner): never cut into chunks —
 // a chunk border would cut every planner's chain.  The pass is a ticket on slot 0 like a chunk of plan_blocking, with the
 // chain kernels in front of its assembly (launch_pass, c->sequence).
+// cached (fsdp_plan_sequence_cached): the planners' sorting-cache entries are chained on the device as well (c->sequence->cached:
+// the speculative sorting kernels and the cache chain of sequence_cache_kernel.h); hits: (n_steps * n_planners, 2) or NULL,
+// n_resorted or NULL.  The cache buffers are swapped once, after the whole call — a rerun pass reads the same entries.
 static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
-                         const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev, long long* n_replanned) {
+                         const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev, long long* n_replanned,
+                         bool cached = false, int8_t* hits = nullptr, long long* n_resorted = nullptr) {
   if (!c) return 1;
+  const std::string who = cached ? "fsdp_plan_sequence_cached" : "fsdp_plan_sequence";
   if (n_replanned) *n_replanned = 0;
+  if (n_resorted) *n_resorted = 0;
   if (c->mission == 2) {
-    c->err = "fsdp_plan_sequence: a skidpad context plans through fsdp_skidpad_step";
+    c->err = who + ": a skidpad context plans through fsdp_skidpad_step";
     return 1;
   }
-  if (c->n_cache > 0) {
+  if (!cached && c->n_cache > 0) {
     c->err = "fsdp_plan_sequence: the sorting cache is on (fsdp_sort_cache_reset): it is state of lock-step calls (fsdp_plan_batch_sequential)";
     return 1;
   }
   if (!fsdp_seq_launch) {
-    c->err = "fsdp_plan_sequence: this library was built without csrc/sequence_lib.hip";
+    c->err = who + ": this library was built without csrc/sequence_lib.hip";
     return 1;
   }
-  if (c->outstanding) return busy_error(c, "fsdp_plan_sequence");
+  if (cached && !fsdp_seqc_launch_sort) {
+    c->err = who + ": this library was built without csrc/sequence_cache_lib.hip";
+    return 1;
+  }
+  if (c->outstanding) return busy_error(c, who.c_str());
   if (n_planners < 1 || n_steps < 1) {
-    c->err = "fsdp_plan_sequence: n_planners and n_steps must be >= 1";
+    c->err = who + ": n_planners and n_steps must be >= 1";
+    return 1;
+  }
+  if (cached && c->n_cache == 0) {
+    c->err = who + ": the sorting cache is off (fsdp_sort_cache_reset(ctx, n_planners) turns it on)";
+    return 1;
+  }
+  if (cached && n_planners != c->n_cache) {
+    c->err = who + ": the sorting cache is on for " + std::to_string(c->n_cache) + " planners, the call holds " + std::to_string(n_planners) +
+             " planners (frame f is planner f % n_planners; fsdp_sort_cache_reset)";
     return 1;
   }
   const long long frames = (long long)n_planners * n_steps;
   if (frames > (0x7fffffff - SEQ_LIST) / 2) {  // (the head list holds two ints per frame behind its header, indexed by int)
-    c->err = "fsdp_plan_sequence: " + std::to_string(frames) + " frames in one pass (at most 2^30 - 3)";
+    c->err = who + ": " + std::to_string(frames) + " frames in one pass (at most 2^30 - 3)";
     return 1;
   }
   if (!results) {
-    c->err = "fsdp_plan_sequence: results is NULL";
+    c->err = who + ": results is NULL";
     return 1;
   }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1781,6 +1849,7 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
   auto no_room = [&](int rc) {
     q.cap_frames = q.in.cap_frames = q.in.cap_prev = 0;
     q.seq_cap_frames = q.seq_cap_planners = 0;
+    q.seqc_cap_frames = q.seqc_cap_planners = 0;
     (void)hipGetLastError();
     return rc;
   };
@@ -1801,12 +1870,34 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
     }
     q.seq_cap_planners = (size_t)n_planners;
   }
+  if (cached) {
+    if ((size_t)n > q.seqc_cap_frames) {
+      hipError_t e = regrow(q.d_seqc_rec, (size_t)n);
+      if (e == hipSuccess) e = regrow(q.d_seqc_hits, 2 * (size_t)n);
+      if (e != hipSuccess) {
+        c->err = who + ": " + hipGetErrorString(e);
+        return no_room(2);
+      }
+      q.seqc_cap_frames = (size_t)n;
+    }
+    if ((size_t)n_planners > q.seqc_cap_planners) {
+      if (hipError_t e = regrow(q.d_seqc_resorted, (size_t)n_planners)) {
+        c->err = who + ": " + hipGetErrorString(e);
+        return no_room(2);
+      }
+      q.seqc_cap_planners = (size_t)n_planners;
+    }
+    // the buffer the call writes gets room for every planner's largest frame of the sequence (cache_prepare, step by step)
+    for (int s = 0; s < n_steps; s++)
+      if (int rc = cache_prepare(c, n_planners, off + (size_t)s * n_planners, who.c_str())) return rc;
+  }
   const size_t prev_bytes = sizeof(double) * PATH_POINTS * 4 * (size_t)n_planners;
   if (initial_prev) HIP_TRY(c, hipMemcpyAsync(q.d_seq_init, initial_prev, prev_bytes, hipMemcpyHostToDevice, q.stream));
   fsdp_ctx::Sequence sq;
   sq.n_planners = n_planners;
   sq.n_steps = n_steps;
   sq.with_init = initial_prev != nullptr;
+  sq.cached = cached;
   struct Scope {
     fsdp_ctx* c;
     ~Scope() { c->sequence = nullptr; }
@@ -1831,6 +1922,15 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
   if (rc != 0) return rc;
   if (n_replanned) *n_replanned = __atomic_load_n(&q.h_trailer[0].pad, __ATOMIC_RELAXED);
   if (final_prev) HIP_TRY(c, copy_sync(c, final_prev, q.d_seq_final, prev_bytes, hipMemcpyDeviceToHost));
+  if (cached) {
+    std::vector<int32_t> resorted((size_t)n_planners);
+    HIP_TRY(c, copy_sync(c, resorted.data(), q.d_seqc_resorted, sizeof(int32_t) * resorted.size(), hipMemcpyDeviceToHost));
+    if (hits) HIP_TRY(c, copy_sync(c, hits, q.d_seqc_hits, 2 * (size_t)n, hipMemcpyDeviceToHost));
+    if (int rc = cache_finish(c)) return rc;  // (the last step's codes; the entries become the previous ones)
+    long long sum = 0;
+    for (int32_t v : resorted) sum += v;
+    if (n_resorted) *n_resorted = sum;
+  }
   return 0;
 }
 
@@ -1842,6 +1942,19 @@ int fsdp_plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* 
 int fsdp_plan_sequence_compact(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
                                const double* initial_prev, fsdp_compact_result* results, double* final_prev, long long* n_replanned) {
   return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true, final_prev, n_replanned);
+}
+
+int fsdp_plan_sequence_cached(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                              const double* initial_prev, fsdp_frame_result* results, double* final_prev, long long* n_replanned, int8_t* hits,
+                              long long* n_resorted) {
+  return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, results, false, final_prev, n_replanned, true, hits, n_resorted);
+}
+
+int fsdp_plan_sequence_cached_compact(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                                      const double* initial_prev, fsdp_compact_result* results, double* final_prev, long long* n_replanned,
+                                      int8_t* hits, long long* n_resorted) {
+  return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true, final_prev, n_replanned, true,
+                       hits, n_resorted);
 }
 
 int fsdp_sort_cache_reset(fsdp_ctx* c, int n_planners) {

@@ -11,7 +11,10 @@
 namespace fsdp {
 struct MatchOut;
 struct PathOut;
+struct SortOut;
 struct Params;
+struct SortCacheHdr;
+struct SeqSpecRec;
 // the list block of a sequence pass: [0] heads appended, [1] frames planned again (a 16-byte header, zeroed by one memset per
 // pass), then (frame, predecessor) per head: SEQ_LIST + 2 * frames ints
 constexpr int SEQ_HEADS = 0, SEQ_REPLANNED = 1, SEQ_LIST = 4;
@@ -35,4 +38,34 @@ struct fsdp_seq_launch_args {
 // header memset -> seq_mark_kernel -> seq_chain_kernel -> seq_final_kernel on `stream`.  Weak: a library built from fsdp_lib.hip
 // alone (the variant builds of tools/) has no sequence kernels, and fsdp_plan_sequence says so.
 extern "C" __attribute__((weak)) void fsdp_seq_launch(hipStream_t stream, const fsdp_seq_launch_args* a);
+
+// fsdp_plan_sequence_cached (sequence_cache_kernel.h, compiled as sequence_cache_lib.hip): the speculative sorting kernels in the
+// place of the plain ones, and the cache chain between the sorting results and the matching.
+struct fsdp_seqc_launch_args {
+  int n_planners, n_steps;
+  const int32_t* off;  // the batch as the sorting stage plans it (filtered when use_unknown_cones = 0)
+  const double* cones;
+  const double* poses;
+  fsdp::SortOut* sorted;
+  int* big;             // the big route's list
+  void* big_state;      // SortSharedBig blocks, `big_blocks` of them
+  int big_blocks;
+  bool small;           // no frame holds more than 128 cones
+  const fsdp::Params* prm;
+  fsdp::SeqSpecRec* rec;  // (frames)
+  // the two buffers of the sorting cache: the call reads `prev`, writes `next`
+  const fsdp::SortCacheHdr* prev;
+  fsdp::SortCacheHdr* next;
+  const double* prev_xyt;
+  const int32_t* prev_off;
+  double* next_xyt;
+  const int32_t* next_off;
+  int8_t* last_hits;   // (planners, 2)
+  int8_t* hits;        // (frames, 2)
+  int32_t* resorted;   // (planners)
+};
+extern "C" __attribute__((weak)) void fsdp_seqc_launch_sort(hipStream_t stream, const fsdp_seqc_launch_args* a);
+extern "C" __attribute__((weak)) void fsdp_seqc_launch_sort_big(hipStream_t stream, const fsdp_seqc_launch_args* a);
+// seq_cache_mark_kernel -> seq_cache_resolve_kernel
+extern "C" __attribute__((weak)) void fsdp_seqc_launch_chain(hipStream_t stream, const fsdp_seqc_launch_args* a);
 #endif

@@ -51,6 +51,9 @@ constexpr double CACHE_THR2 = 0.1 * 0.1;
 // be < 0.1 * 0.1 (np.min propagates a NaN, which fails), and the first row at that distance (np.argmin) must have the
 // row's type.  Distances in my_cdist_sq_euclidean's expansion form (cdist_sq: NumPy's dot of the (m,6) / (6,n) operands
 // is the same FMA chain for every shape that occurs here — one row or two, as for the n rows of a frame).
+// CAST: the rows are a caller's cone rows, whose type column the sorting stage narrows on its way into the frame state
+// (sort_frame: (uint8_t)(int)type); an entry's cone store holds the narrowed values already.
+template <bool CAST = false>
 __device__ __forceinline__ bool cache_row_similar(double x, double y, double t, const double* rows, int m) {
   double best = INFINITY;
   int arg = 0;
@@ -63,7 +66,34 @@ __device__ __forceinline__ bool cache_row_similar(double x, double y, double t, 
       arg = j;
     }
   }
+  if constexpr (CAST) return !nan && best < CACHE_THR2 && t == (double)(uint8_t)(int)rows[3 * arg + 2];
   return !nan && best < CACHE_THR2 && t == rows[3 * arg + 2];
 }
+
+// ---- fsdp_plan_sequence_cached (sequence_cache_kernel.h): what the speculative instantiation of the sorting kernels (SPEC) leaves
+// per frame next to its SortOut — both sides searched fresh, each side's result as SortCacheHdr holds it BEFORE combine_sides — and
+// what the chain kernel adds to it.  frame = step * n_planners + planner.
+struct SeqSpecRec {
+  int32_t n;             // cones the stage saw (0: more than the frame state holds)
+  int32_t sim_prev;      // cone_arrays_are_similar(this frame's cones, the cones of frame - n_planners; step 0: the planner's entry)
+  int32_t status[2];     // the side's own status; the right side is evaluated whatever the left one raised
+  int32_t best_len[2];
+  int32_t n_configs[2];
+  int32_t first_k[2][2];  // starting cones (-1: none; both -1: the side returned before the cache check)
+  double best_cost[2];
+  int16_t best[2][MAX_LEN];
+  // seq_cache_mark_kernel:
+  int32_t hit[2];        // 1 / 0 / -1 as fsdp_sort_cache_hits defines them
+  int32_t src[2];        // a hit side's result: the frame whose record holds it, -1: the planner's entry in front of the call
+  int32_t resolved;      // the frame's sorting status with the cache on
+  int32_t pad;
+};
+struct SeqSpecView {
+  SeqSpecRec* rec = nullptr;
+  int n_planners = 0;
+  const SortCacheHdr* prev = nullptr;  // the planners' entries in front of the call (step 0's sim_prev)
+  const double* prev_xyt = nullptr;
+  const int32_t* prev_off = nullptr;
+};
 
 }  // namespace fsdp

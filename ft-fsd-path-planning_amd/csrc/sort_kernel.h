@@ -1341,10 +1341,15 @@ __device__ inline void sort_cache_commit(const SH& S, const SortCacheFrame& cf, 
 
 // The sorting stage of one frame on one wavefront; S = the frame state (LDS or global memory).  CACHE: the sorting cache of
 // planner cache->base + frame is read and its next entry written (sort_cache.h).
-template <class SH, bool CACHE = false, bool RANKED = false>
+// SPEC: the speculative pass of fsdp_plan_sequence_cached — a fresh search of both sides, the right one also behind a left side that
+// raised (with the cache on a left hit never raises), the per-side results and the frame's similarity to its planner's previous
+// step into spec->rec[frame] (sort_cache.h SeqSpecRec).  The SortOut is the plain kernels' but for one thing: a capacity refusal
+// of either side sends the frame to sort_big_kernel_spec.
+template <class SH, bool CACHE = false, bool RANKED = false, bool SPEC = false>
 __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
                                   const double* __restrict__ poses, SortOut* __restrict__ out, const StageIn& stage = StageIn(),
-                                  const SortCacheView* cache = nullptr, const SortRankFrame* rank = nullptr) {
+                                  const SortCacheView* cache = nullptr, const SortRankFrame* rank = nullptr,
+                                  const SeqSpecView* spec = nullptr) {
   const int lane = lane_id();
   const bool staging = stage.src_off != nullptr;
   const int32_t* offs = staging ? stage.src_off : cone_offsets;
@@ -1438,10 +1443,33 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
     }
     cf.all_similar = ok;
   }
+  bool spec_similar = false;
+  if constexpr (SPEC) {
+    // the same sweep against the cones the planner's previous step was given (step 0: its entry in front of the call)
+    const int np = spec->n_planners;
+    const double* rows = nullptr;
+    int m = -1;
+    if (frame >= np) {
+      rows = cones_xyt + 3 * (size_t)offs[frame - np];
+      m = offs[frame - np + 1] - offs[frame - np];
+    } else if (spec->prev[frame].valid != 0) {
+      rows = spec->prev_xyt + 3 * (size_t)spec->prev_off[frame];
+      m = spec->prev[frame].n;
+    }
+    bool ok = status == ST_OK && n >= 3 && m == n;
+    for (int i0 = 0; i0 < n && ok; i0 += WAVE) {
+      const int i = i0 + lane;
+      const bool bad = i < n && !cache_row_similar<true>(S.x[i], S.y[i], (double)S.type[i], rows, n);
+      ok = __ballot(bad) == 0ull;
+    }
+    spec_similar = ok;
+  }
   // no cone with a side colour: both sides see the same distance matrix and hence the same mutual-kNN adjacency
   bool coloured = false;
   for (int i = lane; i < n; i += WAVE) coloured = coloured || S.type[i] == T_LEFT || S.type[i] == T_RIGHT;
   const bool colourless = __ballot(coloured) == 0ull;
+  int spec_status[2] = {-1, -1};
+  (void)spec_status;
 #ifndef FSDP_SORT_STOP
 #define FSDP_SORT_STOP 9  // (instruction accounting builds stop the stage after phase 1..4: tools/sort_phase_insts.sh)
 #endif
@@ -1454,10 +1482,50 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
     if (FSDP_SORT_STOP > 3) {
       status = sort_side_finish<SH, CACHE, RANKED>(S, n, T_LEFT, 0, px, py, dx, dy, &rk);
       __syncthreads();
+      if constexpr (SPEC) {
+        spec_status[0] = status;
+        spec_status[1] = sort_side_finish<SH, CACHE, RANKED>(S, n, T_RIGHT, 1, px, py, dx, dy, &rk);
+        if (status == ST_OK) status = spec_status[1];
+      } else {
       if (status == ST_OK) status = sort_side_finish<SH, CACHE, RANKED>(S, n, T_RIGHT, 1, px, py, dx, dy, &rk);
+      }
     }
   }
   __syncthreads();
+  if constexpr (SPEC) {
+    constexpr bool BIG = SH::CAP == BIG_CONES;
+    SeqSpecRec& r = spec->rec[frame];
+    const bool ran = spec_status[0] >= 0;  // the sides were prepared: S.first_k is this frame's
+    if (!ran) spec_status[0] = spec_status[1] = status;
+    if (lane < 2 * MAX_LEN) r.best[lane / MAX_LEN][lane % MAX_LEN] = S.best[lane / MAX_LEN][lane % MAX_LEN];
+    if (lane < 2) {
+      r.status[lane] = spec_status[lane];
+      r.best_len[lane] = ran ? S.best_len[lane] : 0;
+      r.n_configs[lane] = ran ? S.n_configs[lane] : 0;
+      r.best_cost[lane] = ran ? S.best_cost[lane] : 0.0;
+      r.first_k[lane][0] = ran ? S.first_k[lane][0] : -1;
+      r.first_k[lane][1] = ran ? S.first_k[lane][1] : -1;
+      r.hit[lane] = -1;
+      r.src[lane] = frame;
+    }
+    if (lane == 0) {
+      r.n = n;
+      r.sim_prev = spec_similar ? 1 : 0;
+      r.resolved = status;
+      r.pad = 0;
+    }
+    __syncthreads();
+    // what the plain kernels report for a frame whose left side raised: the right side was never evaluated
+    if (ran && spec_status[0] != ST_OK && lane == 0) {
+      S.n_configs[1] = 0;
+      S.best_cost[1] = 0.0;
+    }
+    // a side this frame state cannot hold: the frame is sort_big_kernel_spec's, whichever side it was
+    if (!BIG)
+      for (int sd = 0; sd < 2; sd++)
+        if (spec_status[sd] == ST_OVERFLOW_CONES || spec_status[sd] == ST_OVERFLOW_ENDS) status = spec_status[sd];
+    __syncthreads();
+  }
   int nl = 0, nr = 0;
   if (status == ST_OK && FSDP_SORT_STOP > 4) combine_sides<SH, CACHE, RANKED>(S, nl, nr);
   if (lane == 0) {
@@ -1499,6 +1567,7 @@ __device__ __forceinline__ void sort_kernel_body(SH& S, int n_frames, const int3
     big[1 + atomicAdd(&big[0], 1)] = frame;
   PROF_FLUSH();
 }
+#ifndef FSDP_SEQUENCE_CACHE_UNIT  // (csrc/sequence_cache_lib.hip compiles this header for its own instantiations alone)
 // Up to 255 cones per frame.  Three wavefronts per SIMD (168 registers, 13.0 KB of LDS per frame): the stage is a chain of
 // short dependent sections, and the third resident wavefront fills issue slots the other two leave open (+8 % frames/s over
 // two; 40 bytes of spill).
@@ -1509,6 +1578,7 @@ sort_kernel(int n_frames, const int32_t* __restrict__ cone_offsets, const double
   __shared__ SortShared S;
   sort_kernel_body(S, n_frames, cone_offsets, cones_xyt, poses, out, big, prm, stage);
 }
+#endif
 // The same code over a state for up to 128 cones (the host launches it when no frame of the batch holds more): the cone
 // arrays, neighbour lists and bit masks are half as long, which makes a frame SORT128_LDS and lets a SIMD hold
 // SORT_WAVES_128 wavefronts.
@@ -1517,6 +1587,7 @@ constexpr int SORT_WAVES_128 = 3;  // (the wide shapes' frame state is 12.4 KB: 
 #else
 constexpr int SORT_WAVES_128 = 4;
 #endif
+#ifndef FSDP_SEQUENCE_CACHE_UNIT
 __global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(SORT_WAVES_128)
 sort_kernel_128(int n_frames, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
                 const double* __restrict__ poses, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
@@ -1565,5 +1636,6 @@ __global__ void __launch_bounds__(64) sort_big_kernel_cached(const int32_t* __re
     __syncthreads();
   }
 }
+#endif  // FSDP_SEQUENCE_CACHE_UNIT
 
 }  // namespace fsdp

@@ -266,6 +266,27 @@ class PathPlanner:
             self._prev = np.array(final[0, : self._ctx.horizon])
         return res, final, again
 
+    def plan_sequence_cached(self, cone_offsets, cones_xyt, poses, initial_prev=None, compact: bool = False, continue_state: bool = False):
+        """plan_sequence for a planner built with experimental_performance_improvements=True (fsdp_plan_sequence_cached): T
+        consecutive steps of this one planner with the sorting cache chained on the device — the records T single calls would
+        give.  Returns (results, final_prev, n_replanned, hits (T, 2), n_resorted).
+
+        The sorting cache is the object's: the call starts from the entry its earlier calls left and leaves the one T single calls
+        would leave.  continue_state=True does the same for the previous path (no initial_prev then): the object's goes in, the
+        one the sequence leaves becomes the object's; without it the sequence starts from initial_prev (None: a fresh path-stage
+        history) and the object's previous path stays."""
+        if not self._sort_cache:
+            raise RuntimeError("plan_sequence_cached: a planner built with experimental_performance_improvements=True (the sorting cache); "
+                               "plan_sequence is the call without it")
+        if continue_state:
+            if initial_prev is not None:
+                raise ValueError("continue_state: no initial_prev next to the object's own previous path")
+            initial_prev = None if self._prev is None else self._prev[None]
+        res, final, again, hits, resorted = self._ctx.plan_sequence_cached(cone_offsets, cones_xyt, poses, 1, initial_prev=initial_prev, compact=compact)
+        if continue_state and not np.isnan(final[0, 0, 0]):
+            self._prev = np.array(final[0, : self._ctx.horizon])
+        return res, final, again, hits, resorted
+
     # ---- reference-shaped single-frame call ---------------------------------------------
     def calculate_path_in_global_frame(
         self,

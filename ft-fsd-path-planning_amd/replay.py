@@ -188,7 +188,8 @@ def replay_ranked(mission, positions, directions, observations, top_k: int, devi
 FB_READ_PREVIOUS = 1 | 2 | 4 | 8  # path_fallback bits of the branches that read previous_paths[-1] (include/fsdp.h; the frames fsdp_plan_sequence plans again)
 
 
-def replay_stateful_batched(mission, positions, directions, observations, device=None, batch_frames: int = 4096, depth: int = 4):
+def replay_stateful_batched(mission, positions, directions, observations, device=None, batch_frames: int = 4096, depth: int = 4,
+                            cache: bool = False):
     """The recording as ONE planner sees it — consecutive frames chain through previous_paths[-1] (core_calculate_path.py:
     572-573), which the reference reads in its fallbacks only (:202-203, 218-221, 235-236, 531-536, 564-570) — at the speed
     of a batched replay: the recording cut into consecutive calls of `batch_frames` steps of fsdp_plan_sequence (one planner),
@@ -196,22 +197,29 @@ def replay_stateful_batched(mission, positions, directions, observations, device
     frames first and then, on the device, the frames that did read the previous path once more, in order, with the path
     their predecessor really left (a frame the reference raises on leaves none).  Returns the results in recording order, the
     seconds of the replay and the number of frames planned again.  (depth: kept for callers of the earlier form, which
-    streamed the independent frames; a sequence call is one pass.)"""
-    planner = PathPlanner(mission, device=device)
+    streamed the independent frames; a sequence call is one pass.)
+    cache: the planner of a recording made with experimental_performance_improvements=True (fsdp_plan_sequence_cached: the
+    sorting cache chained on the device as well, its entry carried from call to call by the context)."""
+    planner = PathPlanner(mission, cache, device=device)
     ctx = planner._ctx
     frames = list(zip(observations, positions, directions))
     chunks = [pack_frames(frames[lo:lo + batch_frames]) for lo in range(0, len(frames), batch_frames)]
 
     def one_replay():
         parts, prev, again = [], None, 0
+        if cache:
+            ctx.sort_cache_reset(1)  # (a fresh planner: the warm-up left an entry)
         for off, cones, poses in chunks:
-            res, prev, k = ctx.plan_sequence(off, cones, poses, 1, initial_prev=prev)
+            if cache:
+                res, prev, k = ctx.plan_sequence_cached(off, cones, poses, 1, initial_prev=prev)[:3]
+            else:
+                res, prev, k = ctx.plan_sequence(off, cones, poses, 1, initial_prev=prev)
             parts.append(res)
             again += k
         return parts, again
 
     if chunks:
-        ctx.plan_sequence(*chunks[0], 1)  # warm-up, like replay_batched's
+        (ctx.plan_sequence_cached if cache else ctx.plan_sequence)(*chunks[0], 1)  # warm-up, like replay_batched's
     t0 = time.perf_counter()
     parts, again = one_replay()
     sec = time.perf_counter() - t0
@@ -225,6 +233,7 @@ def main(argv=None):
     ap.add_argument("--remove-color-info", action="store_true")
     ap.add_argument("--batched", action="store_true")
     ap.add_argument("--stateful", action="store_true", help="--batched: one planner's view of the recording (frames chain through the previous path)")
+    ap.add_argument("--cache", action="store_true", help="--batched --stateful: the planner has the reference's sorting cache on (fsdp_plan_sequence_cached)")
     ap.add_argument("--output-path", "-o", type=Path, default=None)
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--devices", type=str, default=None, help='--batched: GPUs the stream is sharded over from this process, e.g. "0,1,2,3" or "all"')
@@ -252,14 +261,17 @@ def main(argv=None):
                           "sides_with_a_runner_up": int(fin.size), "smallest_margin": float(fin.min()) if fin.size else None}))
         return
     if a.batched and a.experimental_performance_improvements:
-        ap.error("--experimental-performance-improvements is state of one planner: per-frame replay only (not with --batched)")
+        ap.error("--experimental-performance-improvements is state of one planner: per-frame replay, or --batched --stateful --cache")
+    if a.cache and not (a.batched and a.stateful):
+        ap.error("--cache goes with --batched --stateful (per-frame replay: --experimental-performance-improvements)")
     mission = select_mission_by_filename(a.data_path.name)
     positions, directions, observations = load_data_json(a.data_path, a.remove_color_info)
     out = {"file": str(a.data_path), "mission": mission.name, "frames": len(positions)}
     if a.batched:
         if a.stateful:
-            res, sec, again = replay_stateful_batched(mission, positions, directions, observations, a.device, batch_frames=a.batch_frames, depth=a.depth)
-            out.update(frames_planned_again_with_their_predecessors_path=again)
+            res, sec, again = replay_stateful_batched(mission, positions, directions, observations, a.device, batch_frames=a.batch_frames, depth=a.depth,
+                                                      cache=a.cache)
+            out.update(frames_planned_again_with_their_predecessors_path=again, sorting_cache=a.cache)
         else:
             devs = None if a.devices is None else ("all" if a.devices == "all" else [int(x) for x in a.devices.split(",")])
             res, sec = replay_batched(mission, positions, directions, observations, a.device, batch_frames=a.batch_frames, depth=a.depth, devices=devs)

@@ -243,7 +243,8 @@ int fsdp_plan_sequence_compact(fsdp_ctx* ctx, int n_planners, int n_steps, const
  *   fsdp_sort_cache_reset(ctx, n): n > 0 turns the cache on for n planners advanced in lock-step, all entries empty; 0 turns
  *   it off (the default).  A skidpad context returns an error.
  *   While it is on, fsdp_plan_batch_sequential (prev_paths NULL allowed: fresh path-stage history, the cache still applies)
- *   and fsdp_sort_batch take n_frames == n planners, frame i = planner i, and read and replace the planners' entries; a call
+ *   and fsdp_sort_batch take n_frames == n planners, frame i = planner i, and read and replace the planners' entries, and so
+ *   does fsdp_plan_sequence_cached[_compact] (below: n_steps such steps in one call); a call
  *   with another n_frames returns an error and leaves the cache as it was, and so does any failed call.  The chunked form of
  *   the blocking call (16 384+ frames) gives the same results.
  *   No other entry point reads or writes the cache: fsdp_plan_batch[_compact], fsdp_submit* / fsdp_collect, fsdp_upload /
@@ -254,6 +255,28 @@ int fsdp_plan_sequence_compact(fsdp_ctx* ctx, int n_planners, int n_steps, const
  *   no starting cone).  Returns an error while the cache is off. */
 int fsdp_sort_cache_reset(fsdp_ctx* ctx, int n_planners);
 int fsdp_sort_cache_hits(const fsdp_ctx* ctx, int8_t* out);
+
+/* fsdp_plan_sequence with the sorting cache on: layout, initial_prev, final_prev and n_replanned as above; the context must
+ * have the cache on for exactly n_planners planners (fsdp_sort_cache_reset(ctx, n_planners)).  The results are those of n_steps
+ * calls of fsdp_plan_batch_sequential on that context with the previous-path rows chained as fsdp_plan_sequence chains them —
+ * records, final_prev and n_replanned byte for byte.  The call reads the planners' current entries and leaves the entries the
+ * n_steps lock-step calls would leave, so lock-step calls and further sequence calls follow in any mix, and a recording cut
+ * into several calls gives the bytes of one call.
+ *   hits (or NULL): int8 (n_steps * n_planners, 2), the codes of fsdp_sort_cache_hits for every frame and side; afterwards
+ *   fsdp_sort_cache_hits returns the last step's.
+ *   n_resorted (or NULL): frames whose all-cones similarity had to be decided inside the in-order chain because the planner's
+ *   entry was older than the previous step (after a step the reference raised on, or a dropped entry).
+ * One pass: every frame is searched fresh on both sides in parallel (speculative instantiations of the sorting kernels), a
+ * wavefront per planner then walks the steps' few words in order, and the frames with a reused side are re-combined in
+ * parallel (csrc/sequence_cache_kernel.h); matching and the path stage run once, on the final sorting results.
+ * Returns an error, with nothing planned and the cache as it was: the cache off or on for another planner count; what
+ * fsdp_plan_sequence refuses otherwise.  A failed call leaves cache and context as they were. */
+int fsdp_plan_sequence_cached(fsdp_ctx* ctx, int n_planners, int n_steps, const int32_t* cone_offsets, const double* cones_xyt,
+                              const double* poses, const double* initial_prev, fsdp_frame_result* results, double* final_prev,
+                              long long* n_replanned, int8_t* hits /* or NULL */, long long* n_resorted /* or NULL */);
+int fsdp_plan_sequence_cached_compact(fsdp_ctx* ctx, int n_planners, int n_steps, const int32_t* cone_offsets, const double* cones_xyt,
+                                      const double* poses, const double* initial_prev, fsdp_compact_result* results, double* final_prev,
+                                      long long* n_replanned, int8_t* hits /* or NULL */, long long* n_resorted /* or NULL */);
 
 /* PathPlanner.set_global_path (full_pipeline.py:81-82) / the known path of a relocalized planner (:118-136): with a
  * global path (n,2) the path of every following frame is drawn from it (core_calculate_path.py:514-529: the part within
