@@ -479,22 +479,7 @@ class Context:
         successful paths.  initial_prev: (n_planners, <= path_points, 4) or None, a row starting with NaN = none (the fresh
         planner's initial path).  -> (results, final_prev (n_planners, path_points, 4) with NaN rows for planners that have no
         path yet, n_replanned = frames planned a second time on the device)."""
-        offsets, cones, poses, n = self._prep_any_base(cone_offsets, cones_xyt, poses)
-        n_planners = int(n_planners)
-        if n_planners < 1 or n < 1 or n % n_planners:
-            raise ValueError(f"plan_sequence: {n} frames are not a whole number (>= 1) of steps of {n_planners} planners")
-        init = None
-        if initial_prev is not None:
-            init = self.pad_paths(initial_prev)
-            assert len(init) == n_planners
-        out = np.zeros(n, dtype=self.compact_dtype if compact else self.result_dtype)
-        final = np.zeros((n_planners, self.shapes.path_points, 4))
-        again = ctypes.c_longlong(0)
-        fn = self._lib.fsdp_plan_sequence_compact if compact else self._lib.fsdp_plan_sequence
-        self._check(fn(self._h, n_planners, n // n_planners, offsets.ctypes.data, cones.ctypes.data if len(cones) else None, poses.ctypes.data,
-                       None if init is None else init.ctypes.data, out.ctypes.data, final.ctypes.data, ctypes.byref(again)), "fsdp_plan_sequence")
-        self.n_frames = n
-        return out, final, int(again.value)
+        return self._plan_sequence(cone_offsets, cones_xyt, poses, int(n_planners), initial_prev, compact, cached=False)[:3]
 
     def plan_sequence_cached(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False):
         """fsdp_plan_sequence_cached: plan_sequence on a context whose sorting cache is on for exactly n_planners planners
@@ -505,9 +490,14 @@ class Context:
         if getattr(self, "n_cache", 0) != n_planners or n_planners < 1:
             raise RuntimeError(f"plan_sequence_cached: the sorting cache is on for {getattr(self, 'n_cache', 0)} planners, the call holds "
                                f"{n_planners} (sort_cache_reset(n_planners) turns it on)")
+        return self._plan_sequence(cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact, cached=True)
+
+    def _plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact, cached):
+        """fsdp_plan_sequence[_cached][_compact] -> (results, final_prev, n_replanned, hits, n_resorted), the last two of a cached call"""
+        who = "plan_sequence_cached" if cached else "plan_sequence"
         offsets, cones, poses, n = self._prep_any_base(cone_offsets, cones_xyt, poses)
-        if n < 1 or n % n_planners:
-            raise ValueError(f"plan_sequence_cached: {n} frames are not a whole number (>= 1) of steps of {n_planners} planners")
+        if n_planners < 1 or n < 1 or n % n_planners:
+            raise ValueError(f"{who}: {n} frames are not a whole number (>= 1) of steps of {n_planners} planners")
         init = None
         if initial_prev is not None:
             init = self.pad_paths(initial_prev)
@@ -516,10 +506,10 @@ class Context:
         final = np.zeros((n_planners, self.shapes.path_points, 4))
         hits = np.zeros((n, 2), dtype=np.int8)
         again, resorted = ctypes.c_longlong(0), ctypes.c_longlong(0)
-        fn = self._lib.fsdp_plan_sequence_cached_compact if compact else self._lib.fsdp_plan_sequence_cached
+        fn = getattr(self._lib, f"fsdp_{who}_compact" if compact else f"fsdp_{who}")
         self._check(fn(self._h, n_planners, n // n_planners, offsets.ctypes.data, cones.ctypes.data if len(cones) else None, poses.ctypes.data,
-                       None if init is None else init.ctypes.data, out.ctypes.data, final.ctypes.data, ctypes.byref(again), hits.ctypes.data,
-                       ctypes.byref(resorted)), "fsdp_plan_sequence_cached")
+                       None if init is None else init.ctypes.data, out.ctypes.data, final.ctypes.data, ctypes.byref(again),
+                       *((hits.ctypes.data, ctypes.byref(resorted)) if cached else ())), f"fsdp_{who}")
         self.n_frames = n
         return out, final, int(again.value), hits, int(resorted.value)
 

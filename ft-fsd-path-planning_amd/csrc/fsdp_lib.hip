@@ -466,9 +466,8 @@ static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
   return v;
 }
 
-// fsdp_plan_sequence_cached: what sequence_cache_lib.hip's launches need (the kernels read cache buffer cache_cur, write the other)
-static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs& in, bool small) {
-  const int p = c->cache_cur, x = 1 - p;
+// fsdp_plan_sequence_cached: what sequence_cache_lib.hip's launches need, once per pass (launch_pass)
+static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs& in) {
   fsdp_seqc_launch_args a;
   a.n_planners = c->sequence->n_planners;
   a.n_steps = c->sequence->n_steps;
@@ -477,18 +476,12 @@ static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs&
   a.poses = in.d_poses;
   a.sorted = q.d_sort;
   a.big = q.d_big;
-  a.big_state = q.d_sort_big;
+  a.big_state = nullptr;  // (launch_sort_big allocates the blocks on first use)
   a.big_blocks = SORT_BIG_BLOCKS;
-  a.small = small;
+  a.small = sort128(c, in);
   a.prm = c->d_params;
   a.rec = q.d_seqc_rec;
-  a.prev = c->d_cache_hdr[p];
-  a.next = c->d_cache_hdr[x];
-  a.prev_xyt = c->d_cache_xyt[p];
-  a.prev_off = c->d_cache_off[p];
-  a.next_xyt = c->d_cache_xyt[x];
-  a.next_off = c->d_cache_off[x];
-  a.last_hits = c->d_cache_hits;
+  a.cache = cache_view(c, q);
   a.hits = q.d_seqc_hits;
   a.resorted = q.d_seqc_resorted;
   return a;
@@ -496,11 +489,13 @@ static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs&
 static bool seq_cached(const fsdp_ctx* c) { return c->sequence && c->sequence->cached; }
 
 // Which instantiation of the three sorting kernels (sort_kernel_128 | sort_kernel, sort_big_kernel) a launch takes: the ranked one
-// for fsdp_sort_batch_ranked, else the cached one while a call advances the sorting cache (c->cache_call), else the plain one
+// for fsdp_sort_batch_ranked, else the cached one while a call advances the sorting cache (c->cache_call), else the speculative one
+// for a pass of fsdp_plan_sequence_cached, else the plain one
 struct SortVariant {
   const SortRankView* rank = nullptr;     // ranked: where the rows go ...
   SortRankScratchBig* scratch = nullptr;  // ... and sort_big_kernel_ranked's block for the cost terms (SORT_BIG_BLOCKS of them)
-  const char* suffix(const fsdp_ctx* c) const { return rank ? "_ranked" : (c->cache_call ? "_cached" : (seq_cached(c) ? "_spec" : "")); }
+  fsdp_seqc_launch_args* seqc = nullptr;  // speculative: the pass's launch arguments (seqc_args)
+  const char* suffix(const fsdp_ctx* c) const { return rank ? "_ranked" : (c->cache_call ? "_cached" : (seqc ? "_spec" : "")); }
 };
 
 // Both launches append the name of the kernel they took to `names` (fsdp_stage_names).
@@ -514,10 +509,9 @@ static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& s
   else if (c->cache_call)
     hipLaunchKernelGGL((small ? sort_kernel_128_cached : sort_kernel_cached), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
                        in.d_poses, q.d_sort, q.d_big, c->d_params, st, cache_view(c, q));
-  else if (seq_cached(c)) {
-    const fsdp_seqc_launch_args a = seqc_args(c, q, in, small);
-    fsdp_seqc_launch_sort(q.stream, &a);
-  } else
+  else if (var.seqc)
+    fsdp_seqc_launch_sort(q.stream, var.seqc);
+  else
     hipLaunchKernelGGL((small ? sort_kernel_128 : sort_kernel), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
                        q.d_sort, q.d_big, c->d_params, st);
   names += std::string(small ? "sort_kernel_128" : "sort_kernel") + var.suffix(c);
@@ -531,9 +525,9 @@ static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in, std::string& 
   else if (c->cache_call)
     hipLaunchKernelGGL(sort_big_kernel_cached, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
                        c->d_params, cache_view(c, q));
-  else if (seq_cached(c)) {
-    const fsdp_seqc_launch_args a = seqc_args(c, q, in, false);
-    fsdp_seqc_launch_sort_big(q.stream, &a);
+  else if (var.seqc) {
+    var.seqc->big_state = q.d_sort_big;
+    fsdp_seqc_launch_sort_big(q.stream, var.seqc);
   } else
     hipLaunchKernelGGL(sort_big_kernel, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
                        c->d_params);
@@ -790,17 +784,22 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io
     (void)hipMemsetAsync(q.d_big + 1, 0xff, sizeof(int) * m, q.stream);
     (void)hipMemsetAsync(q.d_retry + 1, 0xff, sizeof(int) * m, q.stream);
   }
+  fsdp_seqc_launch_args seqc;
+  SortVariant var;
+  if (seq_cached(c)) {
+    seqc = seqc_args(c, q, in);
+    var.seqc = &seqc;
+  }
   mark(q, t);
-  launch_sort(c, q, in, io.stage, names);
+  launch_sort(c, q, in, io.stage, names, var);
   names += ',';
   if (with_big) {
     mark(q, t);
-    if (int rc = launch_sort_big(c, q, in, names)) return rc;
+    if (int rc = launch_sort_big(c, q, in, names, var)) return rc;
     names += ',';
   }
-  if (seq_cached(c)) {  // (fsdp_plan_sequence_cached: the sorting results become those of the cache-on lock-step calls)
-    const fsdp_seqc_launch_args a = seqc_args(c, q, in, false);
-    fsdp_seqc_launch_chain(q.stream, &a);
+  if (var.seqc) {  // (fsdp_plan_sequence_cached: the sorting results become those of the cache-on lock-step calls)
+    fsdp_seqc_launch_chain(q.stream, &seqc);
     names += "seq_cache_mark_kernel,seq_cache_resolve_kernel,";
   }
   mark(q, t);
@@ -1714,6 +1713,29 @@ int fsdp_route_stats(fsdp_ctx* c, int* expect_big, int* expect_retry, long long*
 // (tests), 1 = never.
 constexpr int PLAN_CHUNKS = 4, PLAN_CHUNK_FROM = 16384, PLAN_CHUNK_MIN = 512;
 
+// The internal ticket of a blocking call: batch b as ticket 0 of slot q, planned for in_flight frames on the GPU.  0: issued as
+// q.tk[0].id — the caller collects it and gives the number back (c->next_ticket: the caller's own tickets keep counting up from
+// where they were).  Else nothing of the batch is left running over the caller's buffers and no ticket went out.
+static int issue_blocking(fsdp_ctx* c, Work& q, const Batch& b, long long in_flight, fsdp_frame_result* results, bool compact) {
+  Work::Ticket& t = q.tk[0];
+  t.batch = b;
+  t.skid = false;
+  t.in_flight = in_flight;
+  t.user_results = results;
+  t.user_info = nullptr;
+  t.compact = compact;
+  if (int rc = enqueue_ticket(c, q, t, false)) {
+    (void)hipStreamSynchronize(q.stream);
+    (void)hipGetLastError();
+    t.user_results = nullptr;
+    t.compact = false;
+    return rc;
+  }
+  t.id = c->next_ticket++;
+  c->outstanding++;
+  return 0;
+}
+
 static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev,
                          fsdp_frame_result* results, bool compact, bool sequential = false) {
   if (!c) return 1;
@@ -1741,24 +1763,10 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
   for (int k = 0; k < chunks && rc == 0; k++) {
     const int lo = (int)((long long)n_frames * k / chunks), hi = (int)((long long)n_frames * (k + 1) / chunks);
     Work& q = c->slot[k];  // (slots beyond the overlap depth get their stream here: a chunk is a pass in flight)
-    Work::Ticket& t = q.tk[0];
     if ((rc = ensure_work(c, q, hi - lo))) break;
     q.cache_base = lo;  // (the chunk's frames are planners lo..hi-1 of the sorting cache)
-    t.batch = b.slice(lo, hi);
-    t.skid = false;
-    t.in_flight = n_frames;
-    t.user_results = (fsdp_frame_result*)((char*)results + rec * (size_t)lo);
-    t.user_info = nullptr;
-    t.compact = compact;
-    if ((rc = enqueue_ticket(c, q, t, false))) {
-      (void)hipStreamSynchronize(q.stream);
-      (void)hipGetLastError();
-      t.user_results = nullptr;
-      t.compact = false;
-      break;
-    }
-    t.id = ids[issued++] = c->next_ticket++;
-    c->outstanding++;
+    if ((rc = issue_blocking(c, q, b.slice(lo, hi), n_frames, (fsdp_frame_result*)((char*)results + rec * (size_t)lo), compact))) break;
+    ids[issued++] = q.tk[0].id;
   }
   for (int k = 0; k < issued; k++) {
     const int rck = fsdp_collect(c, ids[k]);  // (every issued chunk is waited for, also after an error: the buffers are the caller's again)
@@ -1844,7 +1852,7 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
   if (int rc = sync_all(c)) return rc;
   c->last = fsdp_ctx::LastPass();
   Work& q = c->slot[0];
-  Work::Ticket& t = q.tk[0];
+  q.cache_base = 0;  // (frame f is planner f % n_planners: seq_cache_mark_kernel takes the view as it is)
   // a frame count the device has no room for is an error code: whatever was replaced on the way is replaced again next time
   auto no_room = [&](int rc) {
     q.cap_frames = q.in.cap_frames = q.in.cap_prev = 0;
@@ -1854,44 +1862,30 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
     return rc;
   };
   if (int rc = ensure_work(c, q, n)) return no_room(rc);
-  if ((size_t)n > q.seq_cap_frames) {
-    if (hipError_t e = regrow(q.d_seq, (size_t)SEQ_LIST + 2 * (size_t)n)) {
-      c->err = std::string("fsdp_plan_sequence: ") + hipGetErrorString(e);
-      return no_room(2);
-    }
-    q.seq_cap_frames = (size_t)n;
-  }
-  if ((size_t)n_planners > q.seq_cap_planners) {
-    hipError_t e = regrow(q.d_seq_init, (size_t)PATH_POINTS * 4 * (size_t)n_planners);
-    if (e == hipSuccess) e = regrow(q.d_seq_final, (size_t)PATH_POINTS * 4 * (size_t)n_planners);
-    if (e != hipSuccess) {
-      c->err = std::string("fsdp_plan_sequence: ") + hipGetErrorString(e);
-      return no_room(2);
-    }
-    q.seq_cap_planners = (size_t)n_planners;
-  }
+  // `count` elements behind p where the slot has had room for `cap` < `want` frames (or planners) so far; false: out of memory
+  auto grown = [&](auto*& p, size_t cap, size_t want, size_t count) {
+    if (want <= cap) return true;
+    const hipError_t e = regrow(p, count);
+    if (e != hipSuccess) c->err = who + ": " + hipGetErrorString(e);
+    return e == hipSuccess;
+  };
+  const size_t nf = (size_t)n, np = (size_t)n_planners, prev_doubles = (size_t)PATH_POINTS * 4 * np;
+  if (!grown(q.d_seq, q.seq_cap_frames, nf, (size_t)SEQ_LIST + 2 * nf) || !grown(q.d_seq_init, q.seq_cap_planners, np, prev_doubles) ||
+      !grown(q.d_seq_final, q.seq_cap_planners, np, prev_doubles))
+    return no_room(2);
+  q.seq_cap_frames = std::max(q.seq_cap_frames, nf);
+  q.seq_cap_planners = std::max(q.seq_cap_planners, np);
   if (cached) {
-    if ((size_t)n > q.seqc_cap_frames) {
-      hipError_t e = regrow(q.d_seqc_rec, (size_t)n);
-      if (e == hipSuccess) e = regrow(q.d_seqc_hits, 2 * (size_t)n);
-      if (e != hipSuccess) {
-        c->err = who + ": " + hipGetErrorString(e);
-        return no_room(2);
-      }
-      q.seqc_cap_frames = (size_t)n;
-    }
-    if ((size_t)n_planners > q.seqc_cap_planners) {
-      if (hipError_t e = regrow(q.d_seqc_resorted, (size_t)n_planners)) {
-        c->err = who + ": " + hipGetErrorString(e);
-        return no_room(2);
-      }
-      q.seqc_cap_planners = (size_t)n_planners;
-    }
+    if (!grown(q.d_seqc_rec, q.seqc_cap_frames, nf, nf) || !grown(q.d_seqc_hits, q.seqc_cap_frames, nf, 2 * nf) ||
+        !grown(q.d_seqc_resorted, q.seqc_cap_planners, np, np))
+      return no_room(2);
+    q.seqc_cap_frames = std::max(q.seqc_cap_frames, nf);
+    q.seqc_cap_planners = std::max(q.seqc_cap_planners, np);
     // the buffer the call writes gets room for every planner's largest frame of the sequence (cache_prepare, step by step)
     for (int s = 0; s < n_steps; s++)
       if (int rc = cache_prepare(c, n_planners, off + (size_t)s * n_planners, who.c_str())) return rc;
   }
-  const size_t prev_bytes = sizeof(double) * PATH_POINTS * 4 * (size_t)n_planners;
+  const size_t prev_bytes = sizeof(double) * prev_doubles;
   if (initial_prev) HIP_TRY(c, hipMemcpyAsync(q.d_seq_init, initial_prev, prev_bytes, hipMemcpyHostToDevice, q.stream));
   fsdp_ctx::Sequence sq;
   sq.n_planners = n_planners;
@@ -1903,21 +1897,8 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
     ~Scope() { c->sequence = nullptr; }
   } scope{c};
   c->sequence = &sq;
-  t.batch = b;
-  t.skid = false;
-  t.in_flight = n;
-  t.user_results = results;
-  t.user_info = nullptr;
-  t.compact = compact;
-  if (int rc = enqueue_ticket(c, q, t, false)) {
-    (void)hipStreamSynchronize(q.stream);
-    t.user_results = nullptr;
-    t.compact = false;
-    return no_room(rc);
-  }
-  t.id = c->next_ticket++;
-  c->outstanding++;
-  int rc = fsdp_collect(c, t.id);  // (waits; runs the pass again, chain kernels included, if it lacked a route)
+  if (int rc = issue_blocking(c, q, b, n, results, compact)) return no_room(rc);
+  int rc = fsdp_collect(c, q.tk[0].id);  // (waits; runs the pass again, chain kernels included, if it lacked a route)
   c->next_ticket--;                // (the number was internal, like plan_blocking's)
   if (rc != 0) return rc;
   if (n_replanned) *n_replanned = __atomic_load_n(&q.h_trailer[0].pad, __ATOMIC_RELAXED);

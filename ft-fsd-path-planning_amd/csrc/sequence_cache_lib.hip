@@ -12,9 +12,9 @@ static fsdp::SeqSpecView spec_view(const fsdp_seqc_launch_args* a) {
   fsdp::SeqSpecView v;
   v.rec = a->rec;
   v.n_planners = a->n_planners;
-  v.prev = a->prev;
-  v.prev_xyt = a->prev_xyt;
-  v.prev_off = a->prev_off;
+  v.prev = a->cache.prev;
+  v.prev_xyt = a->cache.prev_xyt;
+  v.prev_off = a->cache.prev_off;
   return v;
 }
 
@@ -34,16 +34,8 @@ extern "C" void fsdp_seqc_launch_sort_big(hipStream_t stream, const fsdp_seqc_la
 extern "C" void fsdp_seqc_launch_chain(hipStream_t stream, const fsdp_seqc_launch_args* a) {
   using namespace fsdp;
   const int n = a->n_planners * a->n_steps;
-  SortCacheView v;
-  v.prev = a->prev;
-  v.next = a->next;
-  v.prev_xyt = a->prev_xyt;
-  v.prev_off = a->prev_off;
-  v.next_xyt = a->next_xyt;
-  v.next_off = a->next_off;
-  v.hits = a->last_hits;
   hipLaunchKernelGGL(seq_cache_mark_kernel, dim3((unsigned)a->n_planners), dim3(WAVE), 0, stream, a->n_planners, a->n_steps, a->off, a->cones,
-                     a->rec, v, a->hits, a->resorted);
+                     a->rec, a->cache, a->hits, a->resorted);
   hipLaunchKernelGGL(seq_cache_resolve_kernel, dim3((unsigned)n), dim3(WAVE), 0, stream, n, a->n_planners, a->off, a->cones,
-                     (const SeqSpecRec*)a->rec, a->prev, a->sorted);
+                     (const SeqSpecRec*)a->rec, a->cache.prev, a->sorted);
 }

@@ -8,13 +8,12 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include "sort_cache.h"  // SortCacheView, SeqSpecRec
+
 namespace fsdp {
 struct MatchOut;
 struct PathOut;
 struct SortOut;
-struct Params;
-struct SortCacheHdr;
-struct SeqSpecRec;
 // the list block of a sequence pass: [0] heads appended, [1] frames planned again (a 16-byte header, zeroed by one memset per
 // pass), then (frame, predecessor) per head: SEQ_LIST + 2 * frames ints
 constexpr int SEQ_HEADS = 0, SEQ_REPLANNED = 1, SEQ_LIST = 4;
@@ -53,14 +52,7 @@ struct fsdp_seqc_launch_args {
   bool small;           // no frame holds more than 128 cones
   const fsdp::Params* prm;
   fsdp::SeqSpecRec* rec;  // (frames)
-  // the two buffers of the sorting cache: the call reads `prev`, writes `next`
-  const fsdp::SortCacheHdr* prev;
-  fsdp::SortCacheHdr* next;
-  const double* prev_xyt;
-  const int32_t* prev_off;
-  double* next_xyt;
-  const int32_t* next_off;
-  int8_t* last_hits;   // (planners, 2)
+  fsdp::SortCacheView cache;  // the call reads `prev`, writes `next` and, for the last step, `hits`; base 0: frame f is planner f % n_planners
   int8_t* hits;        // (frames, 2)
   int32_t* resorted;   // (planners)
 };

@@ -1,11 +1,11 @@
 // TEST INFRASTRUCTURE — the chain kernels of a sequence pass (csrc/sequence_kernel.h: seq_mark_kernel, seq_chain_kernel,
 // seq_final_kernel) under the host SIMT emulator, launched the way the library's launch_sequence launches them behind the path
-// stage (csrc/fsdp_lib.hip).  A library of its own (sequence.mk: libfsdp_emu_sequence[_wide].so), linked against libfsdp_emu[_wide].so,
-// whose parameters it reads (emu_kernels.cpp g_prm, emu_shared.h).  Never loaded by the package.
+// stage (csrc/fsdp_lib.hip).  A translation unit of libfsdp_emu[_wide].so like emu_ranked.cpp; the parameters come from emu_kernels.cpp
+// (g_prm, emu_shared.h), and path_kernel.h's kernels, which that unit compiles too, are weak (hip_emu.h).  Never loaded by the package.
 #include "emu_shared.h"
 
 #include "../../ft-fsd-path-planning_amd/csrc/match_kernel.h"
-#include "../../ft-fsd-path-planning_amd/csrc/sequence_kernel.h"  // (sequence_launch.h needs nothing but the HIP types hip_emu.h stands in for)
+#include "../../ft-fsd-path-planning_amd/csrc/sequence_kernel.h"
 
 #include <cstdlib>
 

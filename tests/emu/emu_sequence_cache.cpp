@@ -1,8 +1,8 @@
 // TEST INFRASTRUCTURE — the sorting side of a fsdp_plan_sequence_cached pass (csrc/sequence_cache_kernel.h: the speculative
 // instantiations of the three sorting kernels, seq_cache_mark_kernel, seq_cache_resolve_kernel) under the host SIMT emulator,
-// launched the way the library launches them (csrc/sequence_cache_lib.hip), planners starting from empty cache entries.  A library
-// of its own (sequence_cache.mk: libfsdp_emu_sequence_cache[_wide].so), linked against libfsdp_emu[_wide].so, whose parameters,
-// sort128 switch and filter it shares (emu_shared.h).  Never loaded by the package.
+// launched the way the library launches them (csrc/sequence_cache_lib.hip), planners starting from empty cache entries.  A
+// translation unit of libfsdp_emu[_wide].so like emu_ranked.cpp; parameters, sort128 switch and filter come from emu_kernels.cpp
+// (emu_shared.h).  Never loaded by the package.
 #include "emu_shared.h"
 
 #include "../../ft-fsd-path-planning_amd/csrc/sequence_cache_kernel.h"

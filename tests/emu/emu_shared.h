@@ -1,4 +1,5 @@
-// TEST INFRASTRUCTURE — what the emulator's translation units share: emu_kernels.cpp defines it, emu_ranked.cpp uses it too.
+// TEST INFRASTRUCTURE — what the emulator's translation units share: emu_kernels.cpp defines it; emu_ranked.cpp, emu_sequence.cpp
+// and emu_sequence_cache.cpp use it too.
 #pragma once
 #include "hip_emu.h"
 

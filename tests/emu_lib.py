@@ -139,15 +139,20 @@ def default_path():
 def plan(offsets, cones, poses, group=8):
     """Full emulated pipeline; returns a structured array shaped like oracle_lib.RESULT_DTYPE.  group = lanes per frame
     of the path kernel (8: eight frames per wavefront, 16, or 64: one frame per wavefront)."""
+    s = sort(offsets, cones, poses)
+    m = match(offsets, cones, poses, s)
+    lib().emu_sort_remap(ctypes.c_int(len(s)), ctypes.c_void_p(s.ctypes.data))  # (use_unknown_cones = False: indices back to the caller's array)
+    p = path(poses, m, group)
+    return records(s, m, p), p["n_dense"]
+
+
+def records(s, m, p):
+    """The sort, match and path records of the same frames as one structured array shaped like oracle_lib.RESULT_DTYPE."""
     if WIDE_SHAPES:
         import oracle_lib_wide as oracle_lib
     else:
         import oracle_lib
 
-    s = sort(offsets, cones, poses)
-    m = match(offsets, cones, poses, s)
-    lib().emu_sort_remap(ctypes.c_int(len(s)), ctypes.c_void_p(s.ctypes.data))  # (use_unknown_cones = False: indices back to the caller's array)
-    p = path(poses, m, group)
     res = np.zeros(len(s), oracle_lib.RESULT_DTYPE)
     for k in ("n_left", "n_right", "left_idx", "right_idx", "n_configs_left", "n_configs_right", "first_k_left",
               "first_k_right", "best_cost_left", "best_cost_right"):
@@ -160,7 +165,48 @@ def plan(offsets, cones, poses, group=8):
     st = np.where(m["status"] != 0, m["status"], st)
     st = np.where(p["status"] != 0, p["status"], st)
     res["status"] = st
-    return res, p["n_dense"]
+    return res
+
+
+# ---- the kernels of fsdp_plan_sequence[_cached] (tests/emu/emu_sequence.cpp, emu_sequence_cache.cpp); frames step-major ----
+def sequence_mark(n_planners, status, fallback):
+    """seq_mark_kernel over injected status / fallback words -> sorted list of (head frame, predecessor frame or -1)"""
+    status = np.ascontiguousarray(status, np.int32)
+    fallback = np.ascontiguousarray(fallback, np.int32)
+    n = len(status)
+    heads = np.zeros(2 * n + 2, np.int32)
+    k = lib().emu_sequence_mark(ctypes.c_int(n_planners), ctypes.c_int(n // n_planners), _p(status, ctypes.c_int32), _p(fallback, ctypes.c_int32),
+                                _p(heads, ctypes.c_int32))
+    return sorted((int(heads[2 * j]), int(heads[2 * j + 1])) for j in range(k))
+
+
+def sequence_chain(n_planners, poses, matched, paths, initial_prev=None, blocks=8):
+    """seq_mark -> seq_chain (grid `blocks`) -> seq_final over `paths`, the path records of a pass planned without previous paths,
+    resolved in place; initial_prev: (n_planners, <= PATH_POINTS, 4) or None -> (final_prev, frames planned again)"""
+    poses = np.ascontiguousarray(poses, np.float64)
+    init = None
+    if initial_prev is not None:
+        init = np.full((n_planners, PATH_POINTS, 4), np.nan)
+        init[:, : np.shape(initial_prev)[1]] = initial_prev
+    final = np.zeros((n_planners, PATH_POINTS, 4))
+    again = lib().emu_sequence_chain(ctypes.c_int(n_planners), ctypes.c_int(len(poses) // n_planners), _p(poses), ctypes.c_void_p(matched.ctypes.data),
+                                     None if init is None else _p(init), ctypes.c_void_p(paths.ctypes.data), _p(final), ctypes.c_int(blocks))
+    return final, int(again)
+
+
+def sequence_cache(n_planners, offsets, cones, poses):
+    """speculative sort -> [big] -> seq_cache_mark -> seq_cache_resolve, planners with empty entries ->
+    (SortOut records, hits (frames, 2), n_resorted, kernels bit mask, frames of the big route)"""
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    cones = np.ascontiguousarray(cones, np.float64)
+    poses = np.ascontiguousarray(poses, np.float64)
+    n = len(poses)
+    out = np.zeros(n, SORT_DTYPE)
+    hits = np.zeros((n, 2), np.int8)
+    resorted, kernels = ctypes.c_longlong(-1), ctypes.c_int(0)
+    big = lib().emu_sequence_cache(ctypes.c_int(n_planners), ctypes.c_int(n // n_planners), _p(offsets, ctypes.c_int32), _p(cones), _p(poses),
+                                   ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(hits.ctypes.data), ctypes.byref(resorted), ctypes.byref(kernels))
+    return out, hits, int(resorted.value), int(kernels.value), int(big)
 
 
 SKID_STATE_DTYPE = np.dtype(

@@ -1,33 +1,18 @@
-"""TEST INFRASTRUCTURE of fsdp_plan_sequence_cached (csrc/sequence_cache_kernel.h): the ctypes loader of the emulated pass
-(tests/emu/emu_sequence_cache.cpp, tests/emu/sequence_cache.mk), the lock-step expectation — sequence_support.lockstep around
+"""TEST INFRASTRUCTURE of fsdp_plan_sequence_cached (csrc/sequence_cache_kernel.h): the emulated pass (emu_lib's wrapper of
+tests/emu/emu_sequence_cache.cpp), the lock-step expectation — sequence_support.lockstep around
 plan_batch_sequential on a second cache-on context, which also collects sort_cache_hits() per step — and the inputs the CPU and GPU
 tests share."""
 from __future__ import annotations
 
 import ctypes
 import json
-import subprocess
 from importlib import import_module
-from pathlib import Path
 
 import numpy as np
 
 import sequence_support as ss
 
 FIXTURES = ["mapped", "lockstep", "no_unknown", "big", "lockstep_wide"]  # (under the emulator; the GPU adds colourless and wide)
-
-_libs = {}
-
-
-def cache_lib(wide: bool = False):
-    """tests/emu/libfsdp_emu_sequence_cache[_wide].so, linked against the emulator library of the same shapes (loaded first)"""
-    if wide not in _libs:
-        ss.emu(wide).lib()
-        emu_dir = Path(__file__).resolve().parent / "emu"
-        subprocess.run(["make", "-s", "-C", str(emu_dir), "-f", "sequence_cache.mk"], check=True)
-        _libs[wide] = ctypes.CDLL(str(emu_dir / ("libfsdp_emu_sequence_cache_wide.so" if wide else "libfsdp_emu_sequence_cache.so")))
-    return _libs[wide]
-
 
 def load(golden_dir, name):
     g = dict(np.load(golden_dir / f"sort_cache_{name}.npz"))
@@ -38,21 +23,7 @@ def load(golden_dir, name):
 
 
 def emu_sequence_cache(offsets, cones, poses, n_planners, wide=False):
-    """speculative sort -> [big] -> seq_cache_mark -> seq_cache_resolve under the emulator, planners with empty entries ->
-    (SortOut records, hits (frames, 2), n_resorted, kernels bit mask, frames of the big route)"""
-    e = ss.emu(wide)
-    offsets = np.ascontiguousarray(offsets, np.int32)
-    cones = np.ascontiguousarray(cones, np.float64)
-    poses = np.ascontiguousarray(poses, np.float64)
-    n = len(poses)
-    lib = cache_lib(wide)
-    out = np.zeros(n, e.SORT_DTYPE)
-    hits = np.zeros((n, 2), np.int8)
-    resorted, kernels = ctypes.c_longlong(-1), ctypes.c_int(0)
-    big = lib.emu_sequence_cache(ctypes.c_int(n_planners), ctypes.c_int(n // n_planners), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                 ss._dp(cones), ss._dp(poses), ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(hits.ctypes.data),
-                                 ctypes.byref(resorted), ctypes.byref(kernels))
-    return out, hits, int(resorted.value), int(kernels.value), int(big)
+    return ss.emu(wide).sequence_cache(n_planners, offsets, cones, poses)
 
 
 def default_path(ctx):

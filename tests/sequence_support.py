@@ -1,12 +1,10 @@
-"""TEST INFRASTRUCTURE of fsdp_plan_sequence (csrc/sequence_kernel.h): the ctypes loader of the emulator's chain kernels
-(tests/emu/emu_sequence.cpp, tests/emu/sequence.mk), the host restatement of the chain rule — which IS the T lock-step calls of plan_batch_sequential —
+"""TEST INFRASTRUCTURE of fsdp_plan_sequence (csrc/sequence_kernel.h): the emulated pass (emu_lib's wrappers of
+tests/emu/emu_sequence.cpp), the host restatement of the chain rule — which IS the T lock-step calls of plan_batch_sequential —
 and of the run-head rule, and the inputs the CPU and GPU tests share."""
 from __future__ import annotations
 
 import ctypes
-import subprocess
 from importlib import import_module
-from pathlib import Path
 
 import numpy as np
 
@@ -16,24 +14,6 @@ ST_RETRY = 299  # csrc/fsdp_device.h
 
 def emu(wide: bool = False):
     return import_module("emu_lib_wide" if wide else "emu_lib")
-
-
-_seq_libs = {}
-
-
-def seq_lib(wide: bool = False):
-    """tests/emu/libfsdp_emu_sequence[_wide].so (tests/emu/sequence.mk): emu_sequence.cpp, linked against the emulator library of
-    the same shapes, which is loaded first so that both see one set of parameters"""
-    if wide not in _seq_libs:
-        emu(wide).lib()
-        emu_dir = Path(__file__).resolve().parent / "emu"
-        subprocess.run(["make", "-s", "-C", str(emu_dir), "-f", "sequence.mk"], check=True)
-        _seq_libs[wide] = ctypes.CDLL(str(emu_dir / ("libfsdp_emu_sequence_wide.so" if wide else "libfsdp_emu_sequence.so")))
-    return _seq_libs[wide]
-
-
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 # ---- the chain rule on the host ---------------------------------------------------------------------------------------------
@@ -90,13 +70,7 @@ def host_heads(status, fallback, n_planners):
 
 
 def emu_heads(status, fallback, n_planners, wide=False):
-    status = np.ascontiguousarray(status, np.int32)
-    fallback = np.ascontiguousarray(fallback, np.int32)
-    n = len(status)
-    heads = np.zeros(2 * n + 2, np.int32)
-    k = seq_lib(wide).emu_sequence_mark(ctypes.c_int(n_planners), ctypes.c_int(n // n_planners), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                           fallback.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), heads.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-    return sorted((int(heads[2 * j]), int(heads[2 * j + 1])) for j in range(k))
+    return emu(wide).sequence_mark(n_planners, status, fallback)
 
 
 # ---- the emulated pass ------------------------------------------------------------------------------------------------------
@@ -105,33 +79,13 @@ def emu_plan_sequence(offsets, cones, poses, n_planners, initial_prev=None, grou
     `group`, emu_lib.PATH_GROUP_SIZES) -> seq_mark -> seq_chain -> seq_final.  -> (records like emu_lib.plan's, final_prev,
     n_replanned)."""
     e = emu(wide)
-    oracle = import_module("oracle_lib_wide" if wide else "oracle_lib")
-    offsets = np.ascontiguousarray(offsets, np.int32)
-    cones = np.ascontiguousarray(cones, np.float64)
-    poses = np.ascontiguousarray(poses, np.float64)
-    n = len(poses)
     e.lib().emu_set_prev_paths(None)
     s = e.sort(offsets, cones, poses)
     m = e.match(offsets, cones, poses, s)
-    e.lib().emu_sort_remap(ctypes.c_int(n), ctypes.c_void_p(s.ctypes.data))
+    e.lib().emu_sort_remap(ctypes.c_int(len(s)), ctypes.c_void_p(s.ctypes.data))
     p = e.path(poses, m, group)
-    init = None
-    if initial_prev is not None:
-        init = np.full((n_planners, e.PATH_POINTS, 4), np.nan)
-        init[:, : np.shape(initial_prev)[1]] = initial_prev
-    final = np.zeros((n_planners, e.PATH_POINTS, 4))
-    again = seq_lib(wide).emu_sequence_chain(ctypes.c_int(n_planners), ctypes.c_int(n // n_planners), _dp(poses), ctypes.c_void_p(m.ctypes.data),
-                                       None if init is None else _dp(init), ctypes.c_void_p(p.ctypes.data), _dp(final), ctypes.c_int(blocks))
-    res = np.zeros(n, oracle.RESULT_DTYPE)
-    for k in ("n_left", "n_right", "left_idx", "right_idx", "n_configs_left", "n_configs_right", "first_k_left", "first_k_right", "best_cost_left",
-              "best_cost_right"):
-        res[k] = s[k]
-    for k in ("n_left_v", "n_right_v", "left_v", "right_v", "l2r", "r2l"):
-        res[k] = m[k]
-    res["path"], res["path_fallback"] = p["path"], p["fallback"]
-    st = np.where(m["status"] != 0, m["status"], s["status"])
-    res["status"] = np.where(p["status"] != 0, p["status"], st)
-    return res, final, int(again)
+    final, again = e.sequence_chain(n_planners, poses, m, p, initial_prev, blocks)
+    return e.records(s, m, p), final, again
 
 
 def oracle_step(offsets, cones, poses, prev):

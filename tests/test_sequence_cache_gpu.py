@@ -2,6 +2,7 @@
 fsdp_plan_batch_sequential, chained by sequence_support.lockstep) — the reference's captures, a raising step inside a run, drift
 against the run head, continuation across calls in any mix, the regimes of a fleet, refusals that leave the cache alone, the
 planner object, determinism."""
+import ctypes
 import importlib
 
 import numpy as np
@@ -64,6 +65,41 @@ def test_fixture_equals_lockstep_and_reference(golden_dir, name):
         both_ok = (res["status"] == 0) & (plain["status"] == 0)
         h = ctx.horizon  # (rows beyond the horizon are NaN)
         assert (np.abs(res["path"][both_ok][:, :h] - plain["path"][both_ok][:, :h]).max(axis=(1, 2)) > PATH_TOL).any()
+
+
+def stage_string(ctx):
+    buf = ctypes.create_string_buffer(512)
+    assert ctx._lib.fsdp_stage_names(ctx._h, buf, 512) == 0
+    return buf.value.decode()
+
+
+def test_stage_names_of_the_sequence_passes(golden_dir):
+    """fsdp_stage_names character for character behind fsdp_plan_sequence and fsdp_plan_sequence_cached: 3 planners x 6 steps of
+    ss.fleet (48 cones or 2 per frame: the 128-cone state, no route kernel), and with always_route the four 272-cone steps of the
+    `big` fixture (the 255-cone state, and both route kernels with every pass)."""
+    path = "match_kernel<32>,path_kernel<64>,"  # (18 frames and 4: a wavefront per frame)
+    chain = "seq_mark_kernel,seq_chain_kernel,seq_final_kernel,assemble_kernel"
+    cache = "seq_cache_mark_kernel,seq_cache_resolve_kernel,"
+    off, cones, poses = ss.fleet(3, 6)
+    assert set(np.diff(off).tolist()) == {2, 48}
+    ctx = context(0)
+    ctx.plan_sequence(off, cones, poses, 3)
+    print("plan_sequence:", stage_string(ctx))
+    assert stage_string(ctx) == "sort_kernel_128," + path + chain
+    ctx.close()
+    ctx = context(3)
+    ctx.plan_sequence_cached(off, cones, poses, 3)
+    print("plan_sequence_cached:", stage_string(ctx))
+    assert stage_string(ctx) == "sort_kernel_128_spec," + cache + path + chain
+    ctx.close()
+    g = cs.load(golden_dir, "big")
+    assert int(g["n_planners"]) == 1 and (np.diff(g["offsets"]) > 255).all()
+    routed = pkg._capi.Context(device=0, options={"always_route": 1})
+    routed.sort_cache_reset(1)
+    routed.plan_sequence_cached(g["offsets"], g["cones"], g["poses"], 1)
+    print("always_route, 272 cones:", stage_string(routed))
+    assert stage_string(routed) == "sort_kernel_spec,sort_big_kernel_spec," + cache + path + "path_retry_kernel," + chain
+    routed.close()
 
 
 def raising_sequence(fuzz_frame, golden_dir, seed=3, jitter_seed=None):
