@@ -200,6 +200,10 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     lib.fsdp_plan_sequence_compact.argtypes = lib.fsdp_plan_sequence.argtypes
     lib.fsdp_plan_sequence_cached.argtypes = lib.fsdp_plan_sequence.argtypes + [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
     lib.fsdp_plan_sequence_cached_compact.argtypes = lib.fsdp_plan_sequence_cached.argtypes
+    lib.fsdp_submit_sequence.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong),
+                                         ctypes.POINTER(ctypes.c_longlong)]
+    lib.fsdp_submit_sequence_compact.argtypes = lib.fsdp_submit_sequence.argtypes
     lib.fsdp_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_longlong]
     lib.fsdp_pcie_probe.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                     ctypes.POINTER(ctypes.c_double)]
@@ -235,7 +239,7 @@ EXPORTED_SYMBOLS = [
     "fsdp_submit_compact", "fsdp_plan_batch_compact", "fsdp_set_option", "fsdp_pcie_probe",
     "fsdp_skidpad_submit", "fsdp_route_stats", "fsdp_ticket_capacity", "fsdp_selftest_det3", "fsdp_debug_arena", "fsdp_selftest_absminmax", "fsdp_selftest_libm", "fsdp_selftest_givens",
     "fsdp_sort_cache_reset", "fsdp_sort_cache_hits", "fsdp_sort_batch_ranked", "fsdp_plan_sequence", "fsdp_plan_sequence_compact",
-    "fsdp_plan_sequence_cached", "fsdp_plan_sequence_cached_compact",
+    "fsdp_plan_sequence_cached", "fsdp_plan_sequence_cached_compact", "fsdp_submit_sequence", "fsdp_submit_sequence_compact",
 ]
 RANK_MAX, COST_TERMS = 64, 7  # include/fsdp.h FSDP_RANK_MAX, FSDP_COST_TERMS
 COST_TERM_NAMES = ("angle", "residual_distance", "number_of_cones", "initial_direction", "change_of_direction", "cones_on_either",
@@ -349,6 +353,14 @@ class Ticket:
     def __init__(self, id_, out, info, keep):
         self.id, self.out, self.info, self._keep = id_, out, info, keep
 
+class SequenceTicket(Ticket):
+    """A sequence call in flight (Context.submit_sequence): collect() returns (results, final_prev, n_replanned)."""
+
+    __slots__ = ("final", "_again")
+
+    def __init__(self, id_, out, final, again, keep):
+        super().__init__(id_, out, None, keep)
+        self.final, self._again = final, again
 
 
 def _dp(a):
@@ -615,10 +627,49 @@ class Context:
                                           out.ctypes.data + out.strides[0] * lo, ctypes.byref(t)), "fsdp_submit")
         return Ticket(int(t.value), out, None, (offsets, cones, poses, prev))
 
-    def collect(self, ticket: Ticket) -> np.ndarray:
-        """Wait for this ticket only; returns its result array."""
+    def submit_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False, planner_lo: int = 0,
+                        planners_total: int | None = None, out=None, final_prev_out=None) -> SequenceTicket:
+        """fsdp_submit_sequence: plan_sequence as a ticket, for the planners [planner_lo, planner_lo + n_planners) of a recording.
+        The arrays describe the WHOLE recording of planners_total (default: n_planners) planners x T steps, step-major: offsets of
+        T * planners_total frames (any base), their cones and poses, initial_prev (planners_total, <= path_points, 4) or None.
+        out / final_prev_out: the recording's result array (T * planners_total records) and (planners_total, path_points, 4) block
+        the call writes ITS rows of (default: new page-locked arrays) — the planner slices of one recording share them.  Page-locked
+        arrays (pinned_empty / pinned_copy) are read and written in place by the GPU; others are staged.  Everything must stay
+        untouched until collect(), which returns (out, final_prev_out, n_replanned)."""
+        n_planners, planner_lo = int(n_planners), int(planner_lo)
+        total = n_planners if planners_total is None else int(planners_total)
+        offsets, cones, poses, n = self._prep_any_base(cone_offsets, cones_xyt, poses)
+        if total < 1 or n < 1 or n % total:
+            raise ValueError(f"submit_sequence: {n} frames are not a whole number (>= 1) of steps of {total} planners")
+        rows = self.shapes.path_points
+        init = None
+        if initial_prev is not None:
+            init = self.pad_paths(initial_prev)
+            if len(init) != total:
+                raise ValueError(f"submit_sequence: initial_prev holds {len(init)} rows, the recording {total} planners")
+        dt = self.compact_dtype if compact else self.result_dtype
+        if out is None:
+            out = pinned_empty(n, dt)
+        if final_prev_out is None:
+            final_prev_out = pinned_empty((total, rows, 4))
+        if out.dtype != dt or len(out) != n or not out.flags.c_contiguous:
+            raise ValueError(f"submit_sequence: out must be a contiguous {dt} array of the recording's {n} frames")
+        if final_prev_out.dtype != np.float64 or final_prev_out.shape != (total, rows, 4) or not final_prev_out.flags.c_contiguous:
+            raise ValueError(f"submit_sequence: final_prev_out must be a contiguous float64 array of shape {(total, rows, 4)}")
+        again, t = ctypes.c_longlong(0), ctypes.c_longlong(-1)
+        fn = self._lib.fsdp_submit_sequence_compact if compact else self._lib.fsdp_submit_sequence
+        self._check(fn(self._h, n_planners, n // total, planner_lo, total, offsets.ctypes.data, cones.ctypes.data if len(cones) else None,
+                       poses.ctypes.data, None if init is None else init.ctypes.data, out.ctypes.data, final_prev_out.ctypes.data,
+                       ctypes.byref(again), ctypes.byref(t)), "fsdp_submit_sequence")
+        return SequenceTicket(int(t.value), out, final_prev_out, again, (offsets, cones, poses, init))
+
+    def collect(self, ticket: Ticket):
+        """Wait for this ticket only; returns its result array — for a ticket of submit_sequence (results, final_prev,
+        n_replanned), the first two being the recording's arrays the call wrote its rows of."""
         self._check(self._lib.fsdp_collect(self._h, ctypes.c_longlong(ticket.id)), "fsdp_collect")
         ticket._keep = None
+        if isinstance(ticket, SequenceTicket):
+            return ticket.out, ticket.final, int(ticket._again.value)
         return ticket.out
 
     @property

@@ -122,7 +122,26 @@ struct Work {
   // the most recent pass launched on the slot (verify_pass re-runs it with the route kernels when they were needed)
   const Inputs* pass_in = nullptr;
   bool ran_big = false, ran_retry = false, unverified = false, pass_skid = false;
-  // tickets of fsdp_submit / fsdp_skidpad_submit queued on this slot's stream (id -1: free entry)
+  // A sequence pass (fsdp_plan_sequence*, fsdp_submit_sequence*) as its ticket describes it: the ticket's pass — and the rerun
+  // fsdp_collect issues when the pass lacked a route — resolves the planners' previous-path chains between the path stage and the
+  // assembly.  The pointers are the caller's, valid and untouched until fsdp_collect like the batch's.
+  struct SeqPass {
+    bool on = false;
+    SeqSlice s = {};           // planners [lo, lo + n) of a recording of `total`, n_steps steps (whole call: lo = 0, total = n)
+    bool cached = false;       // fsdp_plan_sequence_cached: the speculative sorting kernels and the cache chain (never cache_call)
+    const char* who = "";      // the entry point, for error texts
+    const int32_t* off = nullptr;  // the whole recording's arrays (a slice's frames are not contiguous in them: t.batch holds counts only)
+    const double* cones = nullptr;
+    const double* poses = nullptr;
+    fsdp_frame_result* results = nullptr;
+    const double* init = nullptr;   // the slice's first initial_prev row, or NULL
+    double* final_prev = nullptr;   // the slice's first final_prev row, or NULL
+    long long* n_replanned = nullptr;
+    // set by enqueue_ticket
+    double* final_dev = nullptr;    // where seq_final_kernel writes: page-locked host memory (the caller's rows or the ticket's h_fin), or the slot's d_seq_final
+    bool fin_staged = false;        // final_prev goes through h_fin (fsdp_collect copies it out)
+  };
+  // tickets of fsdp_submit / fsdp_skidpad_submit / fsdp_submit_sequence queued on this slot's stream (id -1: free entry)
   struct Ticket {
     long long id = -1;
     bool skid = false;
@@ -141,7 +160,10 @@ struct Work {
     fsdp_frame_result* h_stage = nullptr;  // pinned + mapped: the assembly kernel writes a pageable caller's results here
     char* h_in = nullptr;                  // pinned + mapped: a small pageable batch is packed here and read by the sorting kernel itself
     SkidInfo* h_info = nullptr;            // pinned
-    size_t cap_stage = 0, cap_in = 0, cap_info = 0;  // their capacities (grow_pinned)
+    SeqSeg* h_seg = nullptr;               // pinned + mapped: the per-step segments of a planner slice (seq_slice_in_kernel reads them)
+    double* h_fin = nullptr;               // pinned + mapped: seq_final_kernel writes a pageable caller's final_prev rows here
+    size_t cap_stage = 0, cap_in = 0, cap_info = 0, cap_seg = 0, cap_fin = 0;  // their capacities (grow_pinned)
+    SeqPass sq;                            // a sequence ticket's pass
     hipEvent_t done = nullptr;             // recorded behind the ticket's last command
   } tk[SLOT_QUEUE];
 };
@@ -250,14 +272,9 @@ struct fsdp_ctx {
   int8_t* d_cache_hits = nullptr;
   std::vector<int8_t> cache_hits;             // codes of the most recent call
   bool cache_call = false;                    // the call in progress advances the cached planners
-  // fsdp_plan_sequence: set for the duration of the call — its pass (and the rerun of a pass that lacked a route) resolves the
-  // planners' previous-path chains between the path stage and the assembly
-  struct Sequence {
-    int n_planners = 0, n_steps = 0;
-    bool with_init = false;  // the slot's d_seq_init holds the caller's initial_prev
-    bool cached = false;     // fsdp_plan_sequence_cached: the speculative sorting kernels and the cache chain (never cache_call)
-  };
-  const Sequence* sequence = nullptr;
+  // the sequence pass enqueue_ticket is launching (its ticket's description), else NULL: launch_pass puts the chain kernels
+  // between the path stage and the assembly
+  const Work::SeqPass* sequence = nullptr;
 };
 // (an empty route launch costs a stream ~1 % of a pass; a pass repeated because the kernel was missing costs a whole pass and
 // stalls the caller's collect: once needed, a route stays for a long time)
@@ -373,6 +390,8 @@ static void free_work(Work& w) {
     if (t.h_stage) (void)hipHostFree(t.h_stage);
     if (t.h_in) (void)hipHostFree(t.h_in);
     if (t.h_info) (void)hipHostFree(t.h_info);
+    if (t.h_seg) (void)hipHostFree(t.h_seg);
+    if (t.h_fin) (void)hipHostFree(t.h_fin);
     if (t.done) (void)hipEventDestroy(t.done);
   }
 }
@@ -469,8 +488,8 @@ static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
 // fsdp_plan_sequence_cached: what sequence_cache_lib.hip's launches need, once per pass (launch_pass)
 static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs& in) {
   fsdp_seqc_launch_args a;
-  a.n_planners = c->sequence->n_planners;
-  a.n_steps = c->sequence->n_steps;
+  a.n_planners = c->sequence->s.n;
+  a.n_steps = c->sequence->s.n_steps;
   a.off = in.d_off;
   a.cones = in.d_cones;
   a.poses = in.d_poses;
@@ -715,19 +734,19 @@ static void launch_assemble(fsdp_ctx* c, Work& q, int n, const PassIO& io, bool 
 // every frame was planned with the constant initial path; the runs of frames that read it are planned again in order, a wavefront
 // per run.
 static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const PassIO& io) {
-  const fsdp_ctx::Sequence& sq = *c->sequence;
+  const Work::SeqPass& sq = *c->sequence;
   fsdp_seq_launch_args a;
-  a.n_planners = sq.n_planners;
-  a.n_steps = sq.n_steps;
+  a.n_planners = sq.s.n;
+  a.n_steps = sq.s.n_steps;
   a.poses = in.d_poses;
   a.matched = q.d_match;
-  a.initial_prev = sq.with_init ? q.d_seq_init : nullptr;
+  a.initial_prev = sq.init ? q.d_seq_init : nullptr;
   a.gpath = c->d_gpath;
   a.n_gpath = c->n_gpath;
   a.arena = q.d_arena;
   a.out = q.d_path;
   a.seq = q.d_seq;
-  a.final_prev = q.d_seq_final;
+  a.final_prev = sq.final_dev;
   a.replanned_out = &(q.d_trailer + io.trailer)->pad;
   a.prm = c->d_params;
   fsdp_seq_launch(q.stream, &a);
@@ -1465,13 +1484,120 @@ static Work::Ticket* find_ticket(fsdp_ctx* c, long long ticket, Work** slot) {
 // four hipMemcpyAsync calls from pageable memory cost a single-frame call ~30 us of its ~860.
 constexpr size_t SMALL_BATCH_BYTES = 256 * 1024;
 
+
+// ---- sequence tickets ---------------------------------------------------------------------------------------------------------
+constexpr size_t SEQ_PREV_DOUBLES = (size_t)PATH_POINTS * 4;  // one planner's row of initial_prev / final_prev
+
+// a frame count the device has no room for is an error code: whatever was replaced on the way is replaced again next time
+static void seq_no_room(Work& q) {
+  q.cap_frames = q.in.cap_frames = q.in.cap_prev = 0;
+  q.seq_cap_frames = q.seq_cap_planners = 0;
+  q.seqc_cap_frames = q.seqc_cap_planners = 0;
+  (void)hipGetLastError();
+}
+
+// the run-head list and the planners' rows of slot q for a sequence pass of `frames` frames (the slot's stream is idle where
+// something has to grow: enqueue_ticket)
+static int ensure_sequence(fsdp_ctx* c, Work& q, const Work::SeqPass& sq, size_t frames) {
+  // `count` elements behind p where the slot has had room for `cap` < `want` frames (or planners) so far; false: out of memory
+  auto grown = [&](auto*& p, size_t cap, size_t want, size_t count) {
+    if (want <= cap) return true;
+    const hipError_t e = regrow(p, count);
+    if (e != hipSuccess) c->err = std::string(sq.who) + ": " + hipGetErrorString(e);
+    return e == hipSuccess;
+  };
+  const size_t np = (size_t)sq.s.n;
+  if (!grown(q.d_seq, q.seq_cap_frames, frames, (size_t)SEQ_LIST + 2 * frames) || !grown(q.d_seq_init, q.seq_cap_planners, np, SEQ_PREV_DOUBLES * np) ||
+      !grown(q.d_seq_final, q.seq_cap_planners, np, SEQ_PREV_DOUBLES * np))
+    return 2;
+  q.seq_cap_frames = std::max(q.seq_cap_frames, frames);
+  q.seq_cap_planners = std::max(q.seq_cap_planners, np);
+  return 0;
+}
+
+// The rows of the caller's arrays a planner slice touches, first to last: n_steps segments `total` frames apart
+struct SliceExtent {
+  size_t span_frames;            // frames from the slice's first to behind its last: (n_steps - 1) * total + n
+  int32_t cone_lo = 0, cone_hi = 0;  // cone rows [lo, hi) the segments read
+};
+static SliceExtent slice_extent(const SeqSlice& s, const SeqSeg* seg) {
+  SliceExtent x;
+  x.span_frames = (size_t)(s.n_steps - 1) * (size_t)s.total + (size_t)s.n;
+  bool any = false;
+  for (int t = 0; t < s.n_steps; t++) {
+    const int32_t cnt = seg[t + 1].dst - seg[t].dst;
+    if (cnt == 0) continue;
+    x.cone_lo = any ? std::min(x.cone_lo, seg[t].src) : seg[t].src;
+    x.cone_hi = any ? std::max(x.cone_hi, seg[t].src + cnt) : seg[t].src + cnt;
+    any = true;
+  }
+  return x;
+}
+// every row seq_slice_in_kernel reads is page-locked
+static bool slice_inputs_pinned(const Work::SeqPass& sq, const SliceExtent& x) {
+  const SeqSlice& s = sq.s;
+  return is_pinned(sq.off + s.lo, sizeof(int32_t) * (x.span_frames + 1)) && is_pinned(sq.poses + 4 * (size_t)s.lo, sizeof(double) * 4 * x.span_frames) &&
+         (x.cone_hi == x.cone_lo || is_pinned(sq.cones + 3 * (size_t)x.cone_lo, sizeof(double) * 3 * (size_t)(x.cone_hi - x.cone_lo))) &&
+         (!sq.init || is_pinned(sq.init, sizeof(double) * SEQ_PREV_DOUBLES * (size_t)s.n));
+}
+
+// A pageable planner slice, packed by the host into the ticket's page-locked block in the call's own order: from there on it
+// is a contiguous page-locked batch like any other (read by the sorting kernel itself).
+static int pack_slice(fsdp_ctx* c, Work::Ticket& t, Batch* b) {
+  const Work::SeqPass& sq = t.sq;
+  const SeqSlice& s = sq.s;
+  const size_t nf = (size_t)s.frames(), rows = (size_t)t.h_seg[s.n_steps].dst;
+  const size_t off_bytes = (sizeof(int32_t) * (nf + 1) + 15) & ~(size_t)15, cone_bytes = sizeof(double) * 3 * rows, pose_bytes = sizeof(double) * 4 * nf;
+  HIP_TRY(c, grow_pinned(t.h_in, t.cap_in, off_bytes + cone_bytes + pose_bytes, hipHostMallocMapped, 16384));
+  int32_t* so = (int32_t*)t.h_in;
+  double* sc = (double*)(t.h_in + off_bytes);
+  double* sp = (double*)(t.h_in + off_bytes + cone_bytes);
+  for (int step = 0; step < s.n_steps; step++) {
+    const SeqSeg g = t.h_seg[step];
+    const size_t r = (size_t)seq_rec_frame(s, step, 0), f = (size_t)step * (size_t)s.n;
+    for (int p = 0; p < s.n; p++) so[f + (size_t)p] = (int32_t)seq_dense_offset(g, sq.off[r + (size_t)p]);  // (within [0, rows]: the segments were checked)
+    const size_t cnt = (size_t)(t.h_seg[step + 1].dst - g.dst);
+    if (cnt) memcpy(sc + 3 * (size_t)g.dst, sq.cones + 3 * (size_t)g.src, sizeof(double) * 3 * cnt);
+    memcpy(sp + 4 * f, sq.poses + 4 * r, sizeof(double) * 4 * (size_t)s.n);
+  }
+  so[nf] = (int32_t)rows;
+  *b = Batch{(int)nf, so, sc, sp, nullptr, rows, b->max_cones};
+  return 0;
+}
+
 static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_routes) {
   Batch b = t.batch;
   const int n = b.n;
+  Work::SeqPass* sq = t.sq.on ? &t.sq : nullptr;
+  const bool sliced = sq && !sq->s.whole();
+  struct Scope {  // (c->sequence: the pass this call launches)
+    fsdp_ctx* c;
+    ~Scope() { c->sequence = nullptr; }
+  } scope{c};
+  c->sequence = sq;
   // a bigger batch than the slot has seen: its buffers are replaced — not under the feet of the passes queued on the stream
-  if (n > q.cap_frames || n > q.in.cap_frames || b.total > q.in.cap_cones || (b.prev && n > q.in.cap_prev)) HIP_TRY(c, hipStreamSynchronize(q.stream));
+  if (n > q.cap_frames || n > q.in.cap_frames || b.total > q.in.cap_cones || (b.prev && n > q.in.cap_prev) ||
+      (sq && ((size_t)n > q.seq_cap_frames || (size_t)sq->s.n > q.seq_cap_planners)))
+    HIP_TRY(c, hipStreamSynchronize(q.stream));
   if (int rc = ensure_work(c, q, n > 0 ? n : 1)) return rc;
-  bool in_pinned = inputs_pinned(b);
+  if (sq)
+    if (int rc = ensure_sequence(c, q, *sq, (size_t)n)) return rc;
+  const size_t init_bytes = sq ? sizeof(double) * SEQ_PREV_DOUBLES * (size_t)sq->s.n : 0;
+  bool slice_in = false;  // a page-locked planner slice: seq_slice_in_kernel leaves the device copies
+  SliceExtent ext;
+  if (sliced) {
+    // (the segments again, from the arrays the submit checked: a repeated pass reads them like the batch itself)
+    HIP_TRY(c, grow_pinned(t.h_seg, t.cap_seg, (size_t)sq->s.n_steps + 1, hipHostMallocMapped, 64));
+    if (seq_slice_segments(sq->s, sq->off, t.h_seg, nullptr) != 0 || (size_t)t.h_seg[sq->s.n_steps].dst != b.total) {
+      c->err = std::string(sq->who) + ": cone_offsets changed between submit and collect";
+      return 1;
+    }
+    ext = slice_extent(sq->s, t.h_seg);
+    slice_in = slice_inputs_pinned(*sq, ext);
+    if (!slice_in)
+      if (int rc = pack_slice(c, t, &b)) return rc;
+  }
+  bool in_pinned = slice_in || sliced || inputs_pinned(b);
   const size_t off_bytes = (sizeof(int32_t) * ((size_t)n + 1) + 15) & ~(size_t)15, cone_bytes = sizeof(double) * 3 * b.total,
                pose_bytes = sizeof(double) * 4 * (size_t)n, prev_bytes = b.prev ? sizeof(double) * PATH_POINTS * 4 * (size_t)n : 0;
   const size_t in_bytes = off_bytes + cone_bytes + pose_bytes + prev_bytes;
@@ -1490,7 +1616,29 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     in_pinned = true;
   }
   PassIO io;
-  if (in_pinned && c->params.use_unknown_cones && !seq_cached(c)) {  // (the speculative kernels read their predecessors' cones: device copies first)
+  if (slice_in) {
+    if (int rc = take_batch(c, q.in, b)) return rc;
+    const SeqSlice& s = sq->s;
+    fsdp_seq_slice_in_args a;
+    a.s = s;
+    a.seg = (const SeqSeg*)device_view(t.h_seg);
+    a.src_off = (const int32_t*)device_view(sq->off + s.lo);
+    a.src_cones = (const double*)device_view(ext.cone_hi > ext.cone_lo ? sq->cones + 3 * (size_t)ext.cone_lo : sq->poses);  // (never read when no segment holds a cone)
+    a.src_poses = (const double*)device_view(sq->poses + 4 * (size_t)s.lo);
+    a.src_init = sq->init ? (const double*)device_view(sq->init) : nullptr;
+    a.cone_base = ext.cone_lo;
+    a.src_rows = (long long)ext.cone_hi - ext.cone_lo;
+    a.rows = (long long)b.total;
+    a.dst_off = q.in.d_off;
+    a.dst_cones = q.in.d_cones;
+    a.dst_poses = q.in.d_poses;
+    a.dst_init = q.d_seq_init;
+    if (!a.seg || !a.src_off || !a.src_cones || !a.src_poses) {
+      c->err = "internal: a slice's page-locked arrays are not mapped into the device's address space";
+      return 2;
+    }
+    fsdp_seq_launch_slice_in(q.stream, &a);
+  } else if (in_pinned && c->params.use_unknown_cones && !seq_cached(c)) {  // (the speculative kernels read their predecessors' cones: device copies first)
     // the pass's sorting kernel reads the batch from the page-locked buffers and leaves the device copies (StageIn)
     if (int rc = take_batch(c, q.in, b)) return rc;
     StageIn& st = io.stage;
@@ -1510,20 +1658,48 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
   } else if (int rc = upload_inputs(c, q.in, q.stream, b)) {
     return rc;
   }
+  // (the initial_prev rows of a sequence pass: adjacent also for a slice; seq_slice_in_kernel brought a page-locked slice's along)
+  if (sq && sq->init && !slice_in) HIP_TRY(c, hipMemcpyAsync(q.d_seq_init, sq->init, init_bytes, hipMemcpyHostToDevice, q.stream));
   t.via_stage = false;
   if (n > 0) {
     // Results always leave the GPU inside the pass's last kernel, written over PCIe into page-locked memory: the caller's own buffer,
     // or — for a pageable one — the ticket's block, which fsdp_collect copies out (no copy command on the stream either way).
+    // A planner slice's records are n_steps segments of the caller's array: seq_slice_out_kernel moves them there from the slot's
+    // result block when the array (and final_prev) is page-locked; else they go through the ticket's block, dense, like any
+    // pageable caller's, and fsdp_collect copies the segments out.
     fsdp_frame_result* dst = t.user_results;
-    if (!is_pinned(t.user_results, t.rec_bytes() * (size_t)n)) {
+    char* slice_dst = sliced ? (char*)t.user_results + t.rec_bytes() * (size_t)sq->s.lo : nullptr;
+    const bool slice_out = sliced && is_pinned(slice_dst, t.rec_bytes() * ext.span_frames) && (!sq->final_prev || is_pinned(sq->final_prev, init_bytes));
+    if (slice_out) {
+      dst = nullptr;
+    } else if (sliced || !is_pinned(t.user_results, t.rec_bytes() * (size_t)n)) {
       HIP_TRY(c, grow_pinned(t.h_stage, t.cap_stage, (size_t)n, hipHostMallocMapped, 64));
       dst = t.h_stage;
       t.via_stage = true;
     }
     io.host = (fsdp_frame_result*)device_view(dst);
-    if (!io.host) {
+    if (dst && !io.host) {
       c->err = "internal: result block is not mapped into the device's address space";
       return 2;
+    }
+    if (sq) {
+      // final_prev leaves the GPU inside seq_final_kernel, written into page-locked memory like the records: the caller's rows, or
+      // the ticket's block (the slot's d_seq_final serves the slot's next ticket before this one is collected)
+      sq->fin_staged = false;
+      sq->final_dev = slice_out ? q.d_seq_final : nullptr;
+      if (sq->final_prev && !slice_out) {
+        double* fdst = sq->final_prev;
+        if (!is_pinned(fdst, init_bytes)) {
+          HIP_TRY(c, grow_pinned(t.h_fin, t.cap_fin, SEQ_PREV_DOUBLES * (size_t)sq->s.n, hipHostMallocMapped, 64 * SEQ_PREV_DOUBLES));
+          fdst = t.h_fin;
+          sq->fin_staged = true;
+        }
+        sq->final_dev = (double*)device_view(fdst);
+        if (!sq->final_dev) {
+          c->err = "internal: final_prev block is not mapped into the device's address space";
+          return 2;
+        }
+      }
     }
     io.compact = t.compact;
     io.trailer = (int)(&t - q.tk);  // the ticket's own trailer
@@ -1531,10 +1707,68 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     t.seq = q.seq;
     t.ran_big = q.ran_big;
     t.ran_retry = q.ran_retry;
+    if (slice_out) {
+      fsdp_seq_slice_out_args a;
+      a.s = sq->s;
+      a.rec_bytes = (int)t.rec_bytes();
+      a.src_records = q.d_result;
+      a.dst_records = device_view(slice_dst);
+      a.src_final = q.d_seq_final;
+      a.dst_final = sq->final_prev ? (double*)device_view(sq->final_prev) : nullptr;
+      if (!a.dst_records || (sq->final_prev && !a.dst_final)) {
+        c->err = "internal: a slice's result arrays are not mapped into the device's address space";
+        return 2;
+      }
+      fsdp_seq_launch_slice_out(q.stream, &a);
+    }
+    // A planner slice, by whichever route, is never the context's "most recent pass": its frames are the call's dense order, not the
+    // caller's recording, so fsdp_resident_frames / fsdp_download / fsdp_debug_* have nothing to hand out.  The whole call stays what
+    // an fsdp_submit ticket is to them (launch_pass: its frame count, results not in the slot's block).
+    if (sliced) c->last = fsdp_ctx::LastPass();
     HIP_TRY(c, hipGetLastError());
   }
   if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
   HIP_TRY(c, hipEventRecord(t.done, q.stream));
+  return 0;
+}
+
+// The slot with the fewest tickets queued, starting from the one after the previous ticket's (in-order traffic: round robin),
+// with its stream and a settled state, and a free ticket entry of it; 4: every entry is taken.
+static int free_ticket(fsdp_ctx* c, const char* who, int n_frames, Work** slot, Work::Ticket** ticket) {
+  int si = -1, best = SLOT_QUEUE;
+  long long oldest = -1;
+  for (int k = 0; k < c->overlap; k++) {
+    const int i = (c->last_ticket_slot + 1 + k) % c->overlap;
+    int cnt = 0;
+    for (const Work::Ticket& e : c->slot[i].tk) {
+      if (e.id < 0) continue;
+      cnt++;
+      if (oldest < 0 || e.id < oldest) oldest = e.id;
+    }
+    if (cnt < best) {
+      best = cnt;
+      si = i;
+    }
+  }
+  if (si < 0) {
+    c->err = std::string(who) + ": " + std::to_string(c->outstanding) + " tickets outstanding (" + std::to_string(SLOT_QUEUE) + " per slot, " +
+             std::to_string(c->overlap) + " slots): collect one first, e.g. ticket " + std::to_string(oldest);
+    return 4;
+  }
+  c->last_ticket_slot = si;
+  Work& q = c->slot[si];
+  Work::Ticket* t = nullptr;
+  for (Work::Ticket& e : q.tk)
+    if (e.id < 0 && !t) t = &e;
+  if (!q.stream) {
+    if (int rc = ensure_work(c, q, n_frames > 0 ? n_frames : 1)) return rc;
+  }
+  if (q.unverified) {  // an fsdp_run pass nobody waited for
+    HIP_TRY(c, hipStreamSynchronize(q.stream));
+    if (int rc = verify_pass(c, q)) return rc;
+  }
+  *slot = &q;
+  *ticket = t;
   return 0;
 }
 
@@ -1553,45 +1787,17 @@ static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
   HIP_TRY(c, hipSetDevice(c->device));
   Batch b;
   if (int rc = check_batch(c, n_frames, off, cones, poses, prev_paths, &b)) return rc;
-  // the slot with the fewest tickets queued, starting from the one after the previous ticket's (in-order traffic: round robin)
-  int si = -1, best = SLOT_QUEUE;
-  long long oldest = -1;
-  for (int k = 0; k < c->overlap; k++) {
-    const int i = (c->last_ticket_slot + 1 + k) % c->overlap;
-    int cnt = 0;
-    for (const Work::Ticket& e : c->slot[i].tk) {
-      if (e.id < 0) continue;
-      cnt++;
-      if (oldest < 0 || e.id < oldest) oldest = e.id;
-    }
-    if (cnt < best) {
-      best = cnt;
-      si = i;
-    }
-  }
-  if (si < 0) {
-    c->err = "fsdp_submit: " + std::to_string(c->outstanding) + " tickets outstanding (" + std::to_string(SLOT_QUEUE) + " per slot, " +
-             std::to_string(c->overlap) + " slots): collect one first, e.g. ticket " + std::to_string(oldest);
-    return 4;
-  }
-  c->last_ticket_slot = si;
-  Work& q = c->slot[si];
+  Work* qp = nullptr;
   Work::Ticket* t = nullptr;
-  for (Work::Ticket& e : q.tk)
-    if (e.id < 0 && !t) t = &e;
-  if (!q.stream) {
-    if (int rc = ensure_work(c, q, n_frames > 0 ? n_frames : 1)) return rc;
-  }
-  if (q.unverified) {  // an fsdp_run pass nobody waited for
-    HIP_TRY(c, hipStreamSynchronize(q.stream));
-    if (int rc = verify_pass(c, q)) return rc;
-  }
+  if (int rc = free_ticket(c, "fsdp_submit", n_frames, &qp, &t)) return rc;
+  Work& q = *qp;
   t->batch = b;
   t->skid = false;
   t->in_flight = frames_in_flight(c, n_frames, true);
   t->user_results = results;
   t->user_info = nullptr;
   t->compact = compact;
+  t->sq = Work::SeqPass();
   if (int rc = enqueue_ticket(c, q, *t, false)) {
     // Part of the batch may already be queued on the slot's stream — kernels that read the caller's buffers or write his
     // page-locked results — and no ticket goes out that he could wait on: wait here, so that an error return means the
@@ -1667,7 +1873,19 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
     }
   }
   if (rc == 0 && n > 0) {
-    if (t.via_stage) memcpy(t.user_results, t.h_stage, t.rec_bytes() * (size_t)n);
+    if (t.via_stage && t.sq.on && !t.sq.s.whole()) {  // a planner slice: the ticket's block is dense, the caller's array holds the whole recording
+      const SeqSlice& s = t.sq.s;
+      const size_t rec = t.rec_bytes(), seg = rec * (size_t)s.n;
+      for (int step = 0; step < s.n_steps; step++)
+        memcpy((char*)t.user_results + rec * (size_t)seq_rec_frame(s, step, 0), (const char*)t.h_stage + seg * (size_t)step, seg);
+    } else if (t.via_stage) {
+      memcpy(t.user_results, t.h_stage, t.rec_bytes() * (size_t)n);
+    }
+    if (t.sq.on) {
+      if (t.sq.fin_staged) memcpy(t.sq.final_prev, t.h_fin, sizeof(double) * SEQ_PREV_DOUBLES * (size_t)t.sq.s.n);
+      // (the ticket's own trailer word: seq_final_kernel of its pass — of the repeated pass, if there was one — wrote it)
+      if (t.sq.n_replanned) *t.sq.n_replanned = __atomic_load_n(&q.h_trailer[&t - q.tk].pad, __ATOMIC_RELAXED);
+    }
     if (t.user_info && t.h_info) {
       if (!c->skid_all_reloc) {
         bool all = true;
@@ -1683,10 +1901,12 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
       }
     }
   }
+  if (rc != 0 && t.sq.on) seq_no_room(q);  // (a repeated pass that found no room: see seq_issue)
   t.id = -1;
   t.user_results = nullptr;
   t.user_info = nullptr;
   t.compact = false;
+  t.sq = Work::SeqPass();
   c->outstanding--;
   return rc;
 }
@@ -1724,6 +1944,7 @@ static int issue_blocking(fsdp_ctx* c, Work& q, const Batch& b, long long in_fli
   t.user_results = results;
   t.user_info = nullptr;
   t.compact = compact;
+  t.sq = Work::SeqPass();
   if (int rc = enqueue_ticket(c, q, t, false)) {
     (void)hipStreamSynchronize(q.stream);
     (void)hipGetLastError();
@@ -1794,115 +2015,180 @@ int fsdp_plan_batch_compact(fsdp_ctx* c, int n_frames, const int32_t* off, const
 }
 
 // n_steps consecutive steps of n_planners planners as ONE pass (frame = step * n_planners + planner): never cut into chunks —
-// a chunk border would cut every planner's chain.  The pass is a ticket on slot 0 like a chunk of plan_blocking, with the
-// chain kernels in front of its assembly (launch_pass, c->sequence).
-// cached (fsdp_plan_sequence_cached): the planners' sorting-cache entries are chained on the device as well (c->sequence->cached:
-// the speculative sorting kernels and the cache chain of sequence_cache_kernel.h); hits: (n_steps * n_planners, 2) or NULL,
+// a chunk border would cut every planner's chain.  The pass is a ticket whose description (Work::SeqPass) puts the chain kernels
+// in front of its assembly (enqueue_ticket, launch_pass); fsdp_submit_sequence hands the ticket out, the blocking calls are
+// submit + collect of the whole call on slot 0, like a chunk of plan_blocking.
+// cached (fsdp_plan_sequence_cached, blocking only): the planners' sorting-cache entries are chained on the device as well (the
+// speculative sorting kernels and the cache chain of sequence_cache_kernel.h); hits: (n_steps * n_planners, 2) or NULL,
 // n_resorted or NULL.  The cache buffers are swapped once, after the whole call — a rerun pass reads the same entries.
-static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
-                         const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev, long long* n_replanned,
-                         bool cached = false, int8_t* hits = nullptr, long long* n_resorted = nullptr) {
-  if (!c) return 1;
-  const std::string who = cached ? "fsdp_plan_sequence_cached" : "fsdp_plan_sequence";
-  if (n_replanned) *n_replanned = 0;
-  if (n_resorted) *n_resorted = 0;
+struct SeqCall {
+  int n_planners, n_steps, planner_lo, planners_total;
+  const int32_t* off;
+  const double* cones;
+  const double* poses;
+  const double* initial_prev;  // the recording's blocks (planners_total rows), or NULL
+  fsdp_frame_result* results;
+  bool compact;
+  double* final_prev;
+  long long* n_replanned;
+  bool cached;
+};
+
+// what every sequence entry point refuses, in one order (blocking: the call needs the context to itself)
+static int seq_refusals(fsdp_ctx* c, const std::string& who, const SeqCall& k, bool blocking) {
   if (c->mission == 2) {
     c->err = who + ": a skidpad context plans through fsdp_skidpad_step";
     return 1;
   }
-  if (!cached && c->n_cache > 0) {
-    c->err = "fsdp_plan_sequence: the sorting cache is on (fsdp_sort_cache_reset): it is state of lock-step calls (fsdp_plan_batch_sequential)";
+  if (!k.cached && c->n_cache > 0) {
+    c->err = who + ": the sorting cache is on (fsdp_sort_cache_reset): it is state of lock-step calls (fsdp_plan_batch_sequential)";
     return 1;
   }
-  if (!fsdp_seq_launch) {
+  if (!fsdp_seq_launch || !fsdp_seq_launch_slice_in || !fsdp_seq_launch_slice_out) {
     c->err = who + ": this library was built without csrc/sequence_lib.hip";
     return 1;
   }
-  if (cached && !fsdp_seqc_launch_sort) {
+  if (k.cached && !fsdp_seqc_launch_sort) {
     c->err = who + ": this library was built without csrc/sequence_cache_lib.hip";
     return 1;
   }
-  if (c->outstanding) return busy_error(c, who.c_str());
-  if (n_planners < 1 || n_steps < 1) {
+  if (blocking && c->outstanding) return busy_error(c, who.c_str());
+  if (k.n_planners < 1 || k.n_steps < 1) {
     c->err = who + ": n_planners and n_steps must be >= 1";
     return 1;
   }
-  if (cached && c->n_cache == 0) {
+  const SeqSlice s{k.n_planners, k.n_steps, k.planner_lo, k.planners_total};
+  if (!seq_slice_valid(s)) {
+    c->err = who + ": planners [" + std::to_string(k.planner_lo) + ", " + std::to_string((long long)k.planner_lo + k.n_planners) +
+             ") are no slice of a recording of " + std::to_string(k.planners_total) + " planners";
+    return 1;
+  }
+  if (k.cached && c->n_cache == 0) {
     c->err = who + ": the sorting cache is off (fsdp_sort_cache_reset(ctx, n_planners) turns it on)";
     return 1;
   }
-  if (cached && n_planners != c->n_cache) {
-    c->err = who + ": the sorting cache is on for " + std::to_string(c->n_cache) + " planners, the call holds " + std::to_string(n_planners) +
+  if (k.cached && k.n_planners != c->n_cache) {
+    c->err = who + ": the sorting cache is on for " + std::to_string(c->n_cache) + " planners, the call holds " + std::to_string(k.n_planners) +
              " planners (frame f is planner f % n_planners; fsdp_sort_cache_reset)";
     return 1;
   }
-  const long long frames = (long long)n_planners * n_steps;
+  const long long frames = (long long)k.n_planners * k.n_steps;
   if (frames > (0x7fffffff - SEQ_LIST) / 2) {  // (the head list holds two ints per frame behind its header, indexed by int)
     c->err = who + ": " + std::to_string(frames) + " frames in one pass (at most 2^30 - 3)";
     return 1;
   }
-  if (!results) {
+  if (!k.results) {
     c->err = who + ": results is NULL";
     return 1;
   }
+  return 0;
+}
+
+// the call's frames as a Batch: the whole call through check_batch (its arrays are the batch); a planner slice's segments
+// checked like it, the Batch holding the counts only (its frames are not contiguous: Work::SeqPass keeps the arrays)
+static int seq_check_batch(fsdp_ctx* c, const SeqCall& k, Batch* b) {
+  const SeqSlice s{k.n_planners, k.n_steps, k.planner_lo, k.planners_total};
+  const int n = (int)s.frames();
+  if (s.whole()) return check_batch(c, n, k.off, k.cones, k.poses, nullptr, b);
+  if (!k.off || !k.poses) {
+    c->err = "batch: NULL offsets / poses";
+    return 1;
+  }
+  std::vector<SeqSeg> seg((size_t)s.n_steps + 1);
+  int most = 0;
+  const int bad = seq_slice_segments(s, k.off, seg.data(), &most);
+  if (bad) {
+    c->err = bad == 1 ? "cone_offsets must be >= 0" : (bad == 2 ? "cone_offsets must be non-decreasing" : "a slice's cone rows exceed 2^31 - 1");
+    return 1;
+  }
+  *b = Batch{n, nullptr, nullptr, nullptr, nullptr, (size_t)seg[(size_t)s.n_steps].dst, most};
+  if (b->total > 0 && !k.cones) {
+    c->err = "cones_xyt is NULL";
+    return 1;
+  }
+  return 0;
+}
+
+// The call as ticket t of slot q, planned for in_flight frames on the GPU.  0: issued as t.id.  Else nothing of it is left running
+// over the caller's buffers, no ticket went out, and the slot's buffers are replaced again next time.
+static int seq_issue(fsdp_ctx* c, Work& q, Work::Ticket& t, const Batch& b, const SeqCall& k, const char* who, long long in_flight) {
+  t.batch = b;
+  t.skid = false;
+  t.in_flight = in_flight;
+  t.user_results = k.results;
+  t.user_info = nullptr;
+  t.compact = k.compact;
+  Work::SeqPass& sq = t.sq;
+  sq = Work::SeqPass();
+  sq.on = true;
+  sq.s = SeqSlice{k.n_planners, k.n_steps, k.planner_lo, k.planners_total};
+  sq.cached = k.cached;
+  sq.who = who;
+  sq.off = k.off;
+  sq.cones = k.cones;
+  sq.poses = k.poses;
+  sq.results = k.results;
+  sq.init = k.initial_prev ? k.initial_prev + SEQ_PREV_DOUBLES * (size_t)k.planner_lo : nullptr;
+  sq.final_prev = k.final_prev ? k.final_prev + SEQ_PREV_DOUBLES * (size_t)k.planner_lo : nullptr;
+  sq.n_replanned = k.n_replanned;
+  if (int rc = enqueue_ticket(c, q, t, false)) {
+    (void)hipStreamSynchronize(q.stream);
+    (void)hipGetLastError();
+    t.user_results = nullptr;
+    t.compact = false;
+    t.sq = Work::SeqPass();
+    seq_no_room(q);
+    return rc;
+  }
+  t.id = c->next_ticket++;
+  c->outstanding++;
+  return 0;
+}
+
+static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                         const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev, long long* n_replanned,
+                         bool cached = false, int8_t* hits = nullptr, long long* n_resorted = nullptr) {
+  if (!c) return 1;
+  const char* who = cached ? "fsdp_plan_sequence_cached" : "fsdp_plan_sequence";
+  if (n_replanned) *n_replanned = 0;
+  if (n_resorted) *n_resorted = 0;
+  const SeqCall k{n_planners, n_steps, 0, n_planners, off, cones, poses, initial_prev, results, compact, final_prev, n_replanned, cached};
+  if (int rc = seq_refusals(c, who, k, true)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  const int n = (int)frames;
+  const int n = n_planners * n_steps;
   Batch b;
-  if (int rc = check_batch(c, n, off, cones, poses, nullptr, &b)) return rc;
+  if (int rc = seq_check_batch(c, k, &b)) return rc;
   if (int rc = sync_all(c)) return rc;
   c->last = fsdp_ctx::LastPass();
   Work& q = c->slot[0];
   q.cache_base = 0;  // (frame f is planner f % n_planners: seq_cache_mark_kernel takes the view as it is)
-  // a frame count the device has no room for is an error code: whatever was replaced on the way is replaced again next time
-  auto no_room = [&](int rc) {
-    q.cap_frames = q.in.cap_frames = q.in.cap_prev = 0;
-    q.seq_cap_frames = q.seq_cap_planners = 0;
-    q.seqc_cap_frames = q.seqc_cap_planners = 0;
-    (void)hipGetLastError();
+  if (int rc = ensure_work(c, q, n)) {
+    seq_no_room(q);
     return rc;
-  };
-  if (int rc = ensure_work(c, q, n)) return no_room(rc);
-  // `count` elements behind p where the slot has had room for `cap` < `want` frames (or planners) so far; false: out of memory
-  auto grown = [&](auto*& p, size_t cap, size_t want, size_t count) {
-    if (want <= cap) return true;
-    const hipError_t e = regrow(p, count);
-    if (e != hipSuccess) c->err = who + ": " + hipGetErrorString(e);
-    return e == hipSuccess;
-  };
-  const size_t nf = (size_t)n, np = (size_t)n_planners, prev_doubles = (size_t)PATH_POINTS * 4 * np;
-  if (!grown(q.d_seq, q.seq_cap_frames, nf, (size_t)SEQ_LIST + 2 * nf) || !grown(q.d_seq_init, q.seq_cap_planners, np, prev_doubles) ||
-      !grown(q.d_seq_final, q.seq_cap_planners, np, prev_doubles))
-    return no_room(2);
-  q.seq_cap_frames = std::max(q.seq_cap_frames, nf);
-  q.seq_cap_planners = std::max(q.seq_cap_planners, np);
+  }
   if (cached) {
+    auto grown = [&](auto*& p, size_t cap, size_t want, size_t count) {
+      if (want <= cap) return true;
+      const hipError_t e = regrow(p, count);
+      if (e != hipSuccess) c->err = std::string(who) + ": " + hipGetErrorString(e);
+      return e == hipSuccess;
+    };
+    const size_t nf = (size_t)n, np = (size_t)n_planners;
     if (!grown(q.d_seqc_rec, q.seqc_cap_frames, nf, nf) || !grown(q.d_seqc_hits, q.seqc_cap_frames, nf, 2 * nf) ||
-        !grown(q.d_seqc_resorted, q.seqc_cap_planners, np, np))
-      return no_room(2);
+        !grown(q.d_seqc_resorted, q.seqc_cap_planners, np, np)) {
+      seq_no_room(q);
+      return 2;
+    }
     q.seqc_cap_frames = std::max(q.seqc_cap_frames, nf);
     q.seqc_cap_planners = std::max(q.seqc_cap_planners, np);
     // the buffer the call writes gets room for every planner's largest frame of the sequence (cache_prepare, step by step)
     for (int s = 0; s < n_steps; s++)
-      if (int rc = cache_prepare(c, n_planners, off + (size_t)s * n_planners, who.c_str())) return rc;
+      if (int rc = cache_prepare(c, n_planners, off + (size_t)s * n_planners, who)) return rc;
   }
-  const size_t prev_bytes = sizeof(double) * prev_doubles;
-  if (initial_prev) HIP_TRY(c, hipMemcpyAsync(q.d_seq_init, initial_prev, prev_bytes, hipMemcpyHostToDevice, q.stream));
-  fsdp_ctx::Sequence sq;
-  sq.n_planners = n_planners;
-  sq.n_steps = n_steps;
-  sq.with_init = initial_prev != nullptr;
-  sq.cached = cached;
-  struct Scope {
-    fsdp_ctx* c;
-    ~Scope() { c->sequence = nullptr; }
-  } scope{c};
-  c->sequence = &sq;
-  if (int rc = issue_blocking(c, q, b, n, results, compact)) return no_room(rc);
+  if (int rc = seq_issue(c, q, q.tk[0], b, k, who, n)) return rc;
   int rc = fsdp_collect(c, q.tk[0].id);  // (waits; runs the pass again, chain kernels included, if it lacked a route)
   c->next_ticket--;                // (the number was internal, like plan_blocking's)
   if (rc != 0) return rc;
-  if (n_replanned) *n_replanned = __atomic_load_n(&q.h_trailer[0].pad, __ATOMIC_RELAXED);
-  if (final_prev) HIP_TRY(c, copy_sync(c, final_prev, q.d_seq_final, prev_bytes, hipMemcpyDeviceToHost));
   if (cached) {
     std::vector<int32_t> resorted((size_t)n_planners);
     HIP_TRY(c, copy_sync(c, resorted.data(), q.d_seqc_resorted, sizeof(int32_t) * resorted.size(), hipMemcpyDeviceToHost));
@@ -1912,6 +2198,31 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
     for (int32_t v : resorted) sum += v;
     if (n_resorted) *n_resorted = sum;
   }
+  return 0;
+}
+
+// The ticket form (include/fsdp.h): planners [planner_lo, planner_lo + n_planners) of a recording of planners_total, cache off.
+static int submit_sequence(fsdp_ctx* c, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* off, const double* cones,
+                           const double* poses, const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev,
+                           long long* n_replanned, long long* ticket) {
+  if (!c) return 1;
+  const char* who = "fsdp_submit_sequence";
+  if (ticket) *ticket = -1;
+  if (n_replanned) *n_replanned = 0;
+  const SeqCall k{n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, results, compact, final_prev, n_replanned, false};
+  if (int rc = seq_refusals(c, who, k, false)) return rc;
+  if (!ticket) {
+    c->err = std::string(who) + ": ticket is NULL";
+    return 1;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  Batch b;
+  if (int rc = seq_check_batch(c, k, &b)) return rc;
+  Work* q = nullptr;
+  Work::Ticket* t = nullptr;
+  if (int rc = free_ticket(c, who, 1, &q, &t)) return rc;
+  if (int rc = seq_issue(c, *q, *t, b, k, who, frames_in_flight(c, b.n, true))) return rc;
+  *ticket = t->id;
   return 0;
 }
 
@@ -1936,6 +2247,20 @@ int fsdp_plan_sequence_cached_compact(fsdp_ctx* c, int n_planners, int n_steps, 
                                       int8_t* hits, long long* n_resorted) {
   return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true, final_prev, n_replanned, true,
                        hits, n_resorted);
+}
+
+int fsdp_submit_sequence(fsdp_ctx* c, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* off, const double* cones,
+                         const double* poses, const double* initial_prev, fsdp_frame_result* results, double* final_prev, long long* n_replanned,
+                         long long* ticket) {
+  return submit_sequence(c, n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, results, false, final_prev, n_replanned,
+                         ticket);
+}
+
+int fsdp_submit_sequence_compact(fsdp_ctx* c, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* off,
+                                 const double* cones, const double* poses, const double* initial_prev, fsdp_compact_result* results,
+                                 double* final_prev, long long* n_replanned, long long* ticket) {
+  return submit_sequence(c, n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true,
+                         final_prev, n_replanned, ticket);
 }
 
 int fsdp_sort_cache_reset(fsdp_ctx* c, int n_planners) {

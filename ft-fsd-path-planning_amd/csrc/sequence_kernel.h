@@ -156,4 +156,83 @@ __global__ void __launch_bounds__(64) seq_final_kernel(int n_planners, int n_ste
   for (int i = lane; i < PATH_POINTS * 4; i += WAVE) dst[i] = src ? src[i] : NAN;
 }
 
+#ifndef FSDP_EMU
+// ---- planner slices of a recording (fsdp_submit_sequence, sequence_slice.h) -----------------------------------------------------
+// A slice is n_steps segments `total` frames apart; the direct routes of a pass (sort_kernel's StageIn, assemble_kernel writing
+// into the caller's buffer) move one contiguous segment only.  These two kernels move a slice between the caller's page-locked
+// arrays and the slot's dense device copies, in front of the pass and behind its assembly: pure data movement over PCIe, no
+// LDS, any grid walks any slice.
+
+// grid = 256 x 256 like stage_in_kernel (~1 MB of loads on the wire).  One wavefront per frame and trip: its offset (rebased into
+// the gap-free device CSR), its pose and its cone rows — 24 bytes each, so whether the source and the destination of a frame
+// are 16-byte aligned depends on the parity of the two row indices: 16 bytes per lane where both are, 8 where not.  What the
+// host checked at submit (sequence_slice.h seq_slice_segments) is clamped again: the caller's arrays are his not to touch, but a
+// touched offset must not send a store beyond the device copies.
+__global__ void __launch_bounds__(256) seq_slice_in_kernel(fsdp_seq_slice_in_args a) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  const int lane = (int)(threadIdx.x & 63), waves_per_block = (int)(blockDim.x >> 6);
+  const long long wave0 = (long long)blockIdx.x * waves_per_block + (threadIdx.x >> 6), n_waves = (long long)gridDim.x * waves_per_block;
+  const long long nf = a.s.frames(), rows = a.rows;
+  for (long long f = wave0; f < nf; f += n_waves) {
+    const long long step = f / a.s.n;
+    const long long r = step * a.s.total + (f - step * a.s.n);  // (relative to the slice's first frame: the sources start there)
+    const SeqSeg g = a.seg[step];
+    const int32_t o0 = a.src_off[r], o1 = a.src_off[r + 1];
+    long long d0 = seq_dense_offset(g, o0), cnt = (long long)o1 - o0, s0 = (long long)o0 - a.cone_base;
+    d0 = d0 < 0 ? 0 : (d0 > rows ? rows : d0);
+    cnt = cnt < 0 ? 0 : (cnt > rows - d0 ? rows - d0 : cnt);
+    if (s0 < 0 || s0 + cnt > a.src_rows) cnt = 0;
+    if (lane == 0) {
+      a.dst_off[f] = (int32_t)d0;
+      if (f == nf - 1) a.dst_off[nf] = (int32_t)rows;
+    }
+    if (lane < 4) a.dst_poses[4 * f + lane] = __builtin_nontemporal_load(a.src_poses + 4 * r + lane);
+    const double* src = a.src_cones + 3 * s0;
+    double* dst = a.dst_cones + 3 * d0;
+    const long long nd = 3 * cnt;
+    if ((((unsigned long long)src | (unsigned long long)dst) & 15ull) == 0) {
+      const long long n2 = nd >> 1;
+      for (long long k = lane; k < n2; k += WAVE) ((d2*)dst)[k] = __builtin_nontemporal_load((const d2*)src + k);
+      if ((nd & 1) && lane == 0) dst[nd - 1] = __builtin_nontemporal_load(src + nd - 1);
+    } else {
+      for (long long k = lane; k < nd; k += WAVE) dst[k] = __builtin_nontemporal_load(src + k);
+    }
+  }
+  // the slice's initial_prev rows: adjacent in the recording's block (planners lo .. lo + n)
+  if (a.src_init != nullptr) {
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
+    const long long nd = (long long)a.s.n * (PATH_POINTS * 4);
+    if ((((unsigned long long)a.src_init | (unsigned long long)a.dst_init) & 15ull) == 0) {
+      for (long long k = tid; k < (nd >> 1); k += nth) ((d2*)a.dst_init)[k] = __builtin_nontemporal_load((const d2*)a.src_init + k);
+    } else {
+      for (long long k = tid; k < nd; k += nth) a.dst_init[k] = __builtin_nontemporal_load(a.src_init + k);
+    }
+  }
+}
+
+// Behind the pass's assembly, which left the records (full or compact, rec_bytes each) dense in the slot's result block: the
+// records of step t to results[t * total + lo ...] and the slice's final_prev rows to theirs, in the caller's page-locked arrays.
+// One wavefront per record and trip, like assemble_kernel: consecutive lanes on consecutive 8-byte words of the destination (a
+// record is a multiple of 8 bytes, not of 16), one division per record; the grid is capped like launch_assemble's for stores
+// towards host memory.
+__global__ void __launch_bounds__(256) seq_slice_out_kernel(fsdp_seq_slice_out_args a) {
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
+  const int lane = (int)(threadIdx.x & 63), waves_per_block = (int)(blockDim.x >> 6), rec = a.rec_bytes / 8;
+  const long long wave0 = (long long)blockIdx.x * waves_per_block + (threadIdx.x >> 6), n_waves = (long long)gridDim.x * waves_per_block;
+  const long long nf = a.s.frames();
+  const unsigned long long* src = (const unsigned long long*)a.src_records;
+  unsigned long long* dst = (unsigned long long*)a.dst_records;  // (the slice's first record: planner lo of step 0)
+  for (long long f = wave0; f < nf; f += n_waves) {
+    const long long step = f / a.s.n;
+    const unsigned long long* s = src + f * rec;
+    unsigned long long* d = dst + (step * a.s.total + (f - step * a.s.n)) * rec;
+    for (int w = lane; w < rec; w += WAVE) d[w] = s[w];
+  }
+  if (a.dst_final != nullptr) {
+    const long long nd = (long long)a.s.n * (PATH_POINTS * 4);
+    for (long long k = tid; k < nd; k += nth) a.dst_final[k] = a.src_final[k];
+  }
+}
+#endif  // FSDP_EMU
+
 }  // namespace fsdp

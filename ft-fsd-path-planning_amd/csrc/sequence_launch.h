@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include "sequence_slice.h"  // SeqSlice, SeqSeg
 #include "sort_cache.h"  // SortCacheView, SeqSpecRec
 
 namespace fsdp {
@@ -37,6 +38,35 @@ struct fsdp_seq_launch_args {
 // header memset -> seq_mark_kernel -> seq_chain_kernel -> seq_final_kernel on `stream`.  Weak: a library built from fsdp_lib.hip
 // alone (the variant builds of tools/) has no sequence kernels, and fsdp_plan_sequence says so.
 extern "C" __attribute__((weak)) void fsdp_seq_launch(hipStream_t stream, const fsdp_seq_launch_args* a);
+
+// A planner slice of a recording (fsdp_submit_sequence with page-locked arrays): seq_slice_in_kernel in front of the pass,
+// seq_slice_out_kernel behind its assembly.  Every src of the first and every dst of the second is the device view of a
+// page-locked host array, already advanced to the slice's first frame (planner lo of step 0) or first row.
+struct fsdp_seq_slice_in_args {
+  fsdp::SeqSlice s;
+  const fsdp::SeqSeg* seg;   // n_steps + 1 segments (the ticket's page-locked block)
+  const int32_t* src_off;    // cone_offsets + lo
+  const double* src_cones;   // cones_xyt + 3 * cone_base: the lowest row any segment reads
+  const double* src_poses;   // poses + 4 * lo
+  const double* src_init;    // initial_prev + lo rows, or NULL
+  int32_t cone_base;
+  long long src_rows;        // rows behind src_cones that the segments span
+  long long rows;            // cone rows of the slice = seg[n_steps].dst
+  int32_t* dst_off;          // the slot's dense device copies: offsets from 0 without gaps, call order (step-major)
+  double* dst_cones;
+  double* dst_poses;
+  double* dst_init;
+};
+struct fsdp_seq_slice_out_args {
+  fsdp::SeqSlice s;
+  int rec_bytes;             // sizeof(fsdp_frame_result) or sizeof(fsdp_compact_result): multiples of 8
+  const void* src_records;   // the slot's result block, dense
+  void* dst_records;         // results + lo records
+  const double* src_final;   // the slot's final_prev rows
+  double* dst_final;         // final_prev + lo rows, or NULL
+};
+extern "C" __attribute__((weak)) void fsdp_seq_launch_slice_in(hipStream_t stream, const fsdp_seq_slice_in_args* a);
+extern "C" __attribute__((weak)) void fsdp_seq_launch_slice_out(hipStream_t stream, const fsdp_seq_slice_out_args* a);
 
 // fsdp_plan_sequence_cached (sequence_cache_kernel.h, compiled as sequence_cache_lib.hip): the speculative sorting kernels in the
 // place of the plain ones, and the cache chain between the sorting results and the matching.

@@ -32,6 +32,16 @@ def shard_ranges(n: int, parts: int) -> List[Tuple[int, int]]:
     return [(g * n // parts, (g + 1) * n // parts) for g in range(parts)]
 
 
+def planner_slices(n_planners: int, parts: int) -> List[Tuple[int, int]]:
+    """The planners of a recording cut for `parts` contexts: [g*n/G, (g+1)*n/G) — ordered, disjoint, covering [0, n), sizes within
+    one of each other; with more parts than planners some slices are empty.  A sequence in step-major layout is cut by PLANNER
+    (every planner's chain stays on one context), which is not a contiguous range of its frames (fsdp_submit_sequence)."""
+    n_planners, parts = int(n_planners), int(parts)
+    if n_planners < 0 or parts < 1:
+        raise ValueError("planner_slices: n_planners >= 0 and parts >= 1")
+    return [(g * n_planners // parts, (g + 1) * n_planners // parts) for g in range(parts)]
+
+
 def visible_devices() -> List[int]:
     return list(range(int(_capi.load().fsdp_device_count())))
 
@@ -70,6 +80,16 @@ class MultiTicket:
 
     def __init__(self, parts, out, host_s=0.0):
         self.parts, self.out, self.host_s = parts, out, host_s
+
+
+class MultiSequenceTicket(MultiTicket):
+    """A recording in flight as planner slices (MultiPlanner.submit_sequence)."""
+
+    __slots__ = ("final",)
+
+    def __init__(self, parts, out, final, host_s=0.0):
+        super().__init__(parts, out, host_s)
+        self.final = final
 
 
 class MultiPlanner:
@@ -209,20 +229,82 @@ class MultiPlanner:
             except Exception:
                 pass
 
-    def collect(self, ticket: MultiTicket) -> np.ndarray:
-        """Wait for the batch; returns the page-locked result array the GPUs wrote (not a copy)."""
+    def collect(self, ticket: MultiTicket):
+        """Wait for the batch; returns the page-locked result array the GPUs wrote (not a copy) — for a ticket of submit_sequence
+        (results, final_prev, n_replanned) like Context.plan_sequence."""
         parts, ticket.parts = ticket.parts, []
+        again = 0
         for k, (g, t) in enumerate(parts):
             try:
-                self.ctx[g].collect(t)
+                got = self.ctx[g].collect(t)
+                if isinstance(t, _capi.SequenceTicket):
+                    again += got[2]
             except BaseException:
                 self._drain(parts[k + 1 :])  # (the other GPUs still write their ranges of the block)
                 raise
+        if isinstance(ticket, MultiSequenceTicket):
+            return ticket.out, ticket.final, again
         return ticket.out
 
     def plan_batch(self, offsets, cones, poses, prev_paths=None, compact: bool = False) -> np.ndarray:
         """The bytes of ``Context.plan_batch`` / ``plan_batch_sequential`` over the whole batch, planned on all GPUs."""
         return self.collect(self.submit(offsets, cones, poses, prev_paths, compact=compact))
+
+    # ---- whole stateful sequences, sharded by planner ----------------------------------------------------------------
+    def submit_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False,
+                        out: np.ndarray | None = None) -> MultiSequenceTicket:
+        """Context.plan_sequence's recording (n_planners planners x T steps, step-major) cut by PLANNER over the contexts
+        (planner_slices) and enqueued as one sequence ticket each (fsdp_submit_sequence); contexts that get no planner are
+        skipped.  Page-locked arrays are sharded zero-copy — every context reads its planners' segments of the caller's arrays in
+        place; a pageable recording is staged ONCE into page-locked buffers that all contexts read.  Results and final_prev rows
+        are written by the GPUs into one page-locked array each (``out``: the recording's records; default: blocks of the planner's
+        pool).  The arrays must stay untouched until ``collect``, which returns (results, final_prev, n_replanned)."""
+        import time
+
+        t0 = time.perf_counter()
+        c0 = self.ctx[0]
+        n_planners = int(n_planners)
+        offsets, cones, poses, n = _capi.Context._prep_any_base(cone_offsets, cones_xyt, poses)
+        if n_planners < 1 or n < 1 or n % n_planners:
+            raise ValueError(f"submit_sequence: {n} frames are not a whole number (>= 1) of steps of {n_planners} planners")
+        init = None
+        if initial_prev is not None:
+            init = c0.pad_paths(initial_prev)
+            if len(init) != n_planners:
+                raise ValueError("initial_prev: one (horizon, 4) path per planner")
+        zero_copy = _capi.is_pinned(offsets) and _capi.is_pinned(poses) and (len(cones) == 0 or _capi.is_pinned(cones))
+        if zero_copy:
+            self.zero_copy_batches += 1
+        else:
+            self.staged_batches += 1
+            st = self._stage[0][self._turn[0] % len(self._stage[0])]
+            self._turn[0] += 1
+            offsets, cones, poses, _ = st.load(offsets, cones[offsets[0] : offsets[-1]], poses, None)
+        if init is not None and not _capi.is_pinned(init):
+            init = _capi.pinned_copy(init)
+        dt = c0.compact_dtype if compact else c0.result_dtype
+        if out is None:
+            out = self._pool.get(n, dt)
+        assert out.dtype == dt and len(out) == n and out.flags.c_contiguous
+        rows = c0.shapes.path_points
+        final = self._pool.get(n_planners * rows * 4, np.float64).reshape(n_planners, rows, 4)
+        parts = []
+        try:
+            for g, (lo, hi) in enumerate(planner_slices(n_planners, len(self.ctx))):
+                if hi > lo:
+                    parts.append((g, self.ctx[g].submit_sequence(offsets, cones, poses, hi - lo, initial_prev=init, compact=compact, planner_lo=lo,
+                                                                 planners_total=n_planners, out=out, final_prev_out=final)))
+        except BaseException:
+            self._drain(parts)  # (slices already on their GPUs read the arrays and write the blocks)
+            raise
+        el = time.perf_counter() - t0
+        self.host_seconds += el
+        self.host_frames += n
+        return MultiSequenceTicket(parts, out, final, el)
+
+    def plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False):
+        """The bytes of ``Context.plan_sequence`` — (results, final_prev, n_replanned) — with the planners sharded over the contexts."""
+        return self.collect(self.submit_sequence(cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact))
 
     # ---- a stream of batches ----------------------------------------------------------------------------------------
     def plan_stream(self, batches, depth: int | None = None, compact: bool = False):

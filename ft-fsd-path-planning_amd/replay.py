@@ -188,8 +188,39 @@ def replay_ranked(mission, positions, directions, observations, top_k: int, devi
 FB_READ_PREVIOUS = 1 | 2 | 4 | 8  # path_fallback bits of the branches that read previous_paths[-1] (include/fsdp.h; the frames fsdp_plan_sequence plans again)
 
 
+def _replay_recordings_in_flight(ctxs, chunked):
+    """Recordings (each a list of consecutive chunks (offsets, cones, poses) of one planner) as sequence tickets
+    (fsdp_submit_sequence) over the contexts `ctxs`: as many chunks in flight as the contexts' ticket capacities allow, a
+    recording's next chunk submitted — to the context that planned the previous one — as soon as that one is collected, with the
+    path it left (final_prev -> initial_prev).  -> (per recording the list of its chunks' results, frames planned again)"""
+    from ._capi import pinned_empty
+
+    results = [[None] * len(chunks) for chunks in chunked]
+    # two page-locked final_prev rows per recording, taken in turn: the one chunk k left is read by chunk k + 1 while that writes its own
+    finals = [[pinned_empty((1, ctxs[0].shapes.path_points, 4)) for _ in range(2 if len(chunks) > 1 else 1)] for chunks in chunked]
+    room = [c.ticket_capacity for c in ctxs]
+    waiting = [r for r, chunks in enumerate(chunked) if chunks]
+    inflight, again = [], 0
+
+    def start(r, k, g, prev):
+        inflight.append((g, r, k, ctxs[g].submit_sequence(*chunked[r][k], 1, initial_prev=prev, final_prev_out=finals[r][k % len(finals[r])])))
+        room[g] -= 1
+
+    while waiting or inflight:
+        while waiting and max(room) > 0:
+            start(waiting.pop(0), 0, room.index(max(room)), None)
+        g, r, k, ticket = inflight.pop(0)
+        res, final, n = ctxs[g].collect(ticket)
+        room[g] += 1
+        again += n
+        results[r][k] = res
+        if k + 1 < len(chunked[r]):
+            start(r, k + 1, g, final)
+    return results, again
+
+
 def replay_stateful_batched(mission, positions, directions, observations, device=None, batch_frames: int = 4096, depth: int = 4,
-                            cache: bool = False):
+                            cache: bool = False, multi=None, recordings=None):
     """The recording as ONE planner sees it — consecutive frames chain through previous_paths[-1] (core_calculate_path.py:
     572-573), which the reference reads in its fallbacks only (:202-203, 218-221, 235-236, 531-536, 564-570) — at the speed
     of a batched replay: the recording cut into consecutive calls of `batch_frames` steps of fsdp_plan_sequence (one planner),
@@ -199,7 +230,33 @@ def replay_stateful_batched(mission, positions, directions, observations, device
     seconds of the replay and the number of frames planned again.  (depth: kept for callers of the earlier form, which
     streamed the independent frames; a sequence call is one pass.)
     cache: the planner of a recording made with experimental_performance_improvements=True (fsdp_plan_sequence_cached: the
-    sorting cache chained on the device as well, its entry carried from call to call by the context)."""
+    sorting cache chained on the device as well, its entry carried from call to call by the context).
+    recordings: a list of (positions, directions, observations) INSTEAD of the one recording (pass None for those three) — every
+    recording its own fresh planner, their chunks kept in flight as sequence tickets up to the ticket capacity (a blocking call
+    per chunk leaves the GPU idle between calls); returns a list of result arrays.  multi: a MultiPlanner whose contexts share
+    the recordings (several contexts or GPUs; also for one recording, whose chunks then simply run as tickets on the first
+    context).  Neither goes with cache: the cache-on sequence call has no ticket form."""
+    if multi is not None or recordings is not None:
+        if cache:
+            raise ValueError("replay_stateful_batched: the sorting cache has no ticket form (cache=True goes with one recording and no MultiPlanner)")
+        from ._capi import pinned_copy
+
+        many = recordings if recordings is not None else [(positions, directions, observations)]
+        own = None if multi is not None else PathPlanner(mission, False, device=device)
+        ctxs = multi.ctx if multi is not None else [own._ctx]
+        chunked = []
+        for pos, dirs, obs in many:
+            frames = list(zip(obs, pos, dirs))
+            packed = [pack_frames(frames[lo:lo + batch_frames]) for lo in range(0, len(frames), batch_frames)]
+            chunked.append([(pinned_copy(o, np.int32), pinned_copy(c), pinned_copy(p)) for o, c, p in packed])  # (page-locked: read in place)
+        if chunked and chunked[0]:
+            for c in ctxs:
+                c.plan_sequence(*chunked[0][0], 1)  # warm-up, like replay_batched's
+        t0 = time.perf_counter()
+        parts, again = _replay_recordings_in_flight(ctxs, chunked)
+        sec = time.perf_counter() - t0
+        res = [np.concatenate(p) if p else np.zeros(0, ctxs[0].result_dtype) for p in parts]
+        return (res if recordings is not None else res[0]), sec, again
     planner = PathPlanner(mission, cache, device=device)
     ctx = planner._ctx
     frames = list(zip(observations, positions, directions))
@@ -234,6 +291,8 @@ def main(argv=None):
     ap.add_argument("--batched", action="store_true")
     ap.add_argument("--stateful", action="store_true", help="--batched: one planner's view of the recording (frames chain through the previous path)")
     ap.add_argument("--cache", action="store_true", help="--batched --stateful: the planner has the reference's sorting cache on (fsdp_plan_sequence_cached)")
+    ap.add_argument("--copies", type=int, default=1, help="--batched --stateful: replay this many copies of the recording, each a planner of its own, "
+                                                          "kept in flight as sequence tickets (fsdp_submit_sequence)")
     ap.add_argument("--output-path", "-o", type=Path, default=None)
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--devices", type=str, default=None, help='--batched: GPUs the stream is sharded over from this process, e.g. "0,1,2,3" or "all"')
@@ -269,8 +328,13 @@ def main(argv=None):
     out = {"file": str(a.data_path), "mission": mission.name, "frames": len(positions)}
     if a.batched:
         if a.stateful:
-            res, sec, again = replay_stateful_batched(mission, positions, directions, observations, a.device, batch_frames=a.batch_frames, depth=a.depth,
-                                                      cache=a.cache)
+            if a.copies > 1:
+                many, sec, again = replay_stateful_batched(mission, None, None, None, a.device, batch_frames=a.batch_frames, cache=a.cache,
+                                                           recordings=[(positions, directions, observations)] * a.copies)
+                res = np.concatenate(many)
+            else:
+                res, sec, again = replay_stateful_batched(mission, positions, directions, observations, a.device, batch_frames=a.batch_frames, depth=a.depth,
+                                                          cache=a.cache)
             out.update(frames_planned_again_with_their_predecessors_path=again, sorting_cache=a.cache)
         else:
             devs = None if a.devices is None else ("all" if a.devices == "all" else [int(x) for x in a.devices.split(",")])

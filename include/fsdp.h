@@ -324,6 +324,36 @@ int fsdp_collect(fsdp_ctx* ctx, long long ticket);
 int fsdp_ticket_done(fsdp_ctx* ctx, long long ticket); /* 1: fsdp_collect will not block; 0: still running; -1: unknown ticket */
 int fsdp_ticket_capacity(const fsdp_ctx* ctx);         /* tickets that may be outstanding at the current depth */
 
+/* fsdp_plan_sequence[_compact] as a ticket, and for a planner slice of a recording (the sorting cache must be off; the
+ * cache-on call has no ticket form: its double buffer is swapped once per call, and two tickets on the same planners would
+ * need an ordering the cache does not have).
+ *   Every pointer describes the WHOLE recording of planners_total planners x n_steps steps in the step-major layout of
+ *   fsdp_plan_sequence: cone_offsets has n_steps * planners_total + 1 entries (any base), poses and results hold
+ *   n_steps * planners_total rows, initial_prev and final_prev (either may be NULL) planners_total rows.  The call plans the
+ *   planners [planner_lo, planner_lo + n_planners): its frame (t, p) is recording frame t * planners_total + planner_lo + p, and it
+ *   reads and writes those rows only — the planner-wise counterpart of the cone_offsets[0] != 0 frame slice.  planner_lo = 0
+ *   with planners_total = n_planners is the whole call.
+ *   The ticket is an ordinary ticket: fsdp_collect and fsdp_ticket_done take it, it counts against fsdp_ticket_capacity (4
+ *   beyond that), it may be collected in any order and be in flight next to fsdp_submit tickets of the context.  results,
+ *   final_prev and *n_replanned are valid after fsdp_collect; the buffers must stay untouched from submit to collect.
+ *   The bytes are those of fsdp_plan_sequence on the same planners (records, final_prev rows, n_replanned).  Planners are
+ *   independent, so a recording cut into planner slices — on one context or several, on one GPU or several — gives the bytes
+ *   of one call; so do cuts in time joined by final_prev -> initial_prev, and both cuts together.
+ *   Page-locked arrays are read and written in place: a planner slice is n_steps segments planners_total frames apart, which
+ *   two kernels of the slot's stream move between the caller's arrays and the slot's dense device copies
+ *   (csrc/sequence_kernel.h seq_slice_in_kernel, seq_slice_out_kernel; nothing is rebased or copied on the host); the whole
+ *   call takes the routes of fsdp_submit.  Pageable arrays are accepted: a slice is packed by the host into the ticket's
+ *   page-locked block, results and final_prev go through the ticket's blocks and fsdp_collect copies them out.
+ * Returns an error, with nothing enqueued and the buffers the caller's again: a skidpad context; a context whose sorting cache
+ * is on; n_planners or n_steps < 1; planner_lo < 0 or planner_lo + n_planners > planners_total; a frame count beyond 2^30 - 3
+ * or one the device has no memory for (the context stays usable); results or ticket NULL. */
+int fsdp_submit_sequence(fsdp_ctx* ctx, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* cone_offsets,
+                         const double* cones_xyt, const double* poses, const double* initial_prev, fsdp_frame_result* results,
+                         double* final_prev, long long* n_replanned, long long* ticket);
+int fsdp_submit_sequence_compact(fsdp_ctx* ctx, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* cone_offsets,
+                                 const double* cones_xyt, const double* poses, const double* initial_prev, fsdp_compact_result* results,
+                                 double* final_prev, long long* n_replanned, long long* ticket);
+
 /* The resident form: one batch stays in HBM and is planned again and again (the benchmark's step; a caller that plans the
  * same frames under several global paths / previous paths). */
 int fsdp_upload(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt, const double* poses);
