@@ -432,16 +432,31 @@ __device__ __forceinline__ bool knot_reciprocals(const double* t, int n, double*
   return Grp<G>::ballot(badk) == 0ull;
 }
 
+// The twelve operands every point of knot interval l shares: the knots t(l-2 .. l+3) and the six reciprocals.  Data points
+// come in increasing order and a knot interval holds many of them, so a caller that keeps these in registers fetches them
+// once per interval instead of once per point.
+struct KnotOps {
+  double tm2, tm1, t0, tp1, tp2, tp3;
+  double r01, r02, r03;  // t(l+1..3) - t(l)
+  double rm12, rm13;     // t(l+1..2) - t(l-1)
+  double rm23;           // t(l+1) - t(l-2)
+  template <int A0>
+  __device__ __forceinline__ void load(const double* t, const double* rdt, int l) {
+    tm2 = t[l - 2], tm1 = t[l - 1], t0 = t[l], tp1 = t[l + 1], tp2 = t[l + 2], tp3 = t[l + 3];
+    const double* const rd = rdt + 3 * (l - A0) - 1;  // rd[3 (a - l) + j] = row a, span j
+    r01 = rd[1], r02 = rd[2], r03 = rd[3];
+    rm12 = rd[-3 + 2], rm13 = rd[-3 + 3];
+    rm23 = rd[-6 + 3];
+  }
+};
+
 // fpbspl3 without the coincident-knot selects and with the denominators' reciprocals from the table: the operations on
 // the operands of fpbspl3<true> in its order — same bits (the quotients are div_rcp(num, den, rcp_refined(den))).
 // CHECK: the numerators' exponent band (once per point and knot set is enough: the observation pass).
-template <bool CHECK, int A0 = 1>
-__device__ __forceinline__ void fpbspl3_rd(const double* t, const double* rdt, double x, int l, double* h /*[0..3]*/, int& bad) {
-  const double tm2 = t[l - 2], tm1 = t[l - 1], t0 = t[l], tp1 = t[l + 1], tp2 = t[l + 2], tp3 = t[l + 3];
-  const double* const rd = rdt + 3 * (l - A0) - 1;  // rd[3 (a - l) + j] = row a, span j
-  const double r01 = rd[1], r02 = rd[2], r03 = rd[3];  // t(l+1..3) - t(l)
-  const double rm12 = rd[-3 + 2], rm13 = rd[-3 + 3];   // t(l+1..2) - t(l-1)
-  const double rm23 = rd[-6 + 3];                      // t(l+1) - t(l-2)
+template <bool CHECK>
+__device__ __forceinline__ void fpbspl3_ops(const KnotOps& ko, double x, double* h /*[0..3]*/, int& bad) {
+  const double tm2 = ko.tm2, tm1 = ko.tm1, t0 = ko.t0, tp1 = ko.tp1, tp2 = ko.tp2, tp3 = ko.tp3;
+  const double r01 = ko.r01, r02 = ko.r02, r03 = ko.r03, rm12 = ko.rm12, rm13 = ko.rm13, rm23 = ko.rm23;
   bool ok = true;
   auto quot = [&](double num, double den, double r) {
     if constexpr (CHECK) ok = ok & ((num == 0.0) | ((num >= 0x1p-255) & (num <= 0x1p255)));
@@ -491,6 +506,13 @@ __device__ __forceinline__ void fpbspl3_rd(const double* t, const double* rdt, d
   h[2] = h3;
   h[3] = h4;
   if constexpr (CHECK) bad |= (int)!ok;
+}
+
+template <bool CHECK, int A0 = 1>
+__device__ __forceinline__ void fpbspl3_rd(const double* t, const double* rdt, double x, int l, double* h /*[0..3]*/, int& bad) {
+  KnotOps ko;
+  ko.load<A0>(t, rdt, l);
+  fpbspl3_ops<CHECK>(ko, x, h, bad);
 }
 
 // ---- 4-stage systolic Givens pipeline (degree 3) ------------------------------------------------------
@@ -869,6 +891,10 @@ struct ResidualBatch {
 
   template <class WS>
   __device__ __forceinline__ void compute(WS& ws, int cnt, int n, double* tbuf, int32_t* fbuf) const {
+    if constexpr (HELD) {
+      compute_held(ws, cnt, n, tbuf, fbuf);
+      return;
+    }
     const int lane = Grp<G>::lane();
 #pragma unroll
     for (int q = 0; q < ROUNDS; q++) {
@@ -897,6 +923,71 @@ struct ResidualBatch {
       }
       if (r < cnt) {
         tbuf[r] = term;
+        if constexpr (FLAGS) fbuf[r] = (lv[q] > lpv[q]) ? 1 : 0;
+      }
+    }
+  }
+
+  // compute() of the four-lane refit (fit_kernel<4>: it alone has the registers) in three phases: operand loads,
+  // register-only arithmetic of all rounds, then the stores together.  A lane's rounds are the points base + q G + lane, and a
+  // knot interval holds many points: nearly always they lie in one interval and read the same 20 operands (12 of the basis
+  // values, 8 coefficients).  Every lane fetches the operands of its own first round; its other rounds reuse them when no
+  // lane of the group has a round in another interval (ballot: the group's control flow stays uniform), else every round
+  // fetches its own as compute() does.  The operations per point and their operands are compute()'s: same bits.  Nothing is
+  // held beyond the call: c changes from pass to pass, and rd is rebuilt before every f(p) pass.
+  static constexpr bool HELD = RC && G == 4;
+  template <class WS>
+  __device__ __forceinline__ void compute_held(WS& ws, int cnt, int n, double* tbuf, int32_t* fbuf) const {
+    static_assert(K == 3, "the reciprocal table serves the cubic fit");
+    const int lane = Grp<G>::lane();
+    double term[ROUNDS];
+    auto coefficients = [&](int lq, double(&cv)[2][4]) {  // of a point with FITPACK's l = lq
+#pragma unroll
+      for (int d = 0; d < 2; d++)
+#pragma unroll
+        for (int j = 1; j <= k1; j++) cv[d][j - 1] = ws.c[lq - k2 + d * n + j];
+    };
+    auto round_term = [&](int q, const double(&hb)[4], const double(&cv)[2][4]) {
+      double tq = 0.0;
+#pragma unroll
+      for (int d = 0; d < 2; d++) {
+        double fac = 0.0;
+#pragma unroll
+        for (int j = 1; j <= k1; j++) fac = fac + cv[d][j - 1] * hb[j - 1];
+        double dv = 1.0 * (fac - (d == 0 ? xv[q] : yv[q]));  // w = 1
+        tq = tq + dv * dv;
+      }
+      return tq;
+    };
+    bool flat = true;
+#pragma unroll
+    for (int q = 1; q < ROUNDS; q++) flat = flat & (lv[q] == lv[0]);
+    int unused = 0;
+    if (Grp<G>::ballot(!flat) == 0ull) {
+      KnotOps ko;
+      double cv[2][4];
+      ko.template load<WS::RD_A0>(ws.t, ws.rd, lv[0] - 1);  // (lv = FITPACK's l = interval + 1)
+      coefficients(lv[0], cv);
+#pragma unroll
+      for (int q = 0; q < ROUNDS; q++) {
+        double hb[4];
+        fpbspl3_ops<false>(ko, hv[q][0], hb, unused);
+        term[q] = round_term(q, hb, cv);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < ROUNDS; q++) {
+        double hb[4], cv[2][4];
+        fpbspl3_rd<false, WS::RD_A0>(ws.t, ws.rd, hv[q][0], lv[q] - 1, hb, unused);
+        coefficients(lv[q], cv);
+        term[q] = round_term(q, hb, cv);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < ROUNDS; q++) {
+      const int r = q * G + lane;
+      if (r < cnt) {
+        tbuf[r] = term[q];
         if constexpr (FLAGS) fbuf[r] = (lv[q] > lpv[q]) ? 1 : 0;
       }
     }
