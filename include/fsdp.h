@@ -61,7 +61,8 @@ enum {
   /* fixed device capacities exceeded (the reference's buffers grow without bound) */
   FSDP_OVERFLOW_CONES = 201, /* more than 8192 cones in a frame */
   FSDP_OVERFLOW_ENDS = 202,  /* more than 4096 raw end configurations on one side */
-  FSDP_OVERFLOW_PATH = 203,
+  FSDP_OVERFLOW_PATH = 203,  /* the working polyline (1408 points): more than 1357 dense samples of the first fit, or a global-path
+                                slice of more than 1408 points (see "Capacities" below) */
   FSDP_OVERFLOW_KNOTS = 204, /* more than 256 knots in a spline (fits beyond the packed kernels' 16 / 32 / 64 are re-planned by the
                                 one-frame-per-wavefront kernel, which keeps 256; a skidpad step: 64) */
   FSDP_OVERFLOW_CLUSTERS = 205, /* skidpad relocalization: more than 64 centre clusters */
@@ -82,8 +83,21 @@ enum {
  * mpc_prediction_horizon > 40 (rows of a result path) in the standard build; > 8, > 16, > 64 in the wide build
  * (FSDP_WIDE_SHAPES above).  Refused per frame, with a status and never truncated:
  * more than 8192 cones (201), more than 4096 raw end configurations on a side (202), a working polyline beyond 1408 points
- * (203), more than 256 knots in a spline (204; FITPACK's own bound is nest = m + 2k, utils/spline_fit.py:117 — the noisiest
- * frames of the fuzz sets end with 171), more than 64 skidpad centre clusters (205). */
+ * (203: see below), more than 256 knots in a spline (204; FITPACK's own bound is nest = m + 2k, utils/spline_fit.py:117 — the noisiest
+ * frames of the fuzz sets end with 171), more than 64 skidpad centre clusters (205).
+ *
+ * The working polyline (203).  A frame's path is built in a polyline of 1408 points.  A frame is refused with 203 when
+ *   - its first fit (fit_matches_as_spline, core_calculate_path.py:207-223) yields MORE THAN 1357 dense samples, i.e.
+ *     len(np.arange(0, max_u, predict_every)) > 1357 with max_u the chord length of the points the fit is given: the polyline
+ *     keeps room for the point connect_path_to_car may put in front (1) and the points extend_path may append (up to 50; it
+ *     appends 49 or 29), whether or not the frame needs either — 1357 samples are planned, 1358 are refused; or
+ *   - a global path is set and MORE THAN 1408 of its points lie within 30 m of the car (:514-529) — 1408 are planned.
+ * fsdp_create applies the same reserve to the refit's sampling: it refuses ceil(1.5 mpc_path_length / predict_every) + 51 > 1408
+ * (1357 samples are accepted, 1358 are not), and a predict_every below 0.05.
+ * A frame refused with 203 keeps what sorting and matching computed (sorted indices, virtual cones, matches — those stages
+ * finished); every row of its path is NaN, n_dense is 0, and path_fallback holds the bits set before the first fit
+ * (FSDP_FB_PREVIOUS_CENTER / FSDP_FB_SPLINE_ERROR).  No other frame of the batch is affected, and in fsdp_plan_sequence the
+ * planner's previous path stays what it was, as for every frame without a path.  (tests/test_polyline_capacity.py) */
 
 /* path_fallback bits */
 enum {

@@ -252,9 +252,15 @@ int fsdo_result_size(void) { return (int)sizeof(fsdo_frame_result); }
 // calculate_path_in_global_frame): up to max_fits records of FSDO_FIT_STRIDE doubles [k, n, t[0..n), cx[0..n), cy[0..n)]
 // (n <= FSDO_FIT_KNOTS, longer knot vectors are truncated and flagged by n > FSDO_FIT_KNOTS).  Returns the number of fits.
 int fsdo_plan_frame_capture(const double* cones_xyt, int n, const double* pose, fsdo_frame_result* out, double* fits, int max_fits) {
+  return fsdo_plan_frame_global_capture(cones_xyt, n, pose, nullptr, nullptr, 0, out, fits, max_fits);
+}
+
+// the same of fsdo_plan_frame_global: a planner with a previous path and / or a global path
+int fsdo_plan_frame_global_capture(const double* cones_xyt, int n, const double* pose, const double* prev40x4, const double* gpath_xy,
+                                   int n_gpath, fsdo_frame_result* out, double* fits, int max_fits) {
   std::vector<fsdo::Spline> cap;
   fsdo::g_fit_capture = &cap;
-  fsdo_plan_frame(cones_xyt, n, pose, out);
+  fsdo_plan_frame_global(cones_xyt, n, pose, prev40x4, gpath_xy, n_gpath, out);
   fsdo::g_fit_capture = nullptr;
   for (int i = 0; i < (int)cap.size() && i < max_fits; i++) {
     double* r = fits + (size_t)i * FSDO_FIT_STRIDE;

@@ -16,9 +16,10 @@ extern "C" {
 PROBE_API int probe_path_cap() { return fsdp::PATH_CAP; }
 // params17: the configuration constants in the order of fsdp::Params (ints as doubles); default_path: PATH_POINTS x 4
 // (emu_default_path of the same parameters).  mid_out: n_frames x 4 int32 (status, fallback, off, n); u_out: n_frames x PATH_CAP
-// (the first n entries of a frame with status 0 are its parameter values).
+// (the first n entries of a frame with status 0 are its parameter values).  gpath: (n_gpath, 2) or NULL — a context with a global
+// path, whose three kernels are the 32-knot instantiations; prev_paths: n_frames x PATH_POINTS x 4 or NULL.
 PROBE_API void probe_refit_polyline(int n_frames, const double* poses, const void* matched, const double* default_path, const double* v,
-                          int32_t* mid_out, double* u_out) {
+                          int32_t* mid_out, double* u_out, const double* gpath, int n_gpath, const double* prev_paths) {
   const fsdp::Params prm = {(int32_t)v[0], (int32_t)v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[12],
                             (int32_t)v[13], (int32_t)v[14], (int32_t)v[15], (int32_t)v[16]};
   constexpr int G = fsdp::PATH_G_SPLIT;
@@ -29,8 +30,12 @@ PROBE_API void probe_refit_polyline(int n_frames, const double* poses, const voi
   std::vector<int> retry((size_t)n_frames + 1, 0);
   const unsigned per = 64 / G;
   emu::launch(((unsigned)n_frames + per - 1) / per, 64, [&]() {
-    fsdp::path_prep_kernel<G, fsdp::FIT_KNOTS>(n_frames, poses, (const fsdp::MatchOut*)matched, default_path, nullptr, nullptr, 0, ar,
-                                               out.data(), mid.data(), retry.data(), &prm);
+    if (gpath)
+      fsdp::path_prep_kernel<G, fsdp::WIDE_KNOTS>(n_frames, poses, (const fsdp::MatchOut*)matched, default_path, prev_paths, gpath, n_gpath, ar,
+                                                  out.data(), mid.data(), retry.data(), &prm);
+    else
+      fsdp::path_prep_kernel<G, fsdp::FIT_KNOTS>(n_frames, poses, (const fsdp::MatchOut*)matched, default_path, prev_paths, nullptr, 0, ar,
+                                                 out.data(), mid.data(), retry.data(), &prm);
   });
   for (int f = 0; f < n_frames; f++) {
     memcpy(mid_out + 4 * f, &mid[f], sizeof(fsdp::PathMid));

@@ -266,14 +266,18 @@ class params:
 FIT_KNOTS, FIT_STRIDE, MAX_FITS = 48, 2 + 3 * 48, 6
 
 
-def plan_frame_capture(xyt, pose):
-    """(result row, [(k, n, t, cx, cy), ...]): the frame and every smoothing spline it fitted, in call order."""
+def plan_frame_capture(xyt, pose, prev=None, global_path=None):
+    """(result row, number of fits, [(k, n, t, cx, cy), ...]): the frame and every smoothing spline it fitted, in call order; prev /
+    global_path as plan_frame_global takes them."""
     xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
     pose = np.ascontiguousarray(pose, dtype=np.float64)
     out = np.zeros(1, dtype=RESULT_DTYPE)
     buf = np.zeros((MAX_FITS, FIT_STRIDE))
-    lib().fsdo_plan_frame_capture.restype = ctypes.c_int
-    nf = lib().fsdo_plan_frame_capture(_p(xyt), ctypes.c_int(len(xyt)), _p(pose), ctypes.c_void_p(out.ctypes.data), _p(buf), ctypes.c_int(MAX_FITS))
+    pp = None if prev is None else _p(np.ascontiguousarray(prev, dtype=np.float64))
+    gp = None if global_path is None else np.ascontiguousarray(global_path, dtype=np.float64).reshape(-1, 2)
+    lib().fsdo_plan_frame_global_capture.restype = ctypes.c_int
+    nf = lib().fsdo_plan_frame_global_capture(_p(xyt), ctypes.c_int(len(xyt)), _p(pose), pp, None if gp is None else _p(gp),
+                                              ctypes.c_int(0 if gp is None else len(gp)), ctypes.c_void_p(out.ctypes.data), _p(buf), ctypes.c_int(MAX_FITS))
     fits = []
     for i in range(min(nf, MAX_FITS)):
         k, n = int(buf[i, 0]), int(buf[i, 1])

@@ -30,8 +30,9 @@ def lib():
     return _lib
 
 
-def polylines(offsets, cones, poses, prm=None):
-    """[(status, m, U[0..m))] per frame: what path_prep_kernel hands the refit under the parameters prm (a dict of overrides)."""
+def polylines(offsets, cones, poses, prm=None, global_path=None, prev_paths=None):
+    """[(status, m, U[0..m))] per frame: what path_prep_kernel hands the refit under the parameters prm (a dict of overrides);
+    global_path: (n, 2) as Context.set_global_path takes it, or None; prev_paths: (frames, PATH_POINTS, 4) or None."""
     cap = lib().probe_path_cap()
     with emu_lib.params(prm or {}):
         s = emu_lib.sort(offsets, cones, poses)
@@ -43,8 +44,13 @@ def polylines(offsets, cones, poses, prm=None):
     u = np.zeros((n, cap))
     v = oracle_lib.param_vector(prm)
     d = ctypes.POINTER(ctypes.c_double)
+    pv = None if prev_paths is None else np.ascontiguousarray(prev_paths, np.float64)
+    assert pv is None or pv.shape == (n, emu_lib.PATH_POINTS, 4)
+    gp = None if global_path is None else np.ascontiguousarray(global_path, np.float64).reshape(-1, 2)
     lib().probe_refit_polyline(ctypes.c_int(n), poses.ctypes.data_as(d), ctypes.c_void_p(m.ctypes.data), dp.ctypes.data_as(d),
-                               v.ctypes.data_as(d), mid.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), u.ctypes.data_as(d))
+                               v.ctypes.data_as(d), mid.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), u.ctypes.data_as(d),
+                               None if gp is None else gp.ctypes.data_as(d), ctypes.c_int(0 if gp is None else len(gp)),
+                               None if pv is None else pv.ctypes.data_as(d))
     return [(int(mid[f, 0]), int(mid[f, 3]), u[f, : mid[f, 3]].copy()) for f in range(n)]
 
 
