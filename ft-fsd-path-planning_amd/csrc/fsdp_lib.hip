@@ -96,7 +96,6 @@ struct Work {
   int32_t* d_skid_status = nullptr;       // skid_reloc_kernel's status of the step this slot holds
   bool skid_attempted = true;             // ... which ran for that step (not once every planner is relocalized)
   SortSharedBig* d_sort_big = nullptr;    // frame states of sort_big_kernel, allocated when the route is first needed
-  int cache_base = 0;                     // sorting cache: planner of the slot's frame 0 (a chunk of a blocking call)
   // fsdp_plan_sequence (sequence_kernel.h): the run-head list of a sequence pass, the planners' initial and final previous paths
   int* d_seq = nullptr;                   // [0] heads, [1] frames planned again, then (frame, predecessor) per head
   double* d_seq_init = nullptr;           // (planners, 40, 4)
@@ -124,16 +123,16 @@ struct Work {
   bool ran_big = false, ran_retry = false, unverified = false, pass_skid = false;
   // A sequence pass (fsdp_plan_sequence*, fsdp_submit_sequence*) as its ticket describes it: the ticket's pass — and the rerun
   // fsdp_collect issues when the pass lacked a route — resolves the planners' previous-path chains between the path stage and the
-  // assembly.  The pointers are the caller's, valid and untouched until fsdp_collect like the batch's.
+  // assembly.  enqueue_ticket hands it to the launches inside the pass's description (Pass::sq): nothing about the pass in progress
+  // is kept on the context.  The pointers are the caller's, valid and untouched until fsdp_collect like the batch's.
   struct SeqPass {
     bool on = false;
     SeqSlice s = {};           // planners [lo, lo + n) of a recording of `total`, n_steps steps (whole call: lo = 0, total = n)
-    bool cached = false;       // fsdp_plan_sequence_cached: the speculative sorting kernels and the cache chain (never cache_call)
+    bool cached = false;       // fsdp_plan_sequence_cached: the speculative sorting kernels and the cache chain (never with Ticket::cache_lo)
     const char* who = "";      // the entry point, for error texts
     const int32_t* off = nullptr;  // the whole recording's arrays (a slice's frames are not contiguous in them: t.batch holds counts only)
     const double* cones = nullptr;
     const double* poses = nullptr;
-    fsdp_frame_result* results = nullptr;
     const double* init = nullptr;   // the slice's first initial_prev row, or NULL
     double* final_prev = nullptr;   // the slice's first final_prev row, or NULL
     long long* n_replanned = nullptr;
@@ -141,7 +140,8 @@ struct Work {
     double* final_dev = nullptr;    // where seq_final_kernel writes: page-locked host memory (the caller's rows or the ticket's h_fin), or the slot's d_seq_final
     bool fin_staged = false;        // final_prev goes through h_fin (fsdp_collect copies it out)
   };
-  // tickets of fsdp_submit / fsdp_skidpad_submit / fsdp_submit_sequence queued on this slot's stream (id -1: free entry)
+  // tickets of fsdp_submit / fsdp_skidpad_submit / fsdp_submit_sequence queued on this slot's stream (id -1: free entry).  A ticket
+  // holds the whole description of its pass: enqueue_ticket launches the first pass and fsdp_collect's rerun from it alone.
   struct Ticket {
     long long id = -1;
     bool skid = false;
@@ -164,7 +164,18 @@ struct Work {
     double* h_fin = nullptr;               // pinned + mapped: seq_final_kernel writes a pageable caller's final_prev rows here
     size_t cap_stage = 0, cap_in = 0, cap_info = 0, cap_seg = 0, cap_fin = 0;  // their capacities (grow_pinned)
     SeqPass sq;                            // a sequence ticket's pass
+    int cache_lo = -1;                     // >= 0: a chunk of a lock-step call that advances the sorting cache (the _cached sorting
+                                           // kernels); its frame 0 is this planner
     hipEvent_t done = nullptr;             // recorded behind the ticket's last command
+    // the entry is free again: what the caller owned, and what described his pass, is forgotten
+    void release() {
+      id = -1;
+      user_results = nullptr;
+      user_info = nullptr;
+      compact = false;
+      sq = SeqPass();
+      cache_lo = -1;
+    }
   } tk[SLOT_QUEUE];
 };
 
@@ -271,10 +282,7 @@ struct fsdp_ctx {
   std::vector<int32_t> cache_region;          // rows of a planner's region: the most cones it was ever given
   int8_t* d_cache_hits = nullptr;
   std::vector<int8_t> cache_hits;             // codes of the most recent call
-  bool cache_call = false;                    // the call in progress advances the cached planners
-  // the sequence pass enqueue_ticket is launching (its ticket's description), else NULL: launch_pass puts the chain kernels
-  // between the path stage and the assembly
-  const Work::SeqPass* sequence = nullptr;
+  // (no field says what the call in progress is: a pass is described by the Pass its caller builds — for a ticket, from the ticket)
 };
 // (an empty route launch costs a stream ~1 % of a pass; a pass repeated because the kernel was missing costs a whole pass and
 // stalls the caller's collect: once needed, a route stays for a long time)
@@ -433,6 +441,18 @@ static bool is_pinned(const void* p, size_t bytes) {
   const char* de = (const char*)device_view((const char*)p + bytes - 1);
   return de != nullptr && de - dv == (ptrdiff_t)(bytes - 1);
 }
+// Where a ticket's pass writes for the caller: `user` itself if its `bytes` are page-locked over their whole extent (the kernels
+// write it over PCIe), else the ticket's own mapped block of `count` T's, grown with room for `want` (*staged: fsdp_collect copies
+// it out).  *dev: the device view of whichever it is.
+template <class T>
+static int host_target(fsdp_ctx* c, T* user, size_t bytes, T*& block, size_t& cap, size_t count, size_t want, const char* what, T** dev, bool* staged) {
+  *staged = !is_pinned(user, bytes);
+  if (*staged) HIP_TRY(c, grow_pinned(block, cap, count, hipHostMallocMapped, want));
+  *dev = (T*)device_view(*staged ? block : user);
+  if (*dev) return 0;
+  c->err = std::string("internal: ") + what + " is not mapped into the device's address space";
+  return 2;
+}
 // every row of the batch the staging kernels read (stage_in_kernel, sort_kernel's StageIn) is page-locked: the offsets, the cone
 // rows from cones + 3 * off[0], the poses and the previous paths
 static bool inputs_pinned(const Batch& b) {
@@ -471,7 +491,8 @@ static void mark(const Work& q, StageEvents* t, MarkKind kind = MARK_PLAIN) {
 
 static bool sort128(const fsdp_ctx* c, const Inputs& in) { return in.max_cones <= SortShared128::MAX_N && !c->no_sort128; }
 
-static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
+// the sorting cache as a launch sees it whose frame 0 is planner `base`
+static SortCacheView cache_view(const fsdp_ctx* c, int base) {
   const int p = c->cache_cur, x = 1 - p;
   SortCacheView v;
   v.prev = c->d_cache_hdr[p];
@@ -481,15 +502,15 @@ static SortCacheView cache_view(const fsdp_ctx* c, const Work& q) {
   v.next_xyt = c->d_cache_xyt[x];
   v.next_off = c->d_cache_off[x];
   v.hits = c->d_cache_hits;
-  v.base = q.cache_base;
+  v.base = base;
   return v;
 }
 
 // fsdp_plan_sequence_cached: what sequence_cache_lib.hip's launches need, once per pass (launch_pass)
-static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs& in) {
+static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs& in, const SeqSlice& s) {
   fsdp_seqc_launch_args a;
-  a.n_planners = c->sequence->s.n;
-  a.n_steps = c->sequence->s.n_steps;
+  a.n_planners = s.n;
+  a.n_steps = s.n_steps;
   a.off = in.d_off;
   a.cones = in.d_cones;
   a.poses = in.d_poses;
@@ -500,57 +521,61 @@ static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs&
   a.small = sort128(c, in);
   a.prm = c->d_params;
   a.rec = q.d_seqc_rec;
-  a.cache = cache_view(c, q);
+  a.cache = cache_view(c, 0);  // (frame f is planner f % n_planners: seq_cache_mark_kernel takes the view as it is)
   a.hits = q.d_seqc_hits;
   a.resorted = q.d_seqc_resorted;
   return a;
 }
-static bool seq_cached(const fsdp_ctx* c) { return c->sequence && c->sequence->cached; }
 
-// Which instantiation of the three sorting kernels (sort_kernel_128 | sort_kernel, sort_big_kernel) a launch takes: the ranked one
-// for fsdp_sort_batch_ranked, else the cached one while a call advances the sorting cache (c->cache_call), else the speculative one
-// for a pass of fsdp_plan_sequence_cached, else the plain one
+// Which instantiation of the three sorting kernels (sort_kernel_128 | sort_kernel, sort_big_kernel) a launch takes, and what that
+// instantiation needs.  Whoever describes the launch chooses it, once: the cached one for a lock-step call that advances the sorting
+// cache, the speculative one for a pass of fsdp_plan_sequence_cached, the ranked one for fsdp_sort_batch_ranked, else the plain one.
 struct SortVariant {
-  const SortRankView* rank = nullptr;     // ranked: where the rows go ...
+  enum Kind { PLAIN, CACHED, SPEC, RANKED } kind = PLAIN;
+  SortCacheView cache;                    // CACHED: the cache buffers and the planner of the launch's frame 0
+  fsdp_seqc_launch_args* seqc = nullptr;  // SPEC: the pass's launch arguments (launch_pass: seqc_args)
+  const SortRankView* rank = nullptr;     // RANKED: where the rows go ...
   SortRankScratchBig* scratch = nullptr;  // ... and sort_big_kernel_ranked's block for the cost terms (SORT_BIG_BLOCKS of them)
-  fsdp_seqc_launch_args* seqc = nullptr;  // speculative: the pass's launch arguments (seqc_args)
-  const char* suffix(const fsdp_ctx* c) const { return rank ? "_ranked" : (c->cache_call ? "_cached" : (seqc ? "_spec" : "")); }
+  const char* suffix() const {
+    static const char* const names[] = {"", "_cached", "_spec", "_ranked"};
+    return names[kind];
+  }
 };
 
 // Both launches append the name of the kernel they took to `names` (fsdp_stage_names).
 // st: the batch's stage-in (src_off != NULL: the kernel brings it onto the device itself; the ranked kernels have none)
-static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& st, std::string& names, const SortVariant& var = SortVariant()) {
+static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& st, std::string& names, const SortVariant& var) {
   const bool small = sort128(c, in);
   const dim3 grid(in.n_frames), block(WAVE);
-  if (var.rank)
+  if (var.kind == SortVariant::RANKED)
     hipLaunchKernelGGL((small ? sort_kernel_128_ranked : sort_kernel_ranked), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
                        in.d_poses, q.d_sort, q.d_big, c->d_params, *var.rank);
-  else if (c->cache_call)
+  else if (var.kind == SortVariant::CACHED)
     hipLaunchKernelGGL((small ? sort_kernel_128_cached : sort_kernel_cached), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
-                       in.d_poses, q.d_sort, q.d_big, c->d_params, st, cache_view(c, q));
-  else if (var.seqc)
+                       in.d_poses, q.d_sort, q.d_big, c->d_params, st, var.cache);
+  else if (var.kind == SortVariant::SPEC)
     fsdp_seqc_launch_sort(q.stream, var.seqc);
   else
     hipLaunchKernelGGL((small ? sort_kernel_128 : sort_kernel), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
                        q.d_sort, q.d_big, c->d_params, st);
-  names += std::string(small ? "sort_kernel_128" : "sort_kernel") + var.suffix(c);
+  names += std::string(small ? "sort_kernel_128" : "sort_kernel") + var.suffix();
 }
-static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in, std::string& names, const SortVariant& var = SortVariant()) {
+static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in, std::string& names, const SortVariant& var) {
   if (!q.d_sort_big) HIP_TRY(c, hipMalloc(&q.d_sort_big, sizeof(SortSharedBig) * SORT_BIG_BLOCKS));
   const dim3 grid(SORT_BIG_BLOCKS), block(WAVE);
-  if (var.rank)
+  if (var.kind == SortVariant::RANKED)
     hipLaunchKernelGGL(sort_big_kernel_ranked, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
                        c->d_params, *var.rank, var.scratch);
-  else if (c->cache_call)
+  else if (var.kind == SortVariant::CACHED)
     hipLaunchKernelGGL(sort_big_kernel_cached, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
-                       c->d_params, cache_view(c, q));
-  else if (var.seqc) {
+                       c->d_params, var.cache);
+  else if (var.kind == SortVariant::SPEC) {
     var.seqc->big_state = q.d_sort_big;
     fsdp_seqc_launch_sort_big(q.stream, var.seqc);
   } else
     hipLaunchKernelGGL(sort_big_kernel, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
                        c->d_params);
-  names += std::string("sort_big_kernel") + var.suffix(c);
+  names += std::string("sort_big_kernel") + var.suffix();
   return 0;
 }
 static void launch_match(fsdp_ctx* c, Work& q, const Inputs& in) {
@@ -693,10 +718,10 @@ static void launch_path_retry(fsdp_ctx* c, Work& q, const Inputs& in, bool sized
   hipLaunchKernelGGL(path_retry_kernel, dim3(rb), dim3(WAVE), 0, q.stream, in.d_poses, q.d_match, c->d_default_path, prev, c->d_gpath,
                      c->n_gpath, q.d_arena, q.d_path, q.d_retry, c->d_params);
 }
-// What a pass writes where, and where its sorting kernel finds the batch
-struct PassIO;
-static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const PassIO& io);
-struct PassIO {
+// The description of one pass, beyond its slot and its inputs: what it writes where, where its sorting kernel finds the batch, which
+// kernels it is made of and what it is planned for.  The default is a pass over the resident batch; a ticket's pass is built from
+// the ticket (enqueue_ticket).  The launches read nothing else about the pass: the context holds no per-call state.
+struct Pass {
   fsdp_frame_result* host = nullptr;  // NULL: results into the slot's result block; else the device view of a page-locked host buffer
                                       // that assemble_kernel writes straight over PCIe (a ticket: no copy command at all)
   bool compact = false;               // ... as fsdp_compact_result records (fsdp_submit_compact)
@@ -704,14 +729,20 @@ struct PassIO {
   SkidInfo* info = nullptr;           // skidpad: device view of the page-locked block the planners' information records go to
   StageIn stage;                      // src_off != NULL: device views of the caller's page-locked batch, which the sorting kernel
                                       // brings onto the device itself (sort_kernel.h StageIn)
+  StageEvents* events = nullptr;      // optional timing (fsdp_time_runs)
+  bool force_routes = false;          // both route kernels whatever is expected (a pass that runs again because it lacked one)
+  long long in_flight = -1;           // frames on the GPU while this pass runs, its own included (launch_path); < 0: a resident batch
+                                      // replayed through every slot of the overlap depth
+  SortVariant sort;                   // the sorting kernels' instantiation: PLAIN, CACHED, or SPEC (its arguments are made by launch_pass)
+  const Work::SeqPass* sq = nullptr;  // a sequence pass: the chain kernels between the path stage and the assembly
 };
 
 // skid: a skidpad step's records (path stage only, on the context's stream)
-static void launch_assemble(fsdp_ctx* c, Work& q, int n, const PassIO& io, bool skid) {
+static void launch_assemble(fsdp_ctx* c, Work& q, int n, const Pass& pass, bool skid) {
   long long blocks = ((long long)n + 3) / 4;  // one wavefront per frame, four per workgroup (grid-stride beyond the cap)
   // results that go straight to host memory leave at the link's pace: a few hundred wavefronts keep it busy, more would
   // only sit on the SIMDs' wavefront slots with their stores pending while the other slots' kernels wait for a place
-  const long long cap = io.host ? 128 : 16384;  // (32 / 128 / 512 workgroups towards host memory: 5.1 / 5.2 / 5.4 M frames/s streamed, inside the noise: profiles/r06_streaming_probe.txt)
+  const long long cap = pass.host ? 128 : 16384;  // (32 / 128 / 512 workgroups towards host memory: 5.1 / 5.2 / 5.4 M frames/s streamed, inside the noise: profiles/r06_streaming_probe.txt)
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   q.seq++;
@@ -719,22 +750,22 @@ static void launch_assemble(fsdp_ctx* c, Work& q, int n, const PassIO& io, bool 
   const bool filtered = !skid && !c->params.use_unknown_cones;  // (indices back into the caller's cone lists: launch_filter's map)
   const int32_t* remap = filtered ? q.f_map : nullptr;
   const int32_t* remap_off = filtered ? q.f_off : nullptr;
-  if (io.compact) {  // fsdp_compact_result records (into the slot's result block or the caller's page-locked buffer)
+  if (pass.compact) {  // fsdp_compact_result records (into the slot's result block or the caller's page-locked buffer)
     hipLaunchKernelGGL(assemble_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, q.d_sort, q.d_match, q.d_path,
-                       (fsdp_compact_result*)(io.host ? io.host : q.d_result), q.d_big, q.d_retry, q.d_trailer + io.trailer, q.seq, remap, remap_off);
+                       (fsdp_compact_result*)(pass.host ? pass.host : q.d_result), q.d_big, q.d_retry, q.d_trailer + pass.trailer, q.seq, remap, remap_off);
     return;
   }
   hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, skid ? (const SortOut*)nullptr : q.d_sort,
-                     skid ? (const MatchOut*)nullptr : q.d_match, q.d_path, io.host ? io.host : q.d_result, q.d_big, q.d_retry, q.d_trailer + io.trailer,
-                     q.seq, (const int32_t*)(io.info ? q.d_skid_info : nullptr), (int32_t*)io.info, io.info ? (int)(sizeof(SkidInfo) / 4) * n : 0,
+                     skid ? (const MatchOut*)nullptr : q.d_match, q.d_path, pass.host ? pass.host : q.d_result, q.d_big, q.d_retry, q.d_trailer + pass.trailer,
+                     q.seq, (const int32_t*)(pass.info ? q.d_skid_info : nullptr), (int32_t*)pass.info, pass.info ? (int)(sizeof(SkidInfo) / 4) * n : 0,
                      remap, remap_off);
 }
 
 // The chain kernels of a sequence pass (sequence_kernel.h, launched by sequence_lib.hip), behind the path stage and its retry route:
 // every frame was planned with the constant initial path; the runs of frames that read it are planned again in order, a wavefront
 // per run.
-static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const PassIO& io) {
-  const Work::SeqPass& sq = *c->sequence;
+static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const Pass& pass) {
+  const Work::SeqPass& sq = *pass.sq;
   fsdp_seq_launch_args a;
   a.n_planners = sq.s.n;
   a.n_steps = sq.s.n_steps;
@@ -747,7 +778,7 @@ static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const PassIO
   a.out = q.d_path;
   a.seq = q.d_seq;
   a.final_prev = sq.final_dev;
-  a.replanned_out = &(q.d_trailer + io.trailer)->pad;
+  a.replanned_out = &(q.d_trailer + pass.trailer)->pad;
   a.prm = c->d_params;
   fsdp_seq_launch(q.stream, &a);
 }
@@ -777,14 +808,13 @@ static int launch_filter(fsdp_ctx* c, Work& q, const Inputs& in, Inputs* view) {
   return 0;
 }
 
-// sorting -> matching -> path stage -> result assembly of batch `in` on slot q; it becomes the context's most recent pass
-// in_flight: frames on the GPU while this pass runs, its own included (launch_path); < 0: a resident batch replayed through
-// every slot of the overlap depth
-static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io = PassIO(), StageEvents* t = nullptr, bool force_routes = false,
-                       long long in_flight = -1) {
+// sorting -> matching -> path stage -> result assembly of batch `in` on slot q as `pass` describes the pass (Pass() = a pass over the
+// resident batch into the slot's result block); it becomes the context's most recent pass
+static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const Pass& pass) {
+  StageEvents* const t = pass.events;
   c->primed[q.index] = true;
-  const bool with_big = force_routes || c->always_route || c->expect_big;
-  const bool with_retry = force_routes || c->always_route || c->expect_retry;
+  const bool with_big = pass.force_routes || c->always_route || c->expect_big;
+  const bool with_retry = pass.force_routes || c->always_route || c->expect_retry;
   Inputs fin;
   const bool filtered = !c->params.use_unknown_cones;
   if (filtered)
@@ -804,49 +834,49 @@ static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const PassIO& io
     (void)hipMemsetAsync(q.d_retry + 1, 0xff, sizeof(int) * m, q.stream);
   }
   fsdp_seqc_launch_args seqc;
-  SortVariant var;
-  if (seq_cached(c)) {
-    seqc = seqc_args(c, q, in);
+  SortVariant var = pass.sort;
+  if (var.kind == SortVariant::SPEC) {
+    seqc = seqc_args(c, q, in, pass.sq->s);
     var.seqc = &seqc;
   }
   mark(q, t);
-  launch_sort(c, q, in, io.stage, names, var);
+  launch_sort(c, q, in, pass.stage, names, var);
   names += ',';
   if (with_big) {
     mark(q, t);
     if (int rc = launch_sort_big(c, q, in, names, var)) return rc;
     names += ',';
   }
-  if (var.seqc) {  // (fsdp_plan_sequence_cached: the sorting results become those of the cache-on lock-step calls)
+  if (var.kind == SortVariant::SPEC) {  // (fsdp_plan_sequence_cached: the sorting results become those of the cache-on lock-step calls)
     fsdp_seqc_launch_chain(q.stream, &seqc);
     names += "seq_cache_mark_kernel,seq_cache_resolve_kernel,";
   }
   mark(q, t);
   launch_match(c, q, in);
   names += "match_kernel<" + std::to_string(MATCH_G) + ">,";
-  const bool split = launch_path(c, q, in, t, names, in_flight >= 0 ? in_flight : frames_in_flight(c, in.n_frames, false));
+  const bool split = launch_path(c, q, in, t, names, pass.in_flight >= 0 ? pass.in_flight : frames_in_flight(c, in.n_frames, false));
   MarkKind after_path = split ? MARK_PLAIN : MARK_MAIN;  // (the one-kernel path stage is the main kernel: close its bracket)
   if (with_retry) {
     mark(q, t, after_path);
     after_path = MARK_PLAIN;
-    launch_path_retry(c, q, in, !force_routes || c->retry_hint > 0);
+    launch_path_retry(c, q, in, !pass.force_routes || c->retry_hint > 0);
     names += "path_retry_kernel,";
   }
-  if (c->sequence) {  // (fsdp_plan_sequence: never timed)
-    launch_sequence(c, q, in, io);
+  if (pass.sq) {  // (fsdp_plan_sequence: never timed)
+    launch_sequence(c, q, in, pass);
     names += "seq_mark_kernel,seq_chain_kernel,seq_final_kernel,";
   }
   mark(q, t, after_path);
-  launch_assemble(c, q, in.n_frames, io, false);
+  launch_assemble(c, q, in.n_frames, pass, false);
   names += "assemble_kernel";
   mark(q, t, MARK_LAST);
   c->stage_names = names;
   q.pass_in = &in_;
   q.ran_big = with_big;
   q.ran_retry = with_retry;
-  q.unverified = io.trailer == SLOT_QUEUE;  // (a ticket's pass is settled by fsdp_collect, through the ticket's own trailer)
+  q.unverified = pass.trailer == SLOT_QUEUE;  // (a ticket's pass is settled by fsdp_collect, through the ticket's own trailer)
   q.pass_skid = false;
-  c->last = fsdp_ctx::LastPass{q.index, in.n_frames, io.host == nullptr, true};
+  c->last = fsdp_ctx::LastPass{q.index, in.n_frames, pass.host == nullptr, true};
   return 0;
 }
 
@@ -902,7 +932,9 @@ static int verify_pass(fsdp_ctx* c, Work& q) {
     return 2;
   }
   if (settle_routes(c, tr, q.ran_big, q.ran_retry, q.pass_in == &c->res)) {
-    if (int rc = launch_pass(c, q, *q.pass_in, PassIO(), nullptr, true)) return rc;
+    Pass again;
+    again.force_routes = true;
+    if (int rc = launch_pass(c, q, *q.pass_in, again)) return rc;
     HIP_TRY(c, hipStreamSynchronize(q.stream));
     HIP_TRY(c, hipGetLastError());
     q.unverified = false;
@@ -1096,7 +1128,6 @@ static int cache_prepare(fsdp_ctx* c, int n_frames, const int32_t* off, const ch
     HIP_TRY(c, copy_sync(c, c->d_cache_off[x], lay.data(), sizeof(int32_t) * lay.size(), hipMemcpyHostToDevice));
     c->cache_layout[x].swap(lay);
   }
-  for (Work& w : c->slot) w.cache_base = 0;
   return 0;
 }
 
@@ -1106,13 +1137,6 @@ static int cache_finish(fsdp_ctx* c) {
   c->cache_cur = 1 - c->cache_cur;
   return 0;
 }
-
-// cache_call is set for the duration of one call
-struct CacheCall {
-  fsdp_ctx* c;
-  CacheCall(fsdp_ctx* c_, bool on) : c(c_) { c->cache_call = on; }
-  ~CacheCall() { c->cache_call = false; }
-};
 
 extern "C" {
 
@@ -1393,7 +1417,7 @@ int fsdp_run(fsdp_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(q.stream));
     if (int rc = verify_pass(c, q)) return rc;
   }
-  if (int rc = launch_pass(c, q, c->res)) return rc;
+  if (int rc = launch_pass(c, q, c->res, Pass())) return rc;
   HIP_TRY(c, hipGetLastError());
   return 0;
 }
@@ -1477,13 +1501,10 @@ static Work::Ticket* find_ticket(fsdp_ctx* c, long long ticket, Work** slot) {
   return nullptr;
 }
 
-// enqueue ticket t's batch on slot q: inputs, the pass with its results' way back, the ticket's event (the pass is planned for
-// t.in_flight frames on the GPU)
 // A pageable batch of up to SMALL_BATCH_BYTES is packed into the ticket's own page-locked block by the host (a memcpy of a few KB)
 // and then treated like any page-locked batch: the sorting kernel reads it over PCIe, no copy command is issued at all — three or
 // four hipMemcpyAsync calls from pageable memory cost a single-frame call ~30 us of its ~860.
 constexpr size_t SMALL_BATCH_BYTES = 256 * 1024;
-
 
 // ---- sequence tickets ---------------------------------------------------------------------------------------------------------
 constexpr size_t SEQ_PREV_DOUBLES = (size_t)PATH_POINTS * 4;  // one planner's row of initial_prev / final_prev
@@ -1565,16 +1586,26 @@ static int pack_slice(fsdp_ctx* c, Work::Ticket& t, Batch* b) {
   return 0;
 }
 
+// enqueue ticket t's batch on slot q: inputs, the pass with its results' way back, the ticket's event.  The pass is described by
+// the ticket alone (its Pass is built here from the ticket's fields, nothing is read from the call in progress): fsdp_collect's
+// rerun, with force_routes, is this function of the same data.
 static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_routes) {
   Batch b = t.batch;
   const int n = b.n;
   Work::SeqPass* sq = t.sq.on ? &t.sq : nullptr;
   const bool sliced = sq && !sq->s.whole();
-  struct Scope {  // (c->sequence: the pass this call launches)
-    fsdp_ctx* c;
-    ~Scope() { c->sequence = nullptr; }
-  } scope{c};
-  c->sequence = sq;
+  Pass pass;
+  pass.sq = sq;
+  pass.force_routes = force_routes;
+  pass.in_flight = t.in_flight;
+  pass.compact = t.compact;
+  pass.trailer = (int)(&t - q.tk);  // the ticket's own trailer
+  if (t.cache_lo >= 0) {
+    pass.sort.kind = SortVariant::CACHED;
+    pass.sort.cache = cache_view(c, t.cache_lo);  // (the chunk's frames are planners cache_lo.. of the sorting cache)
+  } else if (sq && sq->cached) {
+    pass.sort.kind = SortVariant::SPEC;
+  }
   // a bigger batch than the slot has seen: its buffers are replaced — not under the feet of the passes queued on the stream
   if (n > q.cap_frames || n > q.in.cap_frames || b.total > q.in.cap_cones || (b.prev && n > q.in.cap_prev) ||
       (sq && ((size_t)n > q.seq_cap_frames || (size_t)sq->s.n > q.seq_cap_planners)))
@@ -1615,7 +1646,6 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     b = Batch{n, so, sc, sp, b.prev ? sv : nullptr, b.total, b.max_cones};
     in_pinned = true;
   }
-  PassIO io;
   if (slice_in) {
     if (int rc = take_batch(c, q.in, b)) return rc;
     const SeqSlice& s = sq->s;
@@ -1638,10 +1668,10 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
       return 2;
     }
     fsdp_seq_launch_slice_in(q.stream, &a);
-  } else if (in_pinned && c->params.use_unknown_cones && !seq_cached(c)) {  // (the speculative kernels read their predecessors' cones: device copies first)
+  } else if (in_pinned && c->params.use_unknown_cones && pass.sort.kind != SortVariant::SPEC) {  // (the speculative kernels read their predecessors' cones: device copies first)
     // the pass's sorting kernel reads the batch from the page-locked buffers and leaves the device copies (StageIn)
     if (int rc = take_batch(c, q.in, b)) return rc;
-    StageIn& st = io.stage;
+    StageIn& st = pass.stage;
     st.src_off = (const int32_t*)device_view(b.off);
     st.base = b.off[0];
     // (the view of the slice's first row, addressed by offsets relative to base; never read when total = 0)
@@ -1667,43 +1697,23 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     // A planner slice's records are n_steps segments of the caller's array: seq_slice_out_kernel moves them there from the slot's
     // result block when the array (and final_prev) is page-locked; else they go through the ticket's block, dense, like any
     // pageable caller's, and fsdp_collect copies the segments out.
-    fsdp_frame_result* dst = t.user_results;
     char* slice_dst = sliced ? (char*)t.user_results + t.rec_bytes() * (size_t)sq->s.lo : nullptr;
     const bool slice_out = sliced && is_pinned(slice_dst, t.rec_bytes() * ext.span_frames) && (!sq->final_prev || is_pinned(sq->final_prev, init_bytes));
-    if (slice_out) {
-      dst = nullptr;
-    } else if (sliced || !is_pinned(t.user_results, t.rec_bytes() * (size_t)n)) {
-      HIP_TRY(c, grow_pinned(t.h_stage, t.cap_stage, (size_t)n, hipHostMallocMapped, 64));
-      dst = t.h_stage;
-      t.via_stage = true;
-    }
-    io.host = (fsdp_frame_result*)device_view(dst);
-    if (dst && !io.host) {
-      c->err = "internal: result block is not mapped into the device's address space";
-      return 2;
-    }
+    if (!slice_out)  // (a slice that cannot go out in place is staged whatever its array is: NULL is never page-locked)
+      if (int rc = host_target(c, sliced ? nullptr : t.user_results, t.rec_bytes() * (size_t)n, t.h_stage, t.cap_stage, (size_t)n, 64, "result block",
+                               &pass.host, &t.via_stage))
+        return rc;
     if (sq) {
       // final_prev leaves the GPU inside seq_final_kernel, written into page-locked memory like the records: the caller's rows, or
       // the ticket's block (the slot's d_seq_final serves the slot's next ticket before this one is collected)
       sq->fin_staged = false;
       sq->final_dev = slice_out ? q.d_seq_final : nullptr;
-      if (sq->final_prev && !slice_out) {
-        double* fdst = sq->final_prev;
-        if (!is_pinned(fdst, init_bytes)) {
-          HIP_TRY(c, grow_pinned(t.h_fin, t.cap_fin, SEQ_PREV_DOUBLES * (size_t)sq->s.n, hipHostMallocMapped, 64 * SEQ_PREV_DOUBLES));
-          fdst = t.h_fin;
-          sq->fin_staged = true;
-        }
-        sq->final_dev = (double*)device_view(fdst);
-        if (!sq->final_dev) {
-          c->err = "internal: final_prev block is not mapped into the device's address space";
-          return 2;
-        }
-      }
+      if (sq->final_prev && !slice_out)
+        if (int rc = host_target(c, sq->final_prev, init_bytes, t.h_fin, t.cap_fin, SEQ_PREV_DOUBLES * (size_t)sq->s.n, 64 * SEQ_PREV_DOUBLES,
+                                 "final_prev block", &sq->final_dev, &sq->fin_staged))
+          return rc;
     }
-    io.compact = t.compact;
-    io.trailer = (int)(&t - q.tk);  // the ticket's own trailer
-    if (int rc = launch_pass(c, q, q.in, io, nullptr, force_routes, t.in_flight)) return rc;
+    if (int rc = launch_pass(c, q, q.in, pass)) return rc;
     t.seq = q.seq;
     t.ran_big = q.ran_big;
     t.ran_retry = q.ran_retry;
@@ -1772,6 +1782,42 @@ static int free_ticket(fsdp_ctx* c, const char* who, int n_frames, Work** slot, 
   return 0;
 }
 
+// What the caller of issue_ticket says about the pass; the rest of the ticket is enqueue_ticket's
+struct TicketSpec {
+  Batch batch;
+  long long in_flight = 0;               // frames on the GPU the pass is planned for
+  fsdp_frame_result* results = nullptr;  // the caller's records, full or compact
+  bool compact = false;
+  int cache_lo = -1;                     // >= 0: a chunk of a call that advances the sorting cache, its frame 0 is this planner
+  Work::SeqPass sq;                      // on: a sequence pass
+};
+
+// The one way a pass becomes a ticket (fsdp_submit*, the chunks of a blocking call, the sequence calls): entry t of slot q gets its
+// description and is enqueued.  0: issued as t.id and counted as outstanding (a blocking call collects it and gives the number
+// back: c->next_ticket).  Else no ticket went out, and an error return means the buffers are the caller's again: part of the batch
+// may already be queued on the slot's stream — kernels that read his buffers or write his page-locked results — so it is waited
+// for here (round-3 advisor); a sequence pass that found no room has its slot's buffers replaced again next time (seq_no_room).
+static int issue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, const TicketSpec& spec) {
+  t.batch = spec.batch;
+  t.skid = false;
+  t.in_flight = spec.in_flight;
+  t.user_results = spec.results;
+  t.user_info = nullptr;
+  t.compact = spec.compact;
+  t.sq = spec.sq;
+  t.cache_lo = spec.cache_lo;
+  if (int rc = enqueue_ticket(c, q, t, false)) {
+    (void)hipStreamSynchronize(q.stream);
+    (void)hipGetLastError();
+    t.release();
+    if (spec.sq.on) seq_no_room(q);
+    return rc;
+  }
+  t.id = c->next_ticket++;
+  c->outstanding++;
+  return 0;
+}
+
 static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev_paths,
                        fsdp_frame_result* results, long long* ticket, bool compact) {
   if (!c || !ticket) return 1;
@@ -1790,26 +1836,12 @@ static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
   Work* qp = nullptr;
   Work::Ticket* t = nullptr;
   if (int rc = free_ticket(c, "fsdp_submit", n_frames, &qp, &t)) return rc;
-  Work& q = *qp;
-  t->batch = b;
-  t->skid = false;
-  t->in_flight = frames_in_flight(c, n_frames, true);
-  t->user_results = results;
-  t->user_info = nullptr;
-  t->compact = compact;
-  t->sq = Work::SeqPass();
-  if (int rc = enqueue_ticket(c, q, *t, false)) {
-    // Part of the batch may already be queued on the slot's stream — kernels that read the caller's buffers or write his
-    // page-locked results — and no ticket goes out that he could wait on: wait here, so that an error return means the
-    // buffers are his again (round-3 advisor).
-    (void)hipStreamSynchronize(q.stream);
-    (void)hipGetLastError();
-    t->user_results = nullptr;
-    t->compact = false;
-    return rc;
-  }
-  t->id = c->next_ticket++;
-  c->outstanding++;
+  TicketSpec spec;
+  spec.batch = b;
+  spec.in_flight = frames_in_flight(c, n_frames, true);
+  spec.results = results;
+  spec.compact = compact;
+  if (int rc = issue_ticket(c, *qp, *t, spec)) return rc;
   *ticket = t->id;
   return 0;
 }
@@ -1901,12 +1933,8 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
       }
     }
   }
-  if (rc != 0 && t.sq.on) seq_no_room(q);  // (a repeated pass that found no room: see seq_issue)
-  t.id = -1;
-  t.user_results = nullptr;
-  t.user_info = nullptr;
-  t.compact = false;
-  t.sq = Work::SeqPass();
+  if (rc != 0 && t.sq.on) seq_no_room(q);  // (a repeated pass that found no room: see issue_ticket)
+  t.release();
   c->outstanding--;
   return rc;
 }
@@ -1933,30 +1961,6 @@ int fsdp_route_stats(fsdp_ctx* c, int* expect_big, int* expect_retry, long long*
 // (tests), 1 = never.
 constexpr int PLAN_CHUNKS = 4, PLAN_CHUNK_FROM = 16384, PLAN_CHUNK_MIN = 512;
 
-// The internal ticket of a blocking call: batch b as ticket 0 of slot q, planned for in_flight frames on the GPU.  0: issued as
-// q.tk[0].id — the caller collects it and gives the number back (c->next_ticket: the caller's own tickets keep counting up from
-// where they were).  Else nothing of the batch is left running over the caller's buffers and no ticket went out.
-static int issue_blocking(fsdp_ctx* c, Work& q, const Batch& b, long long in_flight, fsdp_frame_result* results, bool compact) {
-  Work::Ticket& t = q.tk[0];
-  t.batch = b;
-  t.skid = false;
-  t.in_flight = in_flight;
-  t.user_results = results;
-  t.user_info = nullptr;
-  t.compact = compact;
-  t.sq = Work::SeqPass();
-  if (int rc = enqueue_ticket(c, q, t, false)) {
-    (void)hipStreamSynchronize(q.stream);
-    (void)hipGetLastError();
-    t.user_results = nullptr;
-    t.compact = false;
-    return rc;
-  }
-  t.id = c->next_ticket++;
-  c->outstanding++;
-  return 0;
-}
-
 static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev,
                          fsdp_frame_result* results, bool compact, bool sequential = false) {
   if (!c) return 1;
@@ -1974,7 +1978,6 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
   if (int rc = sync_all(c)) return rc;
   if (cached)
     if (int rc = cache_prepare(c, n_frames, off, "fsdp_plan_batch_sequential")) return rc;
-  const CacheCall cache_call(c, cached);
   c->last = fsdp_ctx::LastPass();
   if (n_frames == 0) return 0;
   const int chunks = c->plan_chunks > 0 ? std::max(1, std::min(c->plan_chunks, n_frames / PLAN_CHUNK_MIN)) : (n_frames >= PLAN_CHUNK_FROM ? PLAN_CHUNKS : 1);
@@ -1985,8 +1988,14 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
     const int lo = (int)((long long)n_frames * k / chunks), hi = (int)((long long)n_frames * (k + 1) / chunks);
     Work& q = c->slot[k];  // (slots beyond the overlap depth get their stream here: a chunk is a pass in flight)
     if ((rc = ensure_work(c, q, hi - lo))) break;
-    q.cache_base = lo;  // (the chunk's frames are planners lo..hi-1 of the sorting cache)
-    if ((rc = issue_blocking(c, q, b.slice(lo, hi), n_frames, (fsdp_frame_result*)((char*)results + rec * (size_t)lo), compact))) break;
+    // (an internal ticket: entry 0 of the chunk's slot, planned for the whole call's frames on the GPU)
+    TicketSpec spec;
+    spec.batch = b.slice(lo, hi);
+    spec.in_flight = n_frames;
+    spec.results = (fsdp_frame_result*)((char*)results + rec * (size_t)lo);
+    spec.compact = compact;
+    if (cached) spec.cache_lo = lo;  // (the chunk's frames are planners lo..hi-1 of the sorting cache)
+    if ((rc = issue_ticket(c, q, q.tk[0], spec))) break;
     ids[issued++] = q.tk[0].id;
   }
   for (int k = 0; k < issued; k++) {
@@ -2109,17 +2118,14 @@ static int seq_check_batch(fsdp_ctx* c, const SeqCall& k, Batch* b) {
   return 0;
 }
 
-// The call as ticket t of slot q, planned for in_flight frames on the GPU.  0: issued as t.id.  Else nothing of it is left running
-// over the caller's buffers, no ticket went out, and the slot's buffers are replaced again next time.
-static int seq_issue(fsdp_ctx* c, Work& q, Work::Ticket& t, const Batch& b, const SeqCall& k, const char* who, long long in_flight) {
-  t.batch = b;
-  t.skid = false;
-  t.in_flight = in_flight;
-  t.user_results = k.results;
-  t.user_info = nullptr;
-  t.compact = k.compact;
-  Work::SeqPass& sq = t.sq;
-  sq = Work::SeqPass();
+// the call as issue_ticket takes it, planned for in_flight frames on the GPU
+static TicketSpec seq_spec(const Batch& b, const SeqCall& k, const char* who, long long in_flight) {
+  TicketSpec spec;
+  spec.batch = b;
+  spec.in_flight = in_flight;
+  spec.results = k.results;
+  spec.compact = k.compact;
+  Work::SeqPass& sq = spec.sq;
   sq.on = true;
   sq.s = SeqSlice{k.n_planners, k.n_steps, k.planner_lo, k.planners_total};
   sq.cached = k.cached;
@@ -2127,22 +2133,10 @@ static int seq_issue(fsdp_ctx* c, Work& q, Work::Ticket& t, const Batch& b, cons
   sq.off = k.off;
   sq.cones = k.cones;
   sq.poses = k.poses;
-  sq.results = k.results;
   sq.init = k.initial_prev ? k.initial_prev + SEQ_PREV_DOUBLES * (size_t)k.planner_lo : nullptr;
   sq.final_prev = k.final_prev ? k.final_prev + SEQ_PREV_DOUBLES * (size_t)k.planner_lo : nullptr;
   sq.n_replanned = k.n_replanned;
-  if (int rc = enqueue_ticket(c, q, t, false)) {
-    (void)hipStreamSynchronize(q.stream);
-    (void)hipGetLastError();
-    t.user_results = nullptr;
-    t.compact = false;
-    t.sq = Work::SeqPass();
-    seq_no_room(q);
-    return rc;
-  }
-  t.id = c->next_ticket++;
-  c->outstanding++;
-  return 0;
+  return spec;
 }
 
 static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
@@ -2161,7 +2155,6 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
   if (int rc = sync_all(c)) return rc;
   c->last = fsdp_ctx::LastPass();
   Work& q = c->slot[0];
-  q.cache_base = 0;  // (frame f is planner f % n_planners: seq_cache_mark_kernel takes the view as it is)
   if (int rc = ensure_work(c, q, n)) {
     seq_no_room(q);
     return rc;
@@ -2185,7 +2178,7 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
     for (int s = 0; s < n_steps; s++)
       if (int rc = cache_prepare(c, n_planners, off + (size_t)s * n_planners, who)) return rc;
   }
-  if (int rc = seq_issue(c, q, q.tk[0], b, k, who, n)) return rc;
+  if (int rc = issue_ticket(c, q, q.tk[0], seq_spec(b, k, who, n))) return rc;
   int rc = fsdp_collect(c, q.tk[0].id);  // (waits; runs the pass again, chain kernels included, if it lacked a route)
   c->next_ticket--;                // (the number was internal, like plan_blocking's)
   if (rc != 0) return rc;
@@ -2221,7 +2214,7 @@ static int submit_sequence(fsdp_ctx* c, int n_planners, int n_steps, int planner
   Work* q = nullptr;
   Work::Ticket* t = nullptr;
   if (int rc = free_ticket(c, who, 1, &q, &t)) return rc;
-  if (int rc = seq_issue(c, *q, *t, b, k, who, frames_in_flight(c, b.n, true))) return rc;
+  if (int rc = issue_ticket(c, *q, *t, seq_spec(b, k, who, frames_in_flight(c, b.n, true)))) return rc;
   *ticket = t->id;
   return 0;
 }
@@ -2430,7 +2423,7 @@ static int check_resident(fsdp_ctx* c) {
   if (c->res_checked || !c->resident || c->res.n_frames == 0) return 0;
   if (int rc = sync_all(c)) return rc;
   Work& q = c->slot[0];
-  if (int rc = launch_pass(c, q, c->res)) return rc;
+  if (int rc = launch_pass(c, q, c->res, Pass())) return rc;
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   return verify_pass(c, q);  // sets res_checked and the exact expectations
 }
@@ -2447,7 +2440,7 @@ int fsdp_time_reserve(fsdp_ctx* c, int iters) {
     if ((rc = check_resident(c))) return rc;
     for (int i = 0; i < c->overlap; i++)
       if (!c->primed[i])
-        if ((rc = launch_pass(c, c->slot[i], c->res))) return rc;
+        if ((rc = launch_pass(c, c->slot[i], c->res, Pass()))) return rc;
     rc = sync_all(c);
     if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
@@ -2523,7 +2516,9 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
     // timed without them are the production launches)
     t.clock_first = c->time_kernel_clock ? c->d_kclock + it : nullptr;
     t.clock_last = c->time_kernel_clock ? c->d_kclock + c->kclock_cap + it : nullptr;
-    if ((rc = launch_pass(c, q, c->res, PassIO(), &t))) return rc;
+    Pass timed;
+    timed.events = &t;
+    if ((rc = launch_pass(c, q, c->res, timed))) return rc;
     n_stages = t.n - 1;
     c->tev_recorded[it] = t.recorded;
     last_of_slot[si] = it;
@@ -2644,7 +2639,6 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
   if (int rc = sync_all(c)) return rc;
   if (cached)
     if (int rc = cache_prepare(c, n_frames, off, "fsdp_sort_batch")) return rc;
-  const CacheCall cache_call(c, cached);
   Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
   if (int rc = upload_inputs(c, q.in, q.stream, b)) return rc;
@@ -2676,8 +2670,12 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
     v.configs = rk->d_configs;
     v.costs = rk->d_costs;
     v.terms = rk->d_terms;
+    var.kind = SortVariant::RANKED;
     var.rank = &v;
     var.scratch = rk->d_scratch;
+  } else if (cached) {
+    var.kind = SortVariant::CACHED;
+    var.cache = cache_view(c, 0);  // (frame i is planner i)
   }
   std::string names;
   launch_sort(c, q, in, StageIn(), names, var);
@@ -3100,10 +3098,10 @@ static int flush_skid(fsdp_ctx* c) {
       continue;
     }
     if (t.user_results || t.user_info) {
-      PassIO io;
-      io.host = direct;
-      io.info = t.user_info ? (SkidInfo*)device_view(t.h_info) : nullptr;
-      launch_assemble(c, q, t.user_results ? n : 0, io, true);
+      Pass pass;
+      pass.host = direct;
+      pass.info = t.user_info ? (SkidInfo*)device_view(t.h_info) : nullptr;
+      launch_assemble(c, q, t.user_results ? n : 0, pass, true);
     }
     HIP_TRY(c, hipGetLastError());
     if (t.via_stage) HIP_TRY(c, hipMemcpyAsync(t.h_stage, q.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, xs));

@@ -250,6 +250,38 @@ def test_scale_hit_codes_follow_the_rule(scale):
     assert near == 0
 
 
+def test_rerun_chunk_of_a_cached_call_keeps_its_planners(golden_dir):
+    """A chunk of a cached lock-step call that has to run again, and whose first planner is not 0: 2048 planners replay the first
+    three frames of the mapped fixture, except one in the last of four chunks (planners 1536..2047), which replays 272-cone frames
+    that need sort_big_kernel.  The chunked context's first call lacks that route, so fsdp_collect runs the last chunk again; a
+    context that never cuts and always carries both routes plans the same bytes and the same hit codes."""
+    n, steps, big_planner = 2048, 3, 1700
+    small, big = load(golden_dir, "mapped"), load(golden_dir, "big")
+    assert all(e == "ok" for e in small["exc"][:steps]) and all(e == "ok" for e in big["exc"][:steps])
+    a = pkg._capi.Context(device=0, options={"plan_chunks": 4})
+    b = pkg._capi.Context(device=0, options={"plan_chunks": 1, "always_route": 1})
+    out = []
+    for ctx in (a, b):
+        ctx.sort_cache_reset(n)
+        prev, rs = None, []
+        for k in range(steps):
+            xs, ps = [frame(small, k)[0]] * n, np.tile(small["poses"][k], (n, 1))
+            xs[big_planner], ps[big_planner] = frame(big, k)
+            assert len(xs[big_planner]) > 255
+            off = np.zeros(n + 1, np.int32)
+            off[1:] = np.cumsum([len(x) for x in xs])
+            r = ctx.plan_batch_sequential(off, np.concatenate(xs), ps, prev)
+            rs.append((r, ctx.sort_cache_hits()))
+            prev = np.where((r["status"] == 0)[:, None, None], r["path"], default_path(ctx)[None] if prev is None else prev)
+        out.append(rs)
+    for k, ((ra, ha), (rb, hb)) in enumerate(zip(*out)):
+        assert same(ra, rb), k
+        assert np.array_equal(ha, hb), k
+        assert int(ra["status"][big_planner]) == 0, k
+    assert (out[0][1][1] == 1).any()  # the small frames hit after step 0
+    assert a.route_stats()[2] >= 1 and b.route_stats()[2] == 0
+
+
 # ---- isolation -----------------------------------------------------------------------------------------------------------
 def test_other_entry_points_do_not_see_the_cache(golden_dir):
     g = load(golden_dir, "lockstep")
