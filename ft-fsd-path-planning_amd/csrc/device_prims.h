@@ -11,13 +11,30 @@
 //
 // The emulator keeps direct IEEE forms (a / b, sqrt) where the device runs a shortened sequence from a hardware rcp / rsq
 // seed: the sequences return the correctly rounded result (held against the IEEE operations on the device by
-// fsdp_selftest_math / givens / absminmax, tests/test_gpu_parity.py), so both builds compute the same bits.
+// fsdp_selftest_math / givens / absminmax, tests/test_gpu_parity.py; on operands built to be hard to round and on the band's
+// edges, tests/test_hard_rounding_gpu.py), so both builds compute the same bits.
+//
+// A third build reads the sequences themselves on the host: with FSDP_SEQ_MODEL next to FSDP_EMU (tests/emu/seq_model.cpp)
+// rcp_refined, div_rcp, sqrt_1_2 and givens_dd_rd keep their DEVICE bodies, and the two seed instructions in them,
+// v_rcp_f64 and v_rsq_f64, are a model the including file provides (fsdp::seq_model_rcp / seq_model_rsq).  Everything else
+// keeps its emulator form.  FSDP_RCP_SEED / FSDP_RSQ_SEED are the builtins themselves in the device build.
 #pragma once
 
 #include <stdint.h>
 
 #ifndef FSDP_EMU
 #include <hip/hip_runtime.h>
+#endif
+
+#if defined(FSDP_EMU) && !defined(FSDP_SEQ_MODEL)
+#define FSDP_EMU_IEEE_FORMS 1  // the emulator's a / b and sqrt in place of the shortened sequences
+#endif
+#ifdef FSDP_SEQ_MODEL
+#define FSDP_RCP_SEED(x) seq_model_rcp(x)
+#define FSDP_RSQ_SEED(x) seq_model_rsq(x)
+#else
+#define FSDP_RCP_SEED(x) __builtin_amdgcn_rcp(x)
+#define FSDP_RSQ_SEED(x) __builtin_amdgcn_rsq(x)
 #endif
 
 namespace fsdp {
@@ -160,9 +177,10 @@ __device__ __forceinline__ double dpp_row16(double d) {
 // ---- exact division without the range scaling ---------------------------------------------------------
 // An IEEE double division on gfx950 is a software sequence: v_div_scale (x2), v_rcp_f64, two Newton steps, a quotient
 // with one correction (v_div_fmas) and v_div_fixup.  The scaling and the fix-up only act when an exponent sits near the
-// limits of the format; for operands in a safe band the sequence below is the same arithmetic on the same operands and
-// returns the same (correctly rounded) bits with 8 instead of 11 instructions — and two quotients over one denominator
-// share the refined reciprocal (11 instead of 22).  The guard: callers flag operands outside [2^-255, 2^255]
+// limits of the format; for operands in a safe band the sequence below is that arithmetic without them, with one Newton
+// step more on the reciprocal (the compiler's two leave it an ulp off for some divisors, and the quotient then one ulp off
+// for some numerators: rcp_newton2) — the correctly rounded quotient with 10 instead of 11 instructions, and two quotients
+// over one denominator share the refined reciprocal (13 instead of 22).  The guard: callers flag operands outside [2^-255, 2^255]
 // (float compares on the operands; the knot differences once per knot set) and such a frame is re-planned with plain
 // divisions (ST_RETRY, path_kernel.h).
 // max(|a|, b) / min(|a|, b) of numbers that are never NaN: one v_max_f64 / v_min_f64 each (the absolute value is a source
@@ -185,11 +203,15 @@ __device__ __forceinline__ double min_abs_nn(double a, double b) {
   return r;
 #endif
 }
-__device__ __forceinline__ double rcp_refined(double d) {
-#ifdef FSDP_EMU
+// v_rcp_f64 and two Newton steps: what the compiler's division refines its reciprocal to.  Within an ulp of 1 / d but NOT always
+// the correctly rounded one (measured on gfx950: d = 0x1.ffffffffffffb 2^k comes out one ulp low), and a quotient corrected
+// with such an r can land on the wrong side of a rounding midpoint (0x1.6666666666663 / 0x1.ffffffffffffb did, in this
+// sequence and in the compiler's: tests/test_hard_rounding_gpu.py).
+__device__ __forceinline__ double rcp_newton2(double d) {
+#ifdef FSDP_EMU_IEEE_FORMS
   return d;  // (the emulator divides directly, see div_rcp)
 #else
-  double r = __builtin_amdgcn_rcp(d);
+  double r = FSDP_RCP_SEED(d);
   double e = fma(-d, r, 1.0);
   r = fma(r, e, r);
   e = fma(-d, r, 1.0);
@@ -197,9 +219,21 @@ __device__ __forceinline__ double rcp_refined(double d) {
   return r;
 #endif
 }
+// One more Newton step on a reciprocal that is within an ulp: the correctly rounded 1 / d (Markstein: for every d whose
+// mantissa is not all ones; for that one the two steps above already return it on this hardware and the step keeps it).
+__device__ __forceinline__ double rcp_newton_last(double d, double r) {
+#ifdef FSDP_EMU_IEEE_FORMS
+  return r;
+#else
+  const double e = fma(-d, r, 1.0);
+  return fma(r, e, r);
+#endif
+}
+// the correctly rounded reciprocal: what div_rcp needs to return the correctly rounded quotient
+__device__ __forceinline__ double rcp_refined(double d) { return rcp_newton_last(d, rcp_newton2(d)); }
 // n / d given r = rcp_refined(d)
 __device__ __forceinline__ double div_rcp(double n, double d, double r) {
-#ifdef FSDP_EMU
+#ifdef FSDP_EMU_IEEE_FORMS
   (void)r;
   return n / d;
 #else
@@ -208,15 +242,48 @@ __device__ __forceinline__ double div_rcp(double n, double d, double r) {
   return fma(rem, r, q);
 #endif
 }
+// n / d given r2 = rcp_newton2(d), for a quotient at the head of a dependent chain: the product and its exact remainder take r2
+// as it is, the last Newton step runs next to them (it needs r2 only), and the correction takes the correctly rounded
+// reciprocal.  Two instructions more than div_rcp, no link more.
+__device__ __forceinline__ double div_rcp_late(double n, double d, double r2) {
+#ifdef FSDP_EMU_IEEE_FORMS
+  (void)r2;
+  return n / d;
+#else
+  const double q = n * r2;
+  const double rem = fma(-d, q, n);
+  return fma(rem, rcp_newton_last(d, r2), q);
+#endif
+}
+
+// a / b for the plain-division route (ST_RETRY) and wherever the fast route's counterpart is div_rcp: the compiler's division,
+// whose result is within an ulp but on gfx950 not always the correctly rounded one (above), followed by the choice between it
+// and its neighbour on the side of the exact remainder — the one with the smaller remainder is the correctly rounded quotient
+// (a quotient of two doubles is never a midpoint: no ties).  Operands whose remainders could underflow or overflow keep
+// the compiler's result.
+__device__ __forceinline__ double div_exact(double a, double b) {
+#ifdef FSDP_EMU
+  return a / b;
+#else
+  const double q = a / b;
+  const double aa = fabs(a), aq = fabs(q);
+  const double rem = fma(-b, q, a);  // exact
+  const bool safe = (aa >= 0x1p-900) & (aa <= 0x1p900) & (aq >= 0x1p-900) & (aq <= 0x1p900) & (rem != 0.0);
+  const bool grow = ((rem > 0.0) == (b > 0.0)) == (q > 0.0);  // the exact quotient lies beyond q in magnitude
+  const double qn = __longlong_as_double(__double_as_longlong(q) + (grow ? 1ll : -1ll));
+  const double remn = fma(-b, qn, a);
+  return (safe & (fabs(remn) < fabs(rem))) ? qn : q;
+#endif
+}
 
 // sqrt for arguments in [1, 2] (1 + r^2 with |r| <= 1): the correctly rounded result, i.e. what sqrt() returns; on the
 // device this is the compiler's own v_rsq_f64 + Goldschmidt sequence without the range scaling that [1, 2] never needs
 // (checked against sqrt() on the GPU: tests/test_gpu_parity.py::test_device_math_helpers)
 __device__ __forceinline__ double sqrt_1_2(double x) {
-#ifdef FSDP_EMU
+#ifdef FSDP_EMU_IEEE_FORMS
   return sqrt(x);
 #else
-  double y = __builtin_amdgcn_rsq(x);
+  double y = FSDP_RSQ_SEED(x);
   double g = x * y;
   double h = y * 0.5;
   double r = fma(-h, g, 0.5);
@@ -243,16 +310,16 @@ __device__ __forceinline__ double sqrt_1_2(double x) {
 // The form before it, dd = den * sqrt_1_2(x) and rd = rcp_refined(dd) from v_rcp_f64 again, was the A side of the measurement that
 // kept the seed (p50 885 -> 857 us, profiles/r05_givens_step.txt).
 __device__ __forceinline__ void givens_dd_rd(double den, double num, double& dd, double& rd) {
-#ifdef FSDP_EMU
+#ifdef FSDP_EMU_IEEE_FORMS
   const double q = num / den;
   dd = den * sqrt(1.0 + q * q);
   rd = dd;  // (the emulator's div_rcp divides directly)
 #else
-  const double rq = rcp_refined(den);
-  const double q = div_rcp(num, den, rq);
+  const double rq = rcp_newton2(den);  // (as a SEED for rd below an ulp is nothing; the quotient corrects with the last step's)
+  const double q = div_rcp_late(num, den, rq);
   const double x = 1.0 + q * q;
   // sqrt_1_2(x), keeping h
-  double y = __builtin_amdgcn_rsq(x);
+  double y = FSDP_RSQ_SEED(x);
   double g = x * y;
   double h = y * 0.5;
   double r = fma(-h, g, 0.5);

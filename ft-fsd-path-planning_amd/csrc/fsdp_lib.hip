@@ -3342,7 +3342,7 @@ static int run_selftest(fsdp_ctx* c, int n, std::initializer_list<SelftestIn> in
 }
 // The hand-rolled sequences of spline_device.h against the compiler's IEEE operations, element-wise on the device:
 // out[0][i] = sqrt_1_2(x[i]), out[1][i] = sqrt(x[i]) (x in [1, 2]); out[2][i] = div_rcp(a[i], b[i], rcp_refined(b[i])),
-// out[3][i] = a[i] / b[i]; out[4][i] = in_div_band(a[i]) && in_div_band(b[i]).
+// out[3][i] = div_exact(a[i], b[i]) (the plain route's division: the compiler's a / b and its last-bit fix-up); out[4][i] = in_div_band(a[i]) && in_div_band(b[i]).
 __global__ void math_selftest_kernel(int n, const double* __restrict__ x, const double* __restrict__ a, const double* __restrict__ b,
                                      double* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3350,7 +3350,7 @@ __global__ void math_selftest_kernel(int n, const double* __restrict__ x, const 
   out[i] = sqrt_1_2(x[i]);
   out[(size_t)n + i] = sqrt(x[i]);
   out[2 * (size_t)n + i] = div_rcp(a[i], b[i], rcp_refined(b[i]));
-  out[3 * (size_t)n + i] = a[i] / b[i];
+  out[3 * (size_t)n + i] = div_exact(a[i], b[i]);
   out[4 * (size_t)n + i] = (in_div_band(a[i]) && in_div_band(b[i])) ? 1.0 : 0.0;
 }
 // max_abs_nn / min_abs_nn (the one-instruction max(|a|, b) / min(|a|, b) of the Givens step) element-wise: out = [max | min]

@@ -202,10 +202,10 @@ __device__ __forceinline__ void fpgivs(double piv, double& ww, double& cs, doubl
   double store = fabs(piv);
   bool big = store >= ww;
   double num = big ? ww : piv, den = big ? piv : ww, scale = big ? store : ww;
-  double r = num / den;
+  double r = div_exact(num, den);
   double dd = scale * sqrt(1.0 + r * r);
-  cs = ww / dd;
-  sn = piv / dd;
+  cs = div_exact(ww, dd);
+  sn = div_exact(piv, dd);
   ww = dd;
 }
 
@@ -318,7 +318,9 @@ __device__ __forceinline__ void fpgivs_guarded(double piv, double& ww, double& c
 // trip instead of a dependent read per term), coincident knots are handled by selects (the quotient of the skipped
 // branch is computed and dropped), and with FAST the six divisions use the exact scaled-free sequence above (operands
 // outside its exponent band set `bad`).  Same operations on the same operands as fpbspl<3>: same bits.
-template <bool FAST>
+// FAST = false: the plain-division route's counterpart of those six quotients, div_exact — or, with EXACT = false, the compiler's
+// own division as it is: spline evaluation (the same statement in both routes, fpbspl for the other degrees likewise).
+template <bool FAST, bool EXACT = true>
 __device__ __forceinline__ void fpbspl3(const double* t, double x, int l, double* h /*[0..3]*/, int& bad) {
   const double tm2 = t[l - 2], tm1 = t[l - 1], t0 = t[l], tp1 = t[l + 1], tp2 = t[l + 2], tp3 = t[l + 3];
   // FAST: the denominators are differences of knots — their exponent band is checked once per knot set by the caller
@@ -328,6 +330,8 @@ __device__ __forceinline__ void fpbspl3(const double* t, double x, int l, double
     if constexpr (FAST) {
       ok = ok & ((num == 0.0) | ((num >= 0x1p-255) & (num <= 0x1p255)));
       return div_rcp(num, den, rcp_refined(den));
+    } else if constexpr (EXACT) {
+      return div_exact(num, den);
     } else {
       return num / den;
     }
@@ -607,10 +611,10 @@ __device__ __forceinline__ void giv_step(GivLane& st, bool feed, double h0, doub
     cs = div_rcp(ww, dd, rd);
     sn = div_rcp(piv, dd, rd);
   } else {
-    const double q = num / den;
+    const double q = div_exact(num, den);
     dd = scale * sqrt(1.0 + q * q);
-    cs = ww / dd;
-    sn = piv / dd;
+    cs = div_exact(ww, dd);
+    sn = div_exact(piv, dd);
   }
   cs = rot ? cs : 1.0;
   sn = rot ? sn : 0.0;
@@ -763,10 +767,10 @@ __device__ __forceinline__ void giv_step(GivGridLane& st, int e, bool feed, doub
     cs = div_rcp(ww, dd, rd);
     sn = div_rcp(piv, dd, rd);
   } else {
-    const double q = num / den;
+    const double q = div_exact(num, den);
     dd = den * sqrt(1.0 + q * q);
-    cs = ww / dd;
-    sn = piv / dd;
+    cs = div_exact(ww, dd);
+    sn = div_exact(piv, dd);
   }
   cs = rot ? cs : 1.0;
   sn = rot ? sn : 0.0;
@@ -1713,7 +1717,7 @@ __device__ __forceinline__ void spline_eval_k(const WS& ws, const SplineFit& f, 
     double h[K + 2];
     if constexpr (K == 3) {
       int unused = 0;
-      fpbspl3<false>(ws.t, arg, l, &h[1], unused);
+      fpbspl3<false, false>(ws.t, arg, l, &h[1], unused);
     } else {
       fpbspl<K>(ws.t, arg, l, h);
     }

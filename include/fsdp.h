@@ -597,8 +597,12 @@ int fsdp_debug_refit(fsdp_ctx* ctx, int32_t* n_knots, double* knots34, double* c
 int fsdp_debug_arena(fsdp_ctx* ctx, int frame, int offset, int count, double* out);
 
 /* Self-test of the device's hand-rolled FP64 sequences against the compiler's IEEE operations (n elements each; out5n =
- * [sqrt_1_2(x) | sqrt(x) | fast quotient a/b | IEEE a/b | operands inside the fast division's exponent band]): the spline
- * kernels replace sqrt on [1, 2] and divisions of safe-band operands by shorter sequences that must return the same bits. */
+ * [sqrt_1_2(x) | sqrt(x) | fast quotient a/b | the plain route's a/b (the compiler's division and its last-bit fix-up, div_exact) |
+ * operands inside the fast division's exponent band]): the spline
+ * kernels replace sqrt on [1, 2] and divisions of safe-band operands by shorter sequences that must return the same bits.
+ * What pins the sequences: tests/test_gpu_parity.py::test_device_math_helpers (10^6 random operands) and
+ * tests/test_hard_rounding_gpu.py (operands next to a rounding midpoint, the divisors with the hardest reciprocals, the band's
+ * edge binades and the first values outside it, each against an exact integer reference). */
 int fsdp_selftest_math(fsdp_ctx* ctx, int n, const double* x, const double* a, const double* b, double* out5n);
 
 /* max(|a|, b) and min(|a|, b) as the Givens step of the spline kernels takes them (one v_max_f64 / v_min_f64 with an
@@ -610,7 +614,9 @@ int fsdp_selftest_absminmax(fsdp_ctx* ctx, int n, const double* a, const double*
  * new diagonal seeded from the square root's own iterate (spline_device.h givens_dd_rd) — next to the same routine with the
  * compiler's IEEE division and square root: out7n = [cs | sn | dd] of the kernels' sequence, [cs | sn | dd] IEEE, [1 where the operands
  * lie inside the sequence's exponent band (outside it the kernels re-plan the frame with the IEEE operations)].  piv: pivots, ww >= 0:
- * diagonals. */
+ * diagonals.  What pins the sequence: tests/test_gpu_parity.py::test_device_givens_sequence_returns_the_ieee_bits (random pairs) and
+ * tests/test_hard_rounding_gpu.py (hard quotients through the seeded reciprocal, hard square-root arguments, equal magnitudes, the
+ * band's edges, against FITPACK's chain with one exact rounding per operation). */
 int fsdp_selftest_givens(fsdp_ctx* ctx, int n, const double* piv, const double* ww, double* out7n);
 
 /* The device's restatement of numpy.linalg.det for three homogeneous points (calculate_path/path_parameterization.py:86-92

@@ -787,7 +787,8 @@ def test_stage_classes_take_the_reference_kwargs(pkg, golden_dir):
 
 def test_device_math_helpers(ctx):
     """sqrt_1_2 == sqrt on [1, 2] and the scaling-free quotient == the IEEE division for operands in its exponent band,
-    bit for bit, on 10^6 arguments each (incl. the band's edges, exact quotients, tiny / huge ratios inside the band)."""
+    bit for bit, on 10^6 random arguments each (exponents within +-250, exact quotients, tiny / huge ratios inside the band).  The band's
+    last binades, its edges, the first values outside it and operands that are hard to round are tests/test_hard_rounding_gpu.py's."""
     rng = np.random.default_rng(0)
     n = 1_000_000
     x = np.concatenate([rng.uniform(1.0, 2.0, n - 6), [1.0, 2.0, np.nextafter(1.0, 2.0), np.nextafter(2.0, 1.0), 1.5, 1.25]])
