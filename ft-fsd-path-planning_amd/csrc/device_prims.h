@@ -126,12 +126,17 @@ struct Grp {
     return __shfl(v, lane() < G - 1 ? me + 1 : me, WAVE);
 #endif
   }
-  // argmin over (value, index) pairs with "first smallest" semantics; lanes holding no candidate pass idx = -1
+  // argmin over (value, index) pairs with "first smallest" semantics; lanes holding no candidate pass idx = -1.  A NaN is
+  // larger than every number and NaNs order by index (np.argsort's order; a caller that wants np.argmin's, the first NaN, maps
+  // its NaNs below its numbers first): a total order, so every lane of the group ends with the same pair whatever the values
+  // are — with `<` and `==` alone a NaN left each lane with a candidate of its own.
   static __device__ __forceinline__ void argmin(double& v, int& idx) {
     for (int off = G / 2; off >= 1; off >>= 1) {
       double ov = shfl_xor(v, off);
       int oi = shfl_xor(idx, off);
-      bool take = (oi >= 0) && (idx < 0 || ov < v || (ov == v && oi < idx));
+      const bool vn = v != v;
+      const bool before = (ov != ov) ? (vn && oi < idx) : (vn || ov < v || (ov == v && oi < idx));
+      bool take = (oi >= 0) && (idx < 0 || before);
       if (take) {
         v = ov;
         idx = oi;

@@ -87,7 +87,9 @@ __device__ inline void matches_for_side(MatchShared& S, const Params& P, const d
     rot_apply(rot, qx[j] - sx, qy[j] - sy, vx, vy);
     double sc = (vx * vx) / r0 + (vy * vy) / r1;
     bool ok = sc < 1;
-    double a = atan2(vy, vx);
+    // (+ 0.0: the reference's rotation is a gemm, which accumulates from +0 — a zero of it is +0 where the bare fma chain gives
+    // -0.  An other-side cone ON this cone is then at the angle 0, not pi.)
+    double a = atan2(vy + 0.0, vx + 0.0);
     if (fabs(a / 2) > P.max_search_angle) ok = false;
     if (m > 1) {  // with a single other-side cone the reference's direction mask is empty
       if (acos_less(cos_between(S.d1x[i], S.d1y[i], S.d2x[j], S.d2y[j]), FSDP_PI / 2, 0.0)) ok = false;
@@ -95,14 +97,15 @@ __device__ inline void matches_for_side(MatchShared& S, const Params& P, const d
     if (ok) atomicOr(&S.anyok[i], 1);
   }
   Grp<G>::sync();
-  // nearest other-side cone (first smallest), lane = own cone
+  // nearest other-side cone (np.argmin: the first smallest, and the first NaN — the virtual cone of a zero chord — before
+  // everything), lane = own cone
   if (lane < n) {
     const double sx = px[lane], sy = py[lane];
     int best = 0;
     double bd = 0.0;
     for (int j = 0; j < m; j++) {
       double d = cdist_sq(sx, sy, qx[j], qy[j]);
-      if (j == 0 || d < bd) {
+      if (j == 0 || (bd == bd && (d < bd || d != d))) {
         bd = d;
         best = j;
       }
@@ -132,22 +135,26 @@ __device__ inline void matches_for_side(MatchShared& S, const Params& P, const d
 template <int G>
 __device__ inline int insert_virtual(MatchShared& S, int ne, int nt, double carx, double cary) {
   const int lane = Grp<G>::lane();
-  // order_to_insert = cdist(to_insert, existing).min(axis=1).argsort()
+  // order_to_insert = cdist(to_insert, existing).min(axis=1).argsort(): np.min returns a NaN if there is one, and argsort puts
+  // the NaN keys last, in index order — a rank for every lane whatever the keys are (with `<` and `==` alone two lanes took
+  // rank 0 and a slot of S.order stayed unwritten)
   if (lane < nt) {
     double b = 0.0;
     for (int j = 0; j < ne; j++) {
       double d = cdist_sq(S.tx[lane], S.ty[lane], S.ex[j], S.ey[j]);
-      if (j == 0 || d < b) b = d;
+      if (j == 0 || (b == b && (d < b || d != d))) b = d;
     }
     S.key[lane] = b;
   }
   Grp<G>::sync();
   if (lane < nt) {
     int rank = 0;
-    double k = S.key[lane];
+    const double k = S.key[lane];
+    const bool kn = k != k;
     for (int o = 0; o < nt; o++) {
-      double ko = S.key[o];
-      if (ko < k || (ko == k && o < lane)) rank++;
+      const double ko = S.key[o];
+      const bool same = (ko != ko) ? kn : ko == k;
+      if (ko < k || (kn && ko == ko) || (same && o < lane)) rank++;
     }
     S.order[rank] = lane;
   }
@@ -155,7 +162,7 @@ __device__ inline int insert_virtual(MatchShared& S, int ne, int nt, double carx
   for (int r = 0; r < nt; r++) {
     const int ti = S.order[r];
     const double cx = S.tx[ti], cy = S.ty[ti];
-    // two nearest existing cones (argsort of norms, stable)
+    // two nearest existing cones (argsort of norms, stable, NaN last: Grp::argmin's order)
     double v = 0.0;
     int idx = -1;
     if (lane < ne) {

@@ -1116,7 +1116,8 @@ __device__ __forceinline__ int sort_side_finish(SH& S, int n, int cone_type, int
       }
     }
   }
-  // argmin with np.unique's lexicographic row order as tie-break (argsort is stable for the short arrays here)
+  // argmin with np.unique's lexicographic row order as tie-break (argsort is stable for the short arrays here); a NaN cost — a
+  // configuration that steps from a cone to its coincident twin — goes last, as np.argsort puts it
   {
     int best = -1;
     double bc = 0.0;
@@ -1124,8 +1125,8 @@ __device__ __forceinline__ int sort_side_finish(SH& S, int n, int cone_type, int
     for (int c = 0; c < n_ends; c++) {
       if (!S.keep[c]) continue;
       double cc = S.cost[c];
-      bool take = best < 0 || cc < bc;
-      if (!take && cc == bc) {
+      bool take = best < 0 || cc < bc || (bc != bc && cc == cc);
+      if (!take && (cc == bc || (cc != cc && bc != bc))) {
         // lexicographic comparison of rows (ints, -1 padded)
         bool less = false;
         for (int l = 0; l < MAX_LEN; l++) {

@@ -41,7 +41,9 @@ static std::vector<char> has_potential_match(const Pts& start, const Pts& dirs, 
       Vec2 q = rot.apply(other[j].x - start[i].x, other[j].y - start[i].y);
       double s = (q.x * q.x) / r0 + (q.y * q.y) / r1;
       bool ok = s < 1;
-      double a = std::atan2(q.y, q.x);
+      // (+ 0.0: a gemm accumulates from +0, so a zero of the reference's rotation is +0 where the bare fma chain of Rot::apply
+      // gives -0 — the other-side cone ON this cone, whose angle is then 0 and not pi)
+      double a = std::atan2(q.y + 0.0, q.x + 0.0);
       if (std::fabs(a / 2) > max_search_angle) ok = false;
       if (!other_dirs.empty()) {  // empty (N==1) boolean mask indexes nothing in NumPy
         double dd = vec_angle_between(dirs[i].x, dirs[i].y, other_dirs[j].x, other_dirs[j].y);
@@ -64,17 +66,10 @@ static void matches_for_side(const Pts& cones, int cone_type, const Pts& other, 
     if (N > 1) other_dirs = match_search_directions(other, cone_type == T_RIGHT ? T_LEFT : T_RIGHT);
     std::vector<char> any = has_potential_match(cones, dirs, other, other_dirs);
     if (N == 0) return;
+    std::vector<double> row(N);
     for (int i = 0; i < M; i++) {
-      int best = 0;
-      double bd = 0;
-      for (int j = 0; j < N; j++) {
-        double d = cdist_sq(cones[i].x, cones[i].y, other[j].x, other[j].y);
-        if (j == 0 || d < bd) {
-          bd = d;
-          best = j;
-        }
-      }
-      matches[i] = best;
+      for (int j = 0; j < N; j++) row[j] = cdist_sq(cones[i].x, cones[i].y, other[j].x, other[j].y);
+      matches[i] = np_argmin(row);  // (a NaN distance — a virtual cone of a zero chord — is the minimum)
     }
     if (g_prm.matches_should_be_monotonic) {  // functional_cone_matching.py:164-171
       int current_max = matches[0];
@@ -98,14 +93,10 @@ static Pts insert_virtual(const Pts& other, const Pts& virt, Vec2 car) {
     existing = virt;
     to_insert = other;
   }
-  std::vector<double> mind(to_insert.size());
+  std::vector<double> mind(to_insert.size()), row(existing.size());
   for (size_t i = 0; i < to_insert.size(); i++) {
-    double b = 0;
-    for (size_t j = 0; j < existing.size(); j++) {
-      double d = cdist_sq(to_insert[i].x, to_insert[i].y, existing[j].x, existing[j].y);
-      if (j == 0 || d < b) b = d;
-    }
-    mind[i] = b;
+    for (size_t j = 0; j < existing.size(); j++) row[j] = cdist_sq(to_insert[i].x, to_insert[i].y, existing[j].x, existing[j].y);
+    mind[i] = row[np_argmin(row)];  // np.min: NaN if any
   }
   std::vector<int> order = argsort(mind);
   for (int oi : order) {

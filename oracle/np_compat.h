@@ -142,12 +142,22 @@ inline long arange_len(double stop, double step) {
 }
 
 // stable argsort of a short array (NumPy's default sort is insertion sort for n<=16 and
-// otherwise only differs from stable on exact ties)
+// otherwise only differs from stable on exact ties).  NaN sorts last, as in NumPy (and `<` alone would be no ordering).
 inline std::vector<int> argsort(const std::vector<double>& v) {
   std::vector<int> idx(v.size());
   for (size_t i = 0; i < v.size(); i++) idx[i] = (int)i;
-  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return v[a] < v[b]; });
+  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return v[a] < v[b] || (v[b] != v[b] && v[a] == v[a]); });
   return idx;
+}
+// np.argmin / np.min of a non-empty run: the first smallest, and a NaN is smaller than everything (the first NaN wins; np.min
+// returns it)
+inline int np_argmin(const std::vector<double>& v) {
+  int best = 0;
+  for (size_t j = 1; j < v.size(); j++) {
+    if (v[best] != v[best]) break;
+    if (v[j] < v[best] || v[j] != v[j]) best = (int)j;
+  }
+  return best;
 }
 
 // sign of det([[1,x0,y0],[1,x1,y1],[1,x2,y2]]) the way numpy.linalg.det gets it:

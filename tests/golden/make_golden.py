@@ -862,3 +862,99 @@ def gemv_semantics_golden():
 if __name__ == "__main__" and "--gemv-only" in sys.argv:
     refharness.load()
     gemv_semantics_golden()
+
+
+def match_degenerate_golden():
+    """Sides with coincident cones (tests/match_support.py degenerate(): a pair at the start, the end, the interior of a side,
+    a side of two coincident cones, triples, a cone shared by both sides) through the reference's ConeMatching stage object
+    (the pipeline's parameters: cfg.get_default_matching_kwargs, non-monotonic), and 64 frames with one cone reported twice
+    (match_support.duplicated_cone_frames) through the whole planner.  A zero chord makes the reference's search direction
+    0 / 0: it goes on with NaN (warnings, no exception) — what it returns then, or which exception it raises, is the fixture:
+    stage_* arrays for the sides, the usual frame layout with the prefix plan_ for the frames."""
+    m = refharness.load()
+    sys.path.insert(0, str(ROOT / "tests"))
+    import match_support
+    from fsd_path_planning import config as cfg
+    from fsd_path_planning.cone_matching.core_cone_matching import ConeMatching, ConeMatchingInput
+
+    import fsd_path_planning.cone_matching.functional_cone_matching as fcm
+
+    # Exact ties of FINITE values in the two argsorts of the insertion (the order of the cones to insert; the two nearest
+    # existing cones, where a tie among the three smallest distances can change the pair or its order): NumPy's default
+    # argsort is not stable, which of the tied entries comes first depends on its build (this one: AVX-512).  Recorded per
+    # case as stage_tie, like first_k_tie / knn_tie of the frame sets: the oracle's stable order is not pinned there.
+    ties = [False]
+
+    class Watched(np.ndarray):
+        first_three_only = False
+
+        def argsort(self, *a, **kw):
+            v = np.sort(np.asarray(self)[np.isfinite(np.asarray(self))])
+            if (np.diff(v[:3] if self.first_three_only else v) == 0).any():
+                ties[0] = True
+            return np.asarray(self).argsort(*a, **kw)
+
+    class WatchedNorm(Watched):
+        first_three_only = True
+
+    class Linalg:
+        @staticmethod
+        def norm(x, *a, **kw):
+            r = np.linalg.norm(x, *a, **kw)
+            return r.view(WatchedNorm) if isinstance(r, np.ndarray) and r.ndim == 1 else r
+
+    class NumpyProxy:
+        linalg = Linalg()
+
+        def __getattr__(self, name):
+            return getattr(np, name)
+
+    orig_np, orig_cdist = fcm.np, fcm.my_cdist_sq_euclidean
+    fcm.np = NumpyProxy()
+    fcm.my_cdist_sq_euclidean = lambda a, b: orig_cdist(a, b).view(Watched)
+    mission = m["MissionTypes"].trackdrive
+    mk = cfg.get_default_matching_kwargs(mission)
+    mk["matches_should_be_monotonic"] = False  # the pipeline's choice (full_pipeline.py:65)
+    cases = match_support.degenerate()
+    F = len(cases)
+    out = dict(stage_names=np.array([n for n, _ in cases]), stage_ok=np.zeros(F, bool), stage_exc=np.array([""] * F, dtype="U24"),
+               stage_n_left=np.zeros(F, np.int32), stage_n_right=np.zeros(F, np.int32), stage_left=np.zeros((F, MAX_LEN, 2)),
+               stage_right=np.zeros((F, MAX_LEN, 2)), stage_poses=np.zeros((F, 4)), stage_n_left_v=np.zeros(F, np.int32),
+               stage_n_right_v=np.zeros(F, np.int32), stage_left_v=np.zeros((F, MAX_MATCH, 2)), stage_right_v=np.zeros((F, MAX_MATCH, 2)),
+               stage_l2r=np.full((F, MAX_MATCH), -1, np.int32), stage_r2l=np.full((F, MAX_MATCH), -1, np.int32), stage_tie=np.zeros(F, bool))
+    for k, (_name, (l, r, p)) in enumerate(cases):
+        ties[0] = False
+        out["stage_n_left"][k], out["stage_n_right"][k] = len(l), len(r)
+        out["stage_left"][k, : len(l)], out["stage_right"][k, : len(r)], out["stage_poses"][k] = l, r, p
+        sc = [np.zeros((0, 2)) for _ in range(5)]
+        sc[int(m["ConeTypes"].LEFT)], sc[int(m["ConeTypes"].RIGHT)] = l.copy(), r.copy()
+        stage = ConeMatching(**mk)
+        stage.set_new_input(ConeMatchingInput(sc, p[:2].copy(), p[2:].copy()))
+        try:
+            with np.errstate(all="ignore"):
+                lv, rv, l2r, r2l = stage.run_cone_matching()
+        except Exception as e:  # noqa: BLE001 (which class is part of the fixture)
+            out["stage_exc"][k] = type(e).__name__
+            continue
+        finally:
+            out["stage_tie"][k] = ties[0]
+        out["stage_ok"][k] = True
+        assert len(lv) <= MAX_MATCH and len(rv) <= MAX_MATCH
+        out["stage_n_left_v"][k], out["stage_n_right_v"][k] = len(lv), len(rv)
+        out["stage_left_v"][k, : len(lv)], out["stage_right_v"][k, : len(rv)] = lv, rv
+        out["stage_l2r"][k, : len(lv)], out["stage_r2l"][k, : len(rv)] = l2r, r2l
+    fcm.np, fcm.my_cdist_sq_euclidean = orig_np, orig_cdist
+    off, cones, poses = match_support.duplicated_cone_frames(synth)
+    with np.errstate(all="ignore"):
+        d = capture(off, cones, poses)
+    for key, v in d.items():
+        if not key.startswith("fit_"):  # (the splines are pinned on the ordinary sets)
+            out["plan_" + key] = v
+    np.savez_compressed(HERE / "match_degenerate.npz", **out)
+    print("match_degenerate sides", F, "ok", int(out["stage_ok"].sum()), "exc", sorted(set(out["stage_exc"].tolist()) - {""}), "ties", int(out["stage_tie"].sum()),
+          "NaN in the lists of", int(sum(np.isnan(out["stage_left_v"][k]).any() or np.isnan(out["stage_right_v"][k]).any() for k in range(F))),
+          "| frames", len(d["ok"]), "ok", int(d["ok"].sum()), "exc", sorted(set(d["exc"].tolist()) - {""}))
+
+
+if __name__ == "__main__" and "--match-degenerate-only" in sys.argv:  # (-only: without it the frame sets above are captured again first)
+    match_degenerate_golden()

@@ -155,6 +155,32 @@ def plan_batch(offsets, xyt, poses, n_threads: int = 1) -> np.ndarray:
     return out
 
 
+def match(left, right, pose) -> np.ndarray:
+    """The match stage alone (fsdo_match): sorted sides (n, 2) and the pose -> a record whose match fields are set."""
+    left = np.ascontiguousarray(left, dtype=np.float64).reshape(-1, 2)
+    right = np.ascontiguousarray(right, dtype=np.float64).reshape(-1, 2)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    assert len(left) <= MAX_LEN and len(right) <= MAX_LEN and pose.size == 4
+    out = np.zeros(1, dtype=RESULT_DTYPE)
+    lib().fsdo_match(_p(left), ctypes.c_int(len(left)), _p(right), ctypes.c_int(len(right)), _p(pose), ctypes.c_void_p(out.ctypes.data))
+    return out[0]
+
+
+def path(left_v, right_v, l2r, r2l, pose) -> np.ndarray:
+    """The path stage alone (fsdo_path) on a match stage's lists with virtual cones and their matches -> a record whose
+    path, path_fallback and status are set (a fresh planner: the default previous path)."""
+    left_v = np.ascontiguousarray(left_v, dtype=np.float64).reshape(-1, 2)
+    right_v = np.ascontiguousarray(right_v, dtype=np.float64).reshape(-1, 2)
+    l2r = np.ascontiguousarray(l2r, dtype=np.int32)
+    r2l = np.ascontiguousarray(r2l, dtype=np.int32)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    assert len(l2r) == len(left_v) <= MAX_MATCH and len(r2l) == len(right_v) <= MAX_MATCH and pose.size == 4
+    out = np.zeros(1, dtype=RESULT_DTYPE)
+    lib().fsdo_path(_p(left_v), ctypes.c_int(len(left_v)), _p(right_v), ctypes.c_int(len(right_v)), _p(l2r, ctypes.c_int32),
+                    _p(r2l, ctypes.c_int32), _p(pose), ctypes.c_void_p(out.ctypes.data))
+    return out[0]
+
+
 def default_path() -> np.ndarray:
     out = np.zeros((PATH_POINTS, 4))
     lib().fsdo_default_path(_p(out))

@@ -156,3 +156,55 @@ def test_oracle_with_host_libm_is_the_reference_bit_for_bit(golden_dir, name):
         assert np.array_equal(res[k]["path"], ref, equal_nan=True), (k, np.nanmax(np.abs(res[k]["path"] - ref)))
         n += 1
     assert n == int(g["ok"].sum())
+
+
+def test_oracle_matches_reference_on_degenerate_sides(golden_dir):
+    """Sides with coincident cones (match_support.degenerate(); make_golden.py --match-degenerate-only runs the reference's
+    ConeMatching stage object on them).  A zero chord makes the reference's search direction 0 / 0; it raises nothing and goes
+    on with NaN: the cone finds no match, its virtual cone is NaN, np.min / np.argmin return the NaN, np.argsort puts it last,
+    every comparison with it is False.  The oracle returns the reference's lists and matches bit for bit, NaN for NaN —
+    except where an exact tie of finite distances is decided by NumPy's unstable argsort (stage_tie, recorded by the generator:
+    coincident cones among the EXISTING cones of an insertion are equally far from everything), where the reference's result
+    belongs to its NumPy build, like first_k_tie / knn_tie of the frame sets."""
+    import match_support
+
+    g = np.load(golden_dir / "match_degenerate.npz")
+    named = match_support.degenerate()
+    assert [n for n, _c in named] == g["stage_names"].tolist()
+    assert g["stage_ok"].all() and 3 * int(g["stage_tie"].sum()) < len(named)  # the reference raised nowhere; most cases are pinned
+    n_nan = 0
+    for k, (name, (left, right, pose)) in enumerate(named):
+        assert np.array_equal(left, g["stage_left"][k, : g["stage_n_left"][k]]) and np.array_equal(right, g["stage_right"][k, : g["stage_n_right"][k]])
+        assert np.array_equal(pose, g["stage_poses"][k])
+        r = oracle_lib.match(left, right, pose)
+        assert int(r["status"]) == 0, name
+        if g["stage_tie"][k]:
+            continue
+        for f in ("n_left_v", "n_right_v", "left_v", "right_v", "l2r", "r2l"):
+            assert np.array_equal(r[f], g["stage_" + f][k], equal_nan=True), (name, f, r[f], g["stage_" + f][k])
+        n_nan += bool(np.isnan(r["left_v"]).any() or np.isnan(r["right_v"]).any())
+    assert n_nan >= 20  # NaN virtual cones are what this pins
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["libm", "detmath"])
+def test_oracle_matches_reference_on_duplicated_cone_frames(golden_dir, mode):
+    """64 frames with one cone reported twice, through the reference's whole planner (match_degenerate.npz plan_*).  Which of
+    the two twins a sorted side names is the reference's unstable argsort's choice (every frame has knn_tie): the sides are
+    compared by coordinates, everything after them as usual."""
+    g = np.load(golden_dir / "match_degenerate.npz")
+    off, cones, poses = g["plan_offsets"], g["plan_cones"], g["plan_poses"]
+    assert g["plan_ok"].all()
+    with oracle_lib.math_mode(mode):
+        res = oracle_lib.plan_batch(off, cones, poses, n_threads=4)
+    assert (res["status"] == 0).all()
+    for k in range(len(res)):
+        xy = cones[off[k] : off[k + 1], :2]
+        for s in ("left", "right"):
+            n = int(g[f"plan_n_{s}"][k])
+            assert int(res[f"n_{s}"][k]) == n, (k, s)
+            assert np.array_equal(xy[res[f"{s}_idx"][k][:n]], xy[g[f"plan_{s}_idx"][k][:n]]), (k, s)
+        for f in ("n_left_v", "n_right_v", "left_v", "right_v", "l2r", "r2l"):
+            assert np.array_equal(res[f][k], g["plan_" + f][k], equal_nan=True), (k, f)
+        p, q = res["path"][k], g["plan_path"][k]
+        e = float(np.nanmax(np.abs(p - q)))
+        assert e <= parity.PATH_TOL or (int(res["path_fallback"][k]) & parity.ARC_FLAG and parity.is_sample_count_flip(p, q)), (k, e)
