@@ -13,6 +13,8 @@
 #include <cstdlib>
 #include <string>
 
+#include "host_buffers.h"  // DeviceBuf
+
 namespace fsdp_comm {
 
 struct Api {
@@ -74,8 +76,7 @@ inline bool load() {
 struct Comm {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
-  void* d_buf = nullptr;  // device staging of the host-buffer collectives
-  size_t cap = 0;
+  fsdp::DeviceBuf<char> d_buf;  // device staging of the host-buffer collectives (bytes)
 };
 
 }  // namespace fsdp_comm

@@ -29,6 +29,7 @@
 #include "fsdp_comm.h"
 #include "sort_rank_kernels.h"  // (behind the pass kernels: the kernels in front of it keep their order in the code object)
 #include "sequence_launch.h"    // (the chain kernels of fsdp_plan_sequence are a translation unit of their own: sequence_lib.hip)
+#include "host_buffers.h"       // (no kernels: DeviceBuf / PinnedBuf and the stores a slot and a context own)
 
 using namespace fsdp;
 
@@ -40,20 +41,23 @@ static thread_local std::string g_create_error;
 
 constexpr int SORT_BIG_BLOCKS = 32;
 
-// one batch of frames on the device (CSR offsets, flattened cones, poses, optional previous paths)
-struct Inputs {
-  int32_t* d_off = nullptr;
-  double* d_cones = nullptr;
-  double* d_poses = nullptr;
-  double* d_prev = nullptr;  // (n_frames,40,4), allocated on first use
-  int cap_frames = 0;
-  size_t cap_cones = 0;
-  int cap_prev = 0;
-  int n_frames = 0;
-  int max_cones = 0;      // most cones in a frame (picks the sorting kernel's state size)
-  bool use_prev = false;  // d_prev holds this batch's previous paths
-  std::vector<int32_t> off_rebased;  // offsets - cone_offsets[0] for the copy paths (kept until the slot's next batch)
+// A stream or an event that is destroyed with its owner (move-only, handed to the runtime as the handle it holds)
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Handle& operator=(Handle&& o) noexcept {
+    std::swap(h, o.h);
+    return *this;
+  }
+  ~Handle() {
+    if (h) (void)Destroy(h);
+  }
+  operator H() const { return h; }
 };
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
 
 // one batch of frames as the caller hands it over (host memory, checked by check_batch).  cone_offsets[0] = off[0] >= 0: the
 // batch's cones are the rows [off[0], off[n]) of `cones` — a slice of a larger batch is handed over by pointing at its offsets
@@ -82,44 +86,19 @@ constexpr int N_TRAILERS = SLOT_QUEUE + 1;  // pass trailers per slot: one per t
 // one pass slot: a stream, the inputs of the batch submitted to it, the intermediates of a pass and its results
 struct Work {
   int index = 0;
-  hipStream_t stream = nullptr;
-  Inputs in;
-  SortOut* d_sort = nullptr;
-  MatchOut* d_match = nullptr;
-  PathOut* d_path = nullptr;
-  double* d_arena = nullptr;  // per-frame working polyline + basis cache (ARENA_DOUBLES doubles), HBM/L2 scratch
-  int* d_big = nullptr;       // [0] counter + frames beyond sort_kernel's LDS capacities (n + 1 ints)
-  int* d_retry = nullptr;     // [0] counter + frames for the exact re-plan kernel (n + 1 ints)
-  PathMid* d_mid = nullptr;   // hand-over records of the three-kernel path stage
-  fsdp_frame_result* d_result = nullptr;  // the pass's results in the ABI's layout (assemble_kernel)
-  SkidInfo* d_skid_info = nullptr;        // skidpad contexts
-  int32_t* d_skid_status = nullptr;       // skid_reloc_kernel's status of the step this slot holds
+  Stream stream;  // (first: whatever the slot owns is freed before its stream goes; fsdp_destroy / release_slot synchronise it before)
+  InputStore<> in;
+  PassStore<> buf;   // the intermediates of a pass and its result block
   bool skid_attempted = true;             // ... which ran for that step (not once every planner is relocalized)
-  SortSharedBig* d_sort_big = nullptr;    // frame states of sort_big_kernel, allocated when the route is first needed
-  // fsdp_plan_sequence (sequence_kernel.h): the run-head list of a sequence pass, the planners' initial and final previous paths
-  int* d_seq = nullptr;                   // [0] heads, [1] frames planned again, then (frame, predecessor) per head
-  double* d_seq_init = nullptr;           // (planners, 40, 4)
-  double* d_seq_final = nullptr;
-  size_t seq_cap_frames = 0, seq_cap_planners = 0;
-  // fsdp_plan_sequence_cached (sequence_cache_kernel.h): the per-frame records of the speculative sort, hit codes, irregular frames per planner
-  SeqSpecRec* d_seqc_rec = nullptr;
-  int8_t* d_seqc_hits = nullptr;
-  int32_t* d_seqc_resorted = nullptr;
-  size_t seqc_cap_frames = 0, seqc_cap_planners = 0;
-  int cap_frames = 0;
-  // use_unknown_cones = False (filter_kernel.h): the batch without its UNKNOWN cones, and the way back for the indices
-  int32_t* f_cnt = nullptr;
-  int32_t* f_off = nullptr;
-  double* f_cones = nullptr;
-  int32_t* f_map = nullptr;
-  int f_cap_frames = 0;
-  size_t f_cap_cones = 0;
-  PassTrailer* h_trailer = nullptr;  // N_TRAILERS of them: pinned, host-coherent, written by assemble_kernel: a ticket's entry
+  DeviceBuf<SortSharedBig> d_sort_big;    // frame states of sort_big_kernel, allocated when the route is first needed
+  FilterStore<> filt;                     // use_unknown_cones = False
+  SeqStore<> seq_buf;                     // fsdp_plan_sequence
+  SeqCacheStore<> seqc_buf;               // fsdp_plan_sequence_cached
+  PinnedBuf<PassTrailer> h_trailer;  // N_TRAILERS of them: pinned, host-coherent, written by assemble_kernel: a ticket's entry
                                      // index, or SLOT_QUEUE (resident / blocking passes)
-  PassTrailer* d_trailer = nullptr;  // their device address
   int seq = 0;                       // passes launched on this slot
   // the most recent pass launched on the slot (verify_pass re-runs it with the route kernels when they were needed)
-  const Inputs* pass_in = nullptr;
+  const InputStore<>* pass_in = nullptr;
   bool ran_big = false, ran_retry = false, unverified = false, pass_skid = false;
   // A sequence pass (fsdp_plan_sequence*, fsdp_submit_sequence*) as its ticket describes it: the ticket's pass — and the rerun
   // fsdp_collect issues when the pass lacked a route — resolves the planners' previous-path chains between the path stage and the
@@ -157,16 +136,15 @@ struct Work {
     bool compact = false;                  // user_results holds compact records: fsdp_path_result (skidpad step) or
                                            // fsdp_compact_result (fsdp_submit_compact)
     size_t rec_bytes() const { return !compact ? sizeof(fsdp_frame_result) : (skid ? sizeof(PathOut) : sizeof(fsdp_compact_result)); }
-    fsdp_frame_result* h_stage = nullptr;  // pinned + mapped: the assembly kernel writes a pageable caller's results here
-    char* h_in = nullptr;                  // pinned + mapped: a small pageable batch is packed here and read by the sorting kernel itself
-    SkidInfo* h_info = nullptr;            // pinned
-    SeqSeg* h_seg = nullptr;               // pinned + mapped: the per-step segments of a planner slice (seq_slice_in_kernel reads them)
-    double* h_fin = nullptr;               // pinned + mapped: seq_final_kernel writes a pageable caller's final_prev rows here
-    size_t cap_stage = 0, cap_in = 0, cap_info = 0, cap_seg = 0, cap_fin = 0;  // their capacities (grow_pinned)
+    PinnedBuf<fsdp_frame_result> h_stage;  // pinned + mapped: the assembly kernel writes a pageable caller's results here
+    PinnedBuf<char> h_in;                  // pinned + mapped: a small pageable batch is packed here and read by the sorting kernel itself
+    PinnedBuf<SkidInfo> h_info;            // pinned
+    PinnedBuf<SeqSeg> h_seg;               // pinned + mapped: the per-step segments of a planner slice (seq_slice_in_kernel reads them)
+    PinnedBuf<double> h_fin;               // pinned + mapped: seq_final_kernel writes a pageable caller's final_prev rows here
     SeqPass sq;                            // a sequence ticket's pass
     int cache_lo = -1;                     // >= 0: a chunk of a lock-step call that advances the sorting cache (the _cached sorting
                                            // kernels); its frame 0 is this planner
-    hipEvent_t done = nullptr;             // recorded behind the ticket's last command
+    Event done;                            // recorded behind the ticket's last command
     // the entry is free again: what the caller owned, and what described his pass, is forgotten
     void release() {
       id = -1;
@@ -183,10 +161,10 @@ struct fsdp_ctx {
   int device = 0;
   int mission = 0;
   hipStream_t stream = nullptr;  // = slot[0].stream
-  hipEvent_t ev[8] = {};
+  Event ev[8];
   std::string err;
   Work slot[FSDP_MAX_OVERLAP];
-  Inputs res;             // the resident batch of fsdp_upload (every slot's fsdp_run pass reads it)
+  InputStore<> res;       // the resident batch of fsdp_upload (every slot's fsdp_run pass reads it)
   bool resident = false;  // res describes a batch fsdp_run may plan
   bool res_checked = false;  // a verified pass over the resident batch has set expect_big / expect_retry exactly
   // The most recent pass (launch_pass, a skidpad step), what fsdp_download, fsdp_resident_frames and fsdp_debug_* read: they
@@ -197,11 +175,11 @@ struct fsdp_ctx {
     bool in_result = false;  // its results are in the slot's result block (an fsdp_run / fsdp_time_runs pass)
     bool whole = false;      // it covered the whole call (not a chunk of a blocking call)
   } last;
-  double* d_default_path = nullptr;  // (40,4)
+  DeviceBuf<double> d_default_path;  // (40,4)
   Params params;                     // configuration constants (fsdp_params) ...
-  Params* d_params = nullptr;        // ... and their device copy, read by every kernel
-  double* d_chord = nullptr;         // (40,2) almost-straight chord (trivial path of the skidpad mission)
-  double* d_gpath = nullptr;         // PathPlanner.global_path (n_gpath,2), or NULL
+  DeviceBuf<Params> d_params;        // ... and their device copy, read by every kernel
+  DeviceBuf<double> d_chord;         // (40,2) almost-straight chord (trivial path of the skidpad mission)
+  DeviceBuf<double> d_gpath;         // PathPlanner.global_path (n_gpath,2), or NULL
   int n_gpath = 0;
   // fsdp_set_option (include/fsdp.h): what a test or a measurement may pin; 0 = the library's own choice
   int force_path_mode = 0;    // "path_mode": 0 = by batch size; 1 = one kernel (64 lanes per frame); 2 = three kernels
@@ -226,61 +204,45 @@ struct fsdp_ctx {
   bool always_route = false;  // "always_route": both route kernels with every pass (tests: results never depend on the prediction)
   long long reruns = 0;  // passes re-run by verify_pass (diagnostics: fsdp_route_stats)
   bool no_sort128 = false;  // "no_sort128": always the 255-cone state of the sorting kernel (tests)
-  std::vector<hipEvent_t> tev;  // per-launch timing events of fsdp_time_runs
+  std::vector<Event> tev;  // per-launch timing events of fsdp_time_runs
   int timed_iters = 0, timed_stages = 0;  // the most recent fsdp_time_runs (fsdp_time_results reads its events)
   bool time_main_only = false;            // fsdp_time_detail: events only around the path stage's main kernel
   bool time_kernel_clock = false;         // fsdp_time_detail bit 1: the refit kernel's launches note their own start / end clock
   std::vector<unsigned> tev_recorded;     // per pass of the most recent fsdp_time_runs: which of its events were recorded
-  unsigned long long* d_kclock = nullptr;  // [2 * kclock_cap]: first-wavefront-start | last-wavefront-end of the refit kernel, per timed pass
-  int kclock_cap = 0;
+  DeviceBuf<unsigned long long> d_kclock;  // [2 * iters]: first-wavefront-start | last-wavefront-end of the refit kernel, per timed pass
   bool primed[FSDP_MAX_OVERLAP] = {};     // slot i has executed a pass of the current packing (its stream / hardware queue is set up)
   // skidpad mission
-  double* d_table = nullptr;
-  double* d_noise = nullptr;
+  DeviceBuf<double> d_table, d_noise;
   SkidTables tables = {};
   fsdp_comm::Comm comm;  // RCCL communicator of this rank (fsdp_comm_init), or none
   double skid_consts[5] = {};  // reference centres (right xy, left xy) + table spacing, computed on the device
   bool have_tables = false;
-  SkidState* d_skid = nullptr;
-  SkidState* d_skid_backup = nullptr;
-  uint32_t* d_skid_sync = nullptr;   // [0] ticket counter of skid_path_kernel, [1 + i] steps instance i has published
+  DeviceBuf<SkidState> d_skid, d_skid_backup;
+  DeviceBuf<uint32_t> d_skid_sync;   // [0] ticket counter of skid_path_kernel, [1 + i] steps instance i has published
   uint32_t skid_ticket_base = 0;
   int skid_step_no = 0;              // steps submitted since fsdp_skidpad_reset
   bool skid_all_reloc = false;       // a collected step reported every planner relocalized: cones have no reader any more
   int skid_group_env = 0;            // "skid_group": steps per launch when the caller submits ahead (0: chosen from the instance count)
   // fsdp_skidpad_time_groups: HIP events around the packed kernels of every group of steps (select | prep | fit | finish | commit)
   bool skid_time_groups = false;
-  std::vector<hipEvent_t> skid_group_ev;  // six per group
+  std::vector<Event> skid_group_ev;       // six per group
   std::vector<int> skid_group_frames;     // (instance, step) pairs per group
   std::string skid_group_names;
   int skid_pack_min = 2048;          // (instance, step) pairs from which a group goes through the packed kernels (one step of
                                      // 2048 planners: 1.49 M frames/s packed, 1.40 M a wavefront each; 1024: 0.98 / 1.08 M)
-  // workspace of a group that goes through the packed kernels, frame = step * n_instances + instance
-  double* d_g_arena = nullptr;
-  PathMid* d_g_mid = nullptr;
-  PathOut* d_g_out = nullptr;
-  int* d_g_retry = nullptr;
-  SkidSel* d_g_sel = nullptr;
-  size_t g_cap = 0;
+  SkidGroupStore<> group;            // workspace of a group that goes through the packed kernels
   int skid_pending[SKID_GROUP_MAX] = {};  // slots whose step waits for its group's launch, oldest first
   int n_skid_pending = 0;
   int n_instances = 0;
-  // pinned host staging of the stage-level entry points (grow_pinned)
-  SortOut* h_sort = nullptr;
-  MatchOut* h_match = nullptr;
-  PathOut* h_path = nullptr;
-  size_t cap_sort = 0, cap_match = 0, cap_path = 0;
+  // pinned host staging of the stage-level entry points
+  PinnedBuf<SortOut> h_sort;
+  PinnedBuf<MatchOut> h_match;
+  PinnedBuf<PathOut> h_path;
   // the sorting cache (fsdp_sort_cache_reset, sort_cache.h): one entry per planner in each of two buffers; the kernels of a
   // call read buffer cache_cur and write the other, and the call swaps them once it has succeeded
   int n_cache = 0;
   int cache_cur = 0;
-  SortCacheHdr* d_cache_hdr[2] = {};
-  double* d_cache_xyt[2] = {};
-  int32_t* d_cache_off[2] = {};
-  size_t cache_rows[2] = {};                  // rows the cone stores hold
-  std::vector<int32_t> cache_layout[2];       // host copies of the two buffers' region offsets
-  std::vector<int32_t> cache_region;          // rows of a planner's region: the most cones it was ever given
-  int8_t* d_cache_hits = nullptr;
+  SortCacheStore<> cache;                     // the two buffers, their layout and the planners' regions
   std::vector<int8_t> cache_hits;             // codes of the most recent call
   // (no field says what the call in progress is: a pass is described by the Pass its caller builds — for a ticket, from the ticket)
 };
@@ -305,118 +267,28 @@ static hipError_t copy_sync(fsdp_ctx* c, void* dst, const void* src, size_t byte
   return hipStreamSynchronize(c->stream);
 }
 
-template <class T>
-static hipError_t regrow(T*& p, size_t count) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  return hipMalloc(&p, sizeof(T) * (count ? count : 1));
-}
-
-// room for a batch's inputs (buffers only grow; the caller has made sure nothing in flight reads them)
-static int ensure_inputs(fsdp_ctx* c, Inputs& in, int n_frames, size_t n_cones, bool with_prev) {
-  if (n_frames > in.cap_frames) {
-    HIP_TRY(c, regrow(in.d_off, (size_t)n_frames + 1));
-    HIP_TRY(c, regrow(in.d_poses, 4 * (size_t)n_frames));
-    in.cap_frames = n_frames;
-  }
-  if (n_cones > in.cap_cones || !in.d_cones) {
-    // (with headroom: a replay's cone count creeps up from step to step, and hipFree synchronises the whole device)
-    const size_t want = n_cones + n_cones / 2 + 64;
-    HIP_TRY(c, regrow(in.d_cones, 3 * want));
-    in.cap_cones = want;
-  }
-  if (with_prev && n_frames > in.cap_prev) {
-    HIP_TRY(c, regrow(in.d_prev, (size_t)PATH_POINTS * 4 * (size_t)n_frames));
-    in.cap_prev = n_frames;
-  }
-  return 0;
-}
-static void free_inputs(Inputs& in) {
-  (void)hipFree(in.d_off);
-  (void)hipFree(in.d_cones);
-  (void)hipFree(in.d_poses);
-  (void)hipFree(in.d_prev);
-  in = Inputs();
-}
-
 // stream, trailer and intermediates of slot w for passes of up to n frames
 static int ensure_work(fsdp_ctx* c, Work& w, int n) {
-  if (!w.stream) HIP_TRY(c, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+  if (!w.stream) HIP_TRY(c, hipStreamCreateWithFlags(&w.stream.h, hipStreamNonBlocking));
   if (!w.h_trailer) {
-    HIP_TRY(c, hipHostMalloc((void**)&w.h_trailer, sizeof(PassTrailer) * N_TRAILERS, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(c, w.h_trailer.reserve(N_TRAILERS, 0, Pin::MappedCoherent));
     memset(w.h_trailer, 0, sizeof(PassTrailer) * N_TRAILERS);
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&w.d_trailer, w.h_trailer, 0));
   }
-  if (n <= w.cap_frames) return 0;
+  if ((size_t)n <= w.buf.frames()) return 0;
   HIP_TRY(c, hipStreamSynchronize(w.stream));
   if (c->last.slot == w.index) c->last = fsdp_ctx::LastPass();  // (its results and scratch are about to go)
-  const size_t m = (size_t)n;
-  HIP_TRY(c, regrow(w.d_sort, m));
-  HIP_TRY(c, regrow(w.d_match, m));
-  HIP_TRY(c, regrow(w.d_path, m));
-  HIP_TRY(c, regrow(w.d_arena, (size_t)ARENA_DOUBLES * m));
-  HIP_TRY(c, regrow(w.d_big, m + 1));
-  HIP_TRY(c, regrow(w.d_retry, m + 1));
-  HIP_TRY(c, regrow(w.d_mid, m));
-  HIP_TRY(c, regrow(w.d_result, m));
-  if (c->mission == 2) {
-    HIP_TRY(c, regrow(w.d_skid_info, m));
-    HIP_TRY(c, regrow(w.d_skid_status, m));
-  }
+  HIP_TRY(c, w.buf.reserve((size_t)n, c->mission == 2));
   // the list counters are zero between passes: assemble_kernel resets them at the end of every pass
-  HIP_TRY(c, hipMemsetAsync(w.d_big, 0, sizeof(int), w.stream));
-  HIP_TRY(c, hipMemsetAsync(w.d_retry, 0, sizeof(int), w.stream));
-  w.cap_frames = n;
+  HIP_TRY(c, hipMemsetAsync(w.buf.d_big, 0, sizeof(int), w.stream));
+  HIP_TRY(c, hipMemsetAsync(w.buf.d_retry, 0, sizeof(int), w.stream));
   return 0;
 }
-static void free_work(Work& w) {
+// the slot gives back its buffers and its stream (nothing of it is in flight)
+static void release_slot(Work& w) {
   if (w.stream) (void)hipStreamSynchronize(w.stream);
-  free_inputs(w.in);
-  (void)hipFree(w.d_sort);
-  (void)hipFree(w.d_match);
-  (void)hipFree(w.d_path);
-  (void)hipFree(w.d_arena);
-  (void)hipFree(w.d_big);
-  (void)hipFree(w.d_retry);
-  (void)hipFree(w.d_mid);
-  (void)hipFree(w.d_result);
-  (void)hipFree(w.d_skid_info);
-  (void)hipFree(w.d_skid_status);
-  (void)hipFree(w.d_sort_big);
-  (void)hipFree(w.d_seq);
-  (void)hipFree(w.d_seq_init);
-  (void)hipFree(w.d_seq_final);
-  (void)hipFree(w.d_seqc_rec);
-  (void)hipFree(w.d_seqc_hits);
-  (void)hipFree(w.d_seqc_resorted);
-  (void)hipFree(w.f_cnt);
-  (void)hipFree(w.f_off);
-  (void)hipFree(w.f_cones);
-  (void)hipFree(w.f_map);
-  if (w.h_trailer) (void)hipHostFree(w.h_trailer);
-  for (Work::Ticket& t : w.tk) {
-    if (t.h_stage) (void)hipHostFree(t.h_stage);
-    if (t.h_in) (void)hipHostFree(t.h_in);
-    if (t.h_info) (void)hipHostFree(t.h_info);
-    if (t.h_seg) (void)hipHostFree(t.h_seg);
-    if (t.h_fin) (void)hipHostFree(t.h_fin);
-    if (t.done) (void)hipEventDestroy(t.done);
-  }
-}
-
-// a page-locked host block `p` of `cap` T's holds at least `count` (the block is replaced, with room for at least `want`: what
-// it held is gone; nothing queued may use it any more).  flags: mapped where a kernel reads or writes the block, default where
-// only a copy command does.
-template <class T>
-static hipError_t grow_pinned(T*& p, size_t& cap, size_t count, unsigned flags, size_t want = 0) {
-  if (count <= cap) return hipSuccess;
-  if (p) (void)hipHostFree(p);
-  p = nullptr;
-  cap = 0;
-  want = std::max(count, want);
-  const hipError_t e = hipHostMalloc((void**)&p, sizeof(T) * want, flags);
-  if (e == hipSuccess) cap = want;
-  return e;
+  const int idx = w.index;
+  w = Work();
+  w.index = idx;
 }
 
 // p as the GPU addresses it if p is page-locked host memory (fsdp_host_alloc, fsdp_host_register: mapped into the device's
@@ -442,13 +314,13 @@ static bool is_pinned(const void* p, size_t bytes) {
   return de != nullptr && de - dv == (ptrdiff_t)(bytes - 1);
 }
 // Where a ticket's pass writes for the caller: `user` itself if its `bytes` are page-locked over their whole extent (the kernels
-// write it over PCIe), else the ticket's own mapped block of `count` T's, grown with room for `want` (*staged: fsdp_collect copies
-// it out).  *dev: the device view of whichever it is.
+// write it over PCIe), else the ticket's own mapped block of `count` T's, grown with room for `want` (what it held is gone: nothing
+// queued may use it any more; *staged: fsdp_collect copies it out).  *dev: the device view of whichever it is.
 template <class T>
-static int host_target(fsdp_ctx* c, T* user, size_t bytes, T*& block, size_t& cap, size_t count, size_t want, const char* what, T** dev, bool* staged) {
+static int host_target(fsdp_ctx* c, T* user, size_t bytes, PinnedBuf<T>& block, size_t count, size_t want, const char* what, T** dev, bool* staged) {
   *staged = !is_pinned(user, bytes);
-  if (*staged) HIP_TRY(c, grow_pinned(block, cap, count, hipHostMallocMapped, want));
-  *dev = (T*)device_view(*staged ? block : user);
+  if (*staged) HIP_TRY(c, block.reserve(count, want, Pin::Mapped));
+  *dev = (T*)device_view(*staged ? block.get() : user);
   if (*dev) return 0;
   c->err = std::string("internal: ") + what + " is not mapped into the device's address space";
   return 2;
@@ -472,7 +344,7 @@ static bool inputs_pinned(const Batch& b) {
 // did not get.  Results never depend on the route or on the prediction.
 constexpr int MAX_STAGES = FSDP_MAX_STAGES;
 struct StageEvents {  // optional timing: ev[k] is recorded before stage k, ev[n_stages] after the last
-  hipEvent_t* ev = nullptr;
+  Event* ev = nullptr;
   int n = 0;
   bool main_only = false;   // record only the events around the path stage's main kernel (and the last one of the pass)
   unsigned recorded = 0;    // bit k: ev[k] was recorded
@@ -495,13 +367,13 @@ static bool sort128(const fsdp_ctx* c, const Inputs& in) { return in.max_cones <
 static SortCacheView cache_view(const fsdp_ctx* c, int base) {
   const int p = c->cache_cur, x = 1 - p;
   SortCacheView v;
-  v.prev = c->d_cache_hdr[p];
-  v.next = c->d_cache_hdr[x];
-  v.prev_xyt = c->d_cache_xyt[p];
-  v.prev_off = c->d_cache_off[p];
-  v.next_xyt = c->d_cache_xyt[x];
-  v.next_off = c->d_cache_off[x];
-  v.hits = c->d_cache_hits;
+  v.prev = c->cache.d_hdr[p];
+  v.next = c->cache.d_hdr[x];
+  v.prev_xyt = c->cache.d_xyt[p];
+  v.prev_off = c->cache.d_off[p];
+  v.next_xyt = c->cache.d_xyt[x];
+  v.next_off = c->cache.d_off[x];
+  v.hits = c->cache.d_hits;
   v.base = base;
   return v;
 }
@@ -514,16 +386,16 @@ static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs&
   a.off = in.d_off;
   a.cones = in.d_cones;
   a.poses = in.d_poses;
-  a.sorted = q.d_sort;
-  a.big = q.d_big;
+  a.sorted = q.buf.d_sort;
+  a.big = q.buf.d_big;
   a.big_state = nullptr;  // (launch_sort_big allocates the blocks on first use)
   a.big_blocks = SORT_BIG_BLOCKS;
   a.small = sort128(c, in);
   a.prm = c->d_params;
-  a.rec = q.d_seqc_rec;
+  a.rec = q.seqc_buf.d_seqc_rec;
   a.cache = cache_view(c, 0);  // (frame f is planner f % n_planners: seq_cache_mark_kernel takes the view as it is)
-  a.hits = q.d_seqc_hits;
-  a.resorted = q.d_seqc_resorted;
+  a.hits = q.seqc_buf.d_seqc_hits;
+  a.resorted = q.seqc_buf.d_seqc_resorted;
   return a;
 }
 
@@ -549,38 +421,38 @@ static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& s
   const dim3 grid(in.n_frames), block(WAVE);
   if (var.kind == SortVariant::RANKED)
     hipLaunchKernelGGL((small ? sort_kernel_128_ranked : sort_kernel_ranked), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
-                       in.d_poses, q.d_sort, q.d_big, c->d_params, *var.rank);
+                       in.d_poses, q.buf.d_sort, q.buf.d_big, c->d_params, *var.rank);
   else if (var.kind == SortVariant::CACHED)
     hipLaunchKernelGGL((small ? sort_kernel_128_cached : sort_kernel_cached), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
-                       in.d_poses, q.d_sort, q.d_big, c->d_params, st, var.cache);
+                       in.d_poses, q.buf.d_sort, q.buf.d_big, c->d_params, st, var.cache);
   else if (var.kind == SortVariant::SPEC)
     fsdp_seqc_launch_sort(q.stream, var.seqc);
   else
     hipLaunchKernelGGL((small ? sort_kernel_128 : sort_kernel), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
-                       q.d_sort, q.d_big, c->d_params, st);
+                       q.buf.d_sort, q.buf.d_big, c->d_params, st);
   names += std::string(small ? "sort_kernel_128" : "sort_kernel") + var.suffix();
 }
 static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in, std::string& names, const SortVariant& var) {
-  if (!q.d_sort_big) HIP_TRY(c, hipMalloc(&q.d_sort_big, sizeof(SortSharedBig) * SORT_BIG_BLOCKS));
+  HIP_TRY(c, q.d_sort_big.reserve(SORT_BIG_BLOCKS));
   const dim3 grid(SORT_BIG_BLOCKS), block(WAVE);
   if (var.kind == SortVariant::RANKED)
-    hipLaunchKernelGGL(sort_big_kernel_ranked, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
+    hipLaunchKernelGGL(sort_big_kernel_ranked, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.buf.d_sort, q.buf.d_big, q.d_sort_big,
                        c->d_params, *var.rank, var.scratch);
   else if (var.kind == SortVariant::CACHED)
-    hipLaunchKernelGGL(sort_big_kernel_cached, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
+    hipLaunchKernelGGL(sort_big_kernel_cached, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.buf.d_sort, q.buf.d_big, q.d_sort_big,
                        c->d_params, var.cache);
   else if (var.kind == SortVariant::SPEC) {
     var.seqc->big_state = q.d_sort_big;
     fsdp_seqc_launch_sort_big(q.stream, var.seqc);
   } else
-    hipLaunchKernelGGL(sort_big_kernel, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_big, q.d_sort_big,
+    hipLaunchKernelGGL(sort_big_kernel, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.buf.d_sort, q.buf.d_big, q.d_sort_big,
                        c->d_params);
   names += std::string("sort_big_kernel") + var.suffix();
   return 0;
 }
 static void launch_match(fsdp_ctx* c, Work& q, const Inputs& in) {
   hipLaunchKernelGGL(match_kernel<MATCH_G>, dim3((in.n_frames + WAVE / MATCH_G - 1) / (WAVE / MATCH_G)), dim3(WAVE), 0, q.stream,
-                     in.n_frames, in.d_off, in.d_cones, in.d_poses, q.d_sort, q.d_match, c->d_params);
+                     in.n_frames, in.d_off, in.d_cones, in.d_poses, q.buf.d_sort, q.buf.d_match, c->d_params);
 }
 // ---- the path stage of one pass ------------------------------------------------------------------------------------------
 // Small batches (<= PATH_SMALL_BATCH frames: single-frame calls, latency): one kernel, one frame per wavefront.
@@ -589,27 +461,27 @@ static void launch_match(fsdp_ctx* c, Work& q, const Inputs& in) {
 template <int GF, int NKC = FIT_KNOTS>
 static void launch_fit(fsdp_ctx* c, Work& q, int n, const StageEvents* t = nullptr) {
   hipLaunchKernelGGL((fit_kernel<GF, NKC>), dim3((n + WAVE / GF - 1) / (WAVE / GF)), dim3(WAVE), 0, q.stream, n,
-                     q.d_arena, q.d_mid, q.d_retry, c->d_params, t ? t->clock_first : nullptr, t ? t->clock_last : nullptr);
+                     q.buf.d_arena, q.buf.d_mid, q.buf.d_retry, c->d_params, t ? t->clock_first : nullptr, t ? t->clock_last : nullptr);
 }
 template <int G, int NKC = FIT_KNOTS>
 static void launch_prep(fsdp_ctx* c, Work& q, const Inputs& in, const double* prev) {
   const int n = in.n_frames;
-  hipLaunchKernelGGL((path_prep_kernel<G, NKC>), dim3((n + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, q.stream, n, in.d_poses, q.d_match,
-                     c->d_default_path, prev, c->d_gpath, c->n_gpath, q.d_arena, q.d_path, q.d_mid, q.d_retry, c->d_params);
+  hipLaunchKernelGGL((path_prep_kernel<G, NKC>), dim3((n + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, q.stream, n, in.d_poses, q.buf.d_match,
+                     c->d_default_path, prev, c->d_gpath, c->n_gpath, q.buf.d_arena, q.buf.d_path, q.buf.d_mid, q.buf.d_retry, c->d_params);
 }
 template <int G, int NKC = FIT_KNOTS>
 static void launch_finish(fsdp_ctx* c, Work& q, int n) {
-  hipLaunchKernelGGL((path_finish_kernel<G, NKC>), dim3((n + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, q.stream, n, q.d_arena, q.d_mid, q.d_path,
-                     q.d_retry, c->d_params);
+  hipLaunchKernelGGL((path_finish_kernel<G, NKC>), dim3((n + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, q.stream, n, q.buf.d_arena, q.buf.d_mid, q.buf.d_path,
+                     q.buf.d_retry, c->d_params);
 }
 
 // the same steps through the packed kernels (csrc/skidpad_kernel.h "steps in flight, many frames per wavefront")
 static void skid_group_mark(fsdp_ctx* c) {  // (timing of the groups' kernels on request: fsdp_skidpad_time_groups)
   if (!c->skid_time_groups) return;
-  hipEvent_t e;
-  if (hipEventCreate(&e) != hipSuccess) return;
+  Event e;
+  if (hipEventCreate(&e.h) != hipSuccess) return;
   (void)hipEventRecord(e, c->stream);
-  c->skid_group_ev.push_back(e);
+  c->skid_group_ev.push_back(std::move(e));
 }
 template <int G, int GF>
 static void launch_skid_packed_kernels(fsdp_ctx* c, int frames) {
@@ -618,14 +490,14 @@ static void launch_skid_packed_kernels(fsdp_ctx* c, int frames) {
     c->skid_group_names = "skid_select_kernel,skid_prep_kernel<" + std::to_string(G) + ">,fit_kernel<" + std::to_string(GF) + ">,path_finish_kernel<" +
                           std::to_string(G) + ">,skid_commit_kernel";
   skid_group_mark(c);
-  hipLaunchKernelGGL(skid_prep_kernel<G>, dim3((frames + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, xs, frames, c->d_g_sel, c->tables, c->d_chord,
-                     c->d_default_path, c->d_g_arena, c->d_g_mid);
+  hipLaunchKernelGGL(skid_prep_kernel<G>, dim3((frames + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, xs, frames, c->group.d_g_sel, c->tables, c->d_chord,
+                     c->d_default_path, c->group.d_g_arena, c->group.d_g_mid);
   skid_group_mark(c);
-  hipLaunchKernelGGL((fit_kernel<GF, FIT_KNOTS>), dim3((frames + WAVE / GF - 1) / (WAVE / GF)), dim3(WAVE), 0, xs, frames, c->d_g_arena, c->d_g_mid,
-                     c->d_g_retry, c->d_params, (unsigned long long*)nullptr, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((fit_kernel<GF, FIT_KNOTS>), dim3((frames + WAVE / GF - 1) / (WAVE / GF)), dim3(WAVE), 0, xs, frames, c->group.d_g_arena, c->group.d_g_mid,
+                     c->group.d_g_retry, c->d_params, (unsigned long long*)nullptr, (unsigned long long*)nullptr);
   skid_group_mark(c);
-  hipLaunchKernelGGL(path_finish_kernel<G>, dim3((frames + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, xs, frames, c->d_g_arena, c->d_g_mid, c->d_g_out,
-                     c->d_g_retry, c->d_params);
+  hipLaunchKernelGGL(path_finish_kernel<G>, dim3((frames + WAVE / G - 1) / (WAVE / G)), dim3(WAVE), 0, xs, frames, c->group.d_g_arena, c->group.d_g_mid, c->group.d_g_out,
+                     c->group.d_g_retry, c->d_params);
   skid_group_mark(c);
 }
 
@@ -663,10 +535,10 @@ static bool launch_path(fsdp_ctx* c, Work& q, const Inputs& in, StageEvents* t, 
     const bool mono16 = c->force_path_mode != 1 && c->params.max_deg != 3 && in_flight > PATH_SMALL_BATCH;
     if (mono16)
       hipLaunchKernelGGL(path_kernel<PATH_G_LATENCY>, dim3((n + WAVE / PATH_G_LATENCY - 1) / (WAVE / PATH_G_LATENCY)), dim3(WAVE), 0, q.stream, n, in.d_poses,
-                         q.d_match, c->d_default_path, prev, c->d_gpath, c->n_gpath, q.d_arena, q.d_path, q.d_retry, c->d_params);
+                         q.buf.d_match, c->d_default_path, prev, c->d_gpath, c->n_gpath, q.buf.d_arena, q.buf.d_path, q.buf.d_retry, c->d_params);
     else
-      hipLaunchKernelGGL(path_kernel<PATH_G_SMALL>, dim3(n), dim3(WAVE), 0, q.stream, n, in.d_poses, q.d_match, c->d_default_path, prev,
-                         c->d_gpath, c->n_gpath, q.d_arena, q.d_path, q.d_retry, c->d_params);
+      hipLaunchKernelGGL(path_kernel<PATH_G_SMALL>, dim3(n), dim3(WAVE), 0, q.stream, n, in.d_poses, q.buf.d_match, c->d_default_path, prev,
+                         c->d_gpath, c->n_gpath, q.buf.d_arena, q.buf.d_path, q.buf.d_retry, c->d_params);
     names += mono16 ? "path_kernel<16>," : "path_kernel<64>,";
     return split;
   }
@@ -715,8 +587,8 @@ static void launch_path_retry(fsdp_ctx* c, Work& q, const Inputs& in, bool sized
   const double* prev = in.use_prev ? in.d_prev : nullptr;
   int rb = in.n_frames < 1024 ? in.n_frames : 1024;  // one wavefront per SIMD at most; blocks beyond the list's length return at once
   if (sized) rb = std::max(1, std::min(rb, 16 + 2 * c->retry_hint));
-  hipLaunchKernelGGL(path_retry_kernel, dim3(rb), dim3(WAVE), 0, q.stream, in.d_poses, q.d_match, c->d_default_path, prev, c->d_gpath,
-                     c->n_gpath, q.d_arena, q.d_path, q.d_retry, c->d_params);
+  hipLaunchKernelGGL(path_retry_kernel, dim3(rb), dim3(WAVE), 0, q.stream, in.d_poses, q.buf.d_match, c->d_default_path, prev, c->d_gpath,
+                     c->n_gpath, q.buf.d_arena, q.buf.d_path, q.buf.d_retry, c->d_params);
 }
 // The description of one pass, beyond its slot and its inputs: what it writes where, where its sorting kernel finds the batch, which
 // kernels it is made of and what it is planned for.  The default is a pass over the resident batch; a ticket's pass is built from
@@ -748,16 +620,16 @@ static void launch_assemble(fsdp_ctx* c, Work& q, int n, const Pass& pass, bool 
   q.seq++;
   hipStream_t s = skid ? c->stream : q.stream;
   const bool filtered = !skid && !c->params.use_unknown_cones;  // (indices back into the caller's cone lists: launch_filter's map)
-  const int32_t* remap = filtered ? q.f_map : nullptr;
-  const int32_t* remap_off = filtered ? q.f_off : nullptr;
+  const int32_t* remap = filtered ? q.filt.f_map : nullptr;
+  const int32_t* remap_off = filtered ? q.filt.f_off : nullptr;
   if (pass.compact) {  // fsdp_compact_result records (into the slot's result block or the caller's page-locked buffer)
-    hipLaunchKernelGGL(assemble_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, q.d_sort, q.d_match, q.d_path,
-                       (fsdp_compact_result*)(pass.host ? pass.host : q.d_result), q.d_big, q.d_retry, q.d_trailer + pass.trailer, q.seq, remap, remap_off);
+    hipLaunchKernelGGL(assemble_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, q.buf.d_sort, q.buf.d_match, q.buf.d_path,
+                       (fsdp_compact_result*)(pass.host ? pass.host : q.buf.d_result), q.buf.d_big, q.buf.d_retry, q.h_trailer.device() + pass.trailer, q.seq, remap, remap_off);
     return;
   }
-  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, skid ? (const SortOut*)nullptr : q.d_sort,
-                     skid ? (const MatchOut*)nullptr : q.d_match, q.d_path, pass.host ? pass.host : q.d_result, q.d_big, q.d_retry, q.d_trailer + pass.trailer,
-                     q.seq, (const int32_t*)(pass.info ? q.d_skid_info : nullptr), (int32_t*)pass.info, pass.info ? (int)(sizeof(SkidInfo) / 4) * n : 0,
+  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, skid ? (const SortOut*)nullptr : q.buf.d_sort,
+                     skid ? (const MatchOut*)nullptr : q.buf.d_match, q.buf.d_path, pass.host ? pass.host : q.buf.d_result, q.buf.d_big, q.buf.d_retry, q.h_trailer.device() + pass.trailer,
+                     q.seq, (const int32_t*)(pass.info ? q.buf.d_skid_info : nullptr), (int32_t*)pass.info, pass.info ? (int)(sizeof(SkidInfo) / 4) * n : 0,
                      remap, remap_off);
 }
 
@@ -770,68 +642,62 @@ static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const Pass& 
   a.n_planners = sq.s.n;
   a.n_steps = sq.s.n_steps;
   a.poses = in.d_poses;
-  a.matched = q.d_match;
-  a.initial_prev = sq.init ? q.d_seq_init : nullptr;
+  a.matched = q.buf.d_match;
+  a.initial_prev = sq.init ? q.seq_buf.d_seq_init : nullptr;
   a.gpath = c->d_gpath;
   a.n_gpath = c->n_gpath;
-  a.arena = q.d_arena;
-  a.out = q.d_path;
-  a.seq = q.d_seq;
+  a.arena = q.buf.d_arena;
+  a.out = q.buf.d_path;
+  a.seq = q.seq_buf.d_seq;
   a.final_prev = sq.final_dev;
-  a.replanned_out = &(q.d_trailer + pass.trailer)->pad;
+  a.replanned_out = &(q.h_trailer.device() + pass.trailer)->pad;
   a.prm = c->d_params;
   fsdp_seq_launch(q.stream, &a);
 }
 
 // use_unknown_cones = False: the batch without its UNKNOWN cones into the slot's filter buffers; returns the view the
 // stage kernels plan (same poses / previous paths)
-static int launch_filter(fsdp_ctx* c, Work& q, const Inputs& in, Inputs* view) {
-  if (in.cap_frames > q.f_cap_frames || !q.f_off) {
+static int launch_filter(fsdp_ctx* c, Work& q, const InputStore<>& in, Inputs* view) {
+  if (!q.filt.fits(in.frames(), in.cone_rows())) {  // (room for whatever the batch's own buffers can hold)
     HIP_TRY(c, hipStreamSynchronize(q.stream));
-    HIP_TRY(c, regrow(q.f_cnt, (size_t)in.cap_frames));
-    HIP_TRY(c, regrow(q.f_off, (size_t)in.cap_frames + 1));
-    q.f_cap_frames = in.cap_frames;
-  }
-  if (in.cap_cones > q.f_cap_cones || !q.f_cones) {
-    HIP_TRY(c, hipStreamSynchronize(q.stream));
-    HIP_TRY(c, regrow(q.f_cones, 3 * in.cap_cones));
-    HIP_TRY(c, regrow(q.f_map, in.cap_cones));
-    q.f_cap_cones = in.cap_cones;
+    HIP_TRY(c, q.filt.reserve(in.frames(), in.cone_rows()));
   }
   const int n = in.n_frames;
-  hipLaunchKernelGGL(filter_count_kernel, dim3(n), dim3(WAVE), 0, q.stream, n, in.d_off, in.d_cones, q.f_cnt);
-  hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(1024), 0, q.stream, n, q.f_cnt, q.f_off);
-  hipLaunchKernelGGL(filter_scatter_kernel, dim3(n), dim3(WAVE), 0, q.stream, n, in.d_off, in.d_cones, q.f_off, q.f_cones, q.f_map);
-  *view = in;
-  view->d_off = q.f_off;
-  view->d_cones = q.f_cones;
+  hipLaunchKernelGGL(filter_count_kernel, dim3(n), dim3(WAVE), 0, q.stream, n, in.d_off, in.d_cones, q.filt.f_cnt);
+  hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(1024), 0, q.stream, n, q.filt.f_cnt, q.filt.f_off);
+  hipLaunchKernelGGL(filter_scatter_kernel, dim3(n), dim3(WAVE), 0, q.stream, n, in.d_off, in.d_cones, q.filt.f_off, q.filt.f_cones, q.filt.f_map);
+  *view = in.view();
+  view->d_off = q.filt.f_off;
+  view->d_cones = q.filt.f_cones;
   return 0;
 }
 
 // sorting -> matching -> path stage -> result assembly of batch `in` on slot q as `pass` describes the pass (Pass() = a pass over the
 // resident batch into the slot's result block); it becomes the context's most recent pass
-static int launch_pass(fsdp_ctx* c, Work& q, const Inputs& in_, const Pass& pass) {
+static int launch_pass(fsdp_ctx* c, Work& q, const InputStore<>& in_, const Pass& pass) {
   StageEvents* const t = pass.events;
+  if ((size_t)in_.n_frames > q.buf.frames()) {  // (a growth that failed left the slot empty: an error code, never a launch on what is not there)
+    c->err = "internal: slot " + std::to_string(q.index) + " holds no room for a pass of " + std::to_string(in_.n_frames) + " frames";
+    return 2;
+  }
   c->primed[q.index] = true;
   const bool with_big = pass.force_routes || c->always_route || c->expect_big;
   const bool with_retry = pass.force_routes || c->always_route || c->expect_retry;
-  Inputs fin;
-  const bool filtered = !c->params.use_unknown_cones;
-  if (filtered)
-    if (int rc = launch_filter(c, q, in_, &fin)) return rc;
-  const Inputs& in = filtered ? fin : in_;
+  Inputs in = in_.view();
+  if (!c->params.use_unknown_cones)
+    if (int rc = launch_filter(c, q, in_, &in)) return rc;
   std::string names;
   if (c->poison) {
     // (tests) whatever a previous pass, another batch or the allocator left in the slot's buffers is gone: 0xFF bytes = NaNs, -1 indices
     const size_t m = (size_t)in.n_frames;
-    (void)hipMemsetAsync(q.d_sort, 0xff, sizeof(SortOut) * m, q.stream);
-    (void)hipMemsetAsync(q.d_match, 0xff, sizeof(MatchOut) * m, q.stream);
-    (void)hipMemsetAsync(q.d_path, 0xff, sizeof(PathOut) * m, q.stream);
-    (void)hipMemsetAsync(q.d_mid, 0xff, sizeof(PathMid) * m, q.stream);
-    (void)hipMemsetAsync(q.d_arena, 0xff, sizeof(double) * (size_t)ARENA_DOUBLES * m, q.stream);
-    (void)hipMemsetAsync(q.d_result, 0xff, sizeof(fsdp_frame_result) * m, q.stream);
-    (void)hipMemsetAsync(q.d_big + 1, 0xff, sizeof(int) * m, q.stream);
-    (void)hipMemsetAsync(q.d_retry + 1, 0xff, sizeof(int) * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_sort, 0xff, sizeof(SortOut) * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_match, 0xff, sizeof(MatchOut) * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_path, 0xff, sizeof(PathOut) * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_mid, 0xff, sizeof(PathMid) * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_arena, 0xff, sizeof(double) * (size_t)ARENA_DOUBLES * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_result, 0xff, sizeof(fsdp_frame_result) * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_big + 1, 0xff, sizeof(int) * m, q.stream);
+    (void)hipMemsetAsync(q.buf.d_retry + 1, 0xff, sizeof(int) * m, q.stream);
   }
   fsdp_seqc_launch_args seqc;
   SortVariant var = pass.sort;
@@ -1031,8 +897,8 @@ static int check_batch(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
 }
 
 // room for batch b in `in`, which then describes it (the caller fills the buffers)
-static int take_batch(fsdp_ctx* c, Inputs& in, const Batch& b) {
-  if (int rc = ensure_inputs(c, in, b.n > 0 ? b.n : 1, b.total, b.prev != nullptr)) return rc;
+static int take_batch(fsdp_ctx* c, InputStore<>& in, const Batch& b) {
+  HIP_TRY(c, in.reserve(b.n > 0 ? (size_t)b.n : 1, b.total, b.prev != nullptr));
   in.n_frames = b.n;
   in.max_cones = b.max_cones;
   in.use_prev = b.prev != nullptr;
@@ -1040,7 +906,7 @@ static int take_batch(fsdp_ctx* c, Inputs& in, const Batch& b) {
 }
 
 // host -> device of a batch on `stream` (asynchronous for page-locked sources)
-static int upload_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, const Batch& b) {
+static int upload_inputs(fsdp_ctx* c, InputStore<>& in, hipStream_t stream, const Batch& b) {
   if (int rc = take_batch(c, in, b)) return rc;
   if (b.n == 0) return 0;
   const int32_t* off = b.off;
@@ -1060,7 +926,7 @@ static int upload_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, const Batc
 }
 
 // the same through stage_in_kernel: every source is page-locked host memory (inputs_pinned)
-static int stage_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, const Batch& b) {
+static int stage_inputs(fsdp_ctx* c, InputStore<>& in, hipStream_t stream, const Batch& b) {
   if (int rc = take_batch(c, in, b)) return rc;
   if (b.n == 0) return 0;
   CopySegs S;
@@ -1069,29 +935,17 @@ static int stage_inputs(fsdp_ctx* c, Inputs& in, hipStream_t stream, const Batch
   // are read from row b — nothing is rebased or copied on the host, nothing pageable is handed to the runtime (round-5 advisor:
   // a pageable copy made the host wait for the stream's earlier work)
   S.rebase = b.off[0];
-  S.seg[S.n++] = CopySeg{device_view(b.off), in.d_off, sizeof(int32_t) * ((unsigned long long)b.n + 1)};
-  if (b.total) S.seg[S.n++] = CopySeg{device_view(b.cones + 3 * (size_t)b.off[0]), in.d_cones, sizeof(double) * 3ull * b.total};
-  S.seg[S.n++] = CopySeg{device_view(b.poses), in.d_poses, sizeof(double) * 4ull * (unsigned long long)b.n};
-  if (b.prev) S.seg[S.n++] = CopySeg{device_view(b.prev), in.d_prev, sizeof(double) * PATH_POINTS * 4ull * (unsigned long long)b.n};
+  S.seg[S.n++] = CopySeg{device_view(b.off), in.d_off.get(), sizeof(int32_t) * ((unsigned long long)b.n + 1)};
+  if (b.total) S.seg[S.n++] = CopySeg{device_view(b.cones + 3 * (size_t)b.off[0]), in.d_cones.get(), sizeof(double) * 3ull * b.total};
+  S.seg[S.n++] = CopySeg{device_view(b.poses), in.d_poses.get(), sizeof(double) * 4ull * (unsigned long long)b.n};
+  if (b.prev) S.seg[S.n++] = CopySeg{device_view(b.prev), in.d_prev.get(), sizeof(double) * PATH_POINTS * 4ull * (unsigned long long)b.n};
   hipLaunchKernelGGL(stage_in_kernel, dim3(256), dim3(256), 0, stream, S);
   return 0;
 }
 
 // ---- the sorting cache ----------------------------------------------------------------------------------------------------
 static void cache_free(fsdp_ctx* c) {
-  for (int b = 0; b < 2; b++) {
-    (void)hipFree(c->d_cache_hdr[b]);
-    (void)hipFree(c->d_cache_xyt[b]);
-    (void)hipFree(c->d_cache_off[b]);
-    c->d_cache_hdr[b] = nullptr;
-    c->d_cache_xyt[b] = nullptr;
-    c->d_cache_off[b] = nullptr;
-    c->cache_rows[b] = 0;
-    c->cache_layout[b].clear();
-  }
-  (void)hipFree(c->d_cache_hits);
-  c->d_cache_hits = nullptr;
-  c->cache_region.clear();
+  c->cache = SortCacheStore<>();
   c->cache_hits.clear();
   c->n_cache = 0;
   c->cache_cur = 0;
@@ -1110,30 +964,26 @@ static int cache_prepare(fsdp_ctx* c, int n_frames, const int32_t* off, const ch
   std::vector<int32_t> lay((size_t)n_frames + 1);
   size_t rows = 0;
   for (int i = 0; i < n_frames; i++) {
-    c->cache_region[(size_t)i] = std::max(c->cache_region[(size_t)i], off[i + 1] - off[i]);
+    c->cache.region[(size_t)i] = std::max(c->cache.region[(size_t)i], off[i + 1] - off[i]);
     lay[(size_t)i] = (int32_t)rows;
-    rows += (size_t)c->cache_region[(size_t)i];
+    rows += (size_t)c->cache.region[(size_t)i];
     if (rows > 0x7fffffff) {
       c->err = std::string(who) + ": the sorting cache's cone store exceeds 2^31 rows";
       return 1;
     }
   }
   lay[(size_t)n_frames] = (int32_t)rows;
-  if (rows > c->cache_rows[x]) {
-    const size_t want = rows + rows / 2 + 64;
-    HIP_TRY(c, regrow(c->d_cache_xyt[x], 3 * want));
-    c->cache_rows[x] = want;
-  }
-  if (lay != c->cache_layout[x]) {
-    HIP_TRY(c, copy_sync(c, c->d_cache_off[x], lay.data(), sizeof(int32_t) * lay.size(), hipMemcpyHostToDevice));
-    c->cache_layout[x].swap(lay);
+  HIP_TRY(c, c->cache.reserve_rows(x, rows));
+  if (lay != c->cache.layout[x]) {
+    HIP_TRY(c, copy_sync(c, c->cache.d_off[x], lay.data(), sizeof(int32_t) * lay.size(), hipMemcpyHostToDevice));
+    c->cache.layout[x].swap(lay);
   }
   return 0;
 }
 
 // after a successful call: its hit codes to the host, and its entries become the previous ones
 static int cache_finish(fsdp_ctx* c) {
-  HIP_TRY(c, copy_sync(c, c->cache_hits.data(), c->d_cache_hits, c->cache_hits.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(c, copy_sync(c, c->cache_hits.data(), c->cache.d_hits, c->cache_hits.size(), hipMemcpyDeviceToHost));
   c->cache_cur = 1 - c->cache_cur;
   return 0;
 }
@@ -1230,9 +1080,9 @@ int fsdp_create(int device, int mission, const fsdp_params* params, fsdp_ctx** o
   c->mission = mission;
   for (int i = 0; i < FSDP_MAX_OVERLAP; i++) c->slot[i].index = i;
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->slot[0].stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->slot[0].stream.h, hipStreamNonBlocking);
   c->stream = c->slot[0].stream;
-  for (int i = 0; i < 8 && e == hipSuccess; i++) e = hipEventCreate(&c->ev[i]);
+  for (int i = 0; i < 8 && e == hipSuccess; i++) e = hipEventCreate(&c->ev[i].h);
   c->params.max_n_neighbors = pp.max_n_neighbors;
   c->params.max_length = pp.max_length;
   c->params.max_dist = pp.max_dist;
@@ -1254,9 +1104,9 @@ int fsdp_create(int device, int mission, const fsdp_params* params, fsdp_ctx** o
   c->params.centers_cap = 0;
   c->params.centers = nullptr;
   c->params.n_centers = nullptr;
-  if (e == hipSuccess) e = hipMalloc(&c->d_params, sizeof(Params));
+  if (e == hipSuccess) e = c->d_params.reserve(1);
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_params, &c->params, sizeof(Params), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMalloc(&c->d_default_path, sizeof(double) * PATH_POINTS * 4);
+  if (e == hipSuccess) e = c->d_default_path.reserve((size_t)PATH_POINTS * 4);
   if (e != hipSuccess) {
     g_create_error = std::string("fsdp_create: ") + hipGetErrorString(e);
     delete c;
@@ -1267,16 +1117,14 @@ int fsdp_create(int device, int mission, const fsdp_params* params, fsdp_ctx** o
   {
     double chord[CHORD_POINTS][2];
     default_chord_points(chord);
-    double*& d_chord = c->d_chord;
-    double* d_arena0 = nullptr;
-    e = hipMalloc(&d_chord, sizeof(chord));
-    if (e == hipSuccess) e = hipMalloc(&d_arena0, sizeof(double) * ARENA_DOUBLES);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_chord, chord, sizeof(chord), hipMemcpyHostToDevice, c->stream);
+    DeviceBuf<double> d_arena0;
+    e = c->d_chord.reserve(sizeof(chord) / sizeof(double));
+    if (e == hipSuccess) e = d_arena0.reserve(ARENA_DOUBLES);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_chord, chord, sizeof(chord), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(default_path_kernel, dim3(1), dim3(WAVE), 0, c->stream, d_chord, d_arena0, c->d_default_path, c->d_params);
+      hipLaunchKernelGGL(default_path_kernel, dim3(1), dim3(WAVE), 0, c->stream, c->d_chord, d_arena0, c->d_default_path, c->d_params);
       e = hipStreamSynchronize(c->stream);
     }
-    if (d_arena0) (void)hipFree(d_arena0);
     if (e != hipSuccess) {
       g_create_error = std::string("fsdp_create(default path): ") + hipGetErrorString(e);
       delete c;
@@ -1293,36 +1141,7 @@ void fsdp_destroy(fsdp_ctx* c) {
   for (int i = 0; i < FSDP_MAX_OVERLAP; i++)
     if (c->slot[i].stream) (void)hipStreamSynchronize(c->slot[i].stream);
   (void)fsdp_comm_destroy(c);
-  free_inputs(c->res);
-  (void)hipFree(c->d_gpath);
-  (void)hipFree(c->d_chord);
-  (void)hipFree(c->d_table);
-  (void)hipFree(c->d_noise);
-  (void)hipFree(c->d_skid);
-  for (hipEvent_t e : c->skid_group_ev) (void)hipEventDestroy(e);
-  (void)hipFree(c->d_skid_backup);
-  (void)hipFree(c->d_skid_sync);
-  (void)hipFree(c->d_g_arena);
-  (void)hipFree(c->d_g_mid);
-  (void)hipFree(c->d_g_out);
-  (void)hipFree(c->d_g_retry);
-  (void)hipFree(c->d_g_sel);
-  (void)hipFree(c->d_default_path);
-  (void)hipFree(c->d_params);
-  cache_free(c);
-  if (c->h_sort) (void)hipHostFree(c->h_sort);
-  if (c->h_match) (void)hipHostFree(c->h_match);
-  if (c->h_path) (void)hipHostFree(c->h_path);
-  for (int i = 0; i < FSDP_MAX_OVERLAP; i++) {
-    Work& w = c->slot[i];
-    free_work(w);
-    if (w.stream) (void)hipStreamDestroy(w.stream);
-  }
-  for (hipEvent_t e : c->tev) (void)hipEventDestroy(e);
-  (void)hipFree(c->d_kclock);
-  for (int i = 0; i < 8; i++)
-    if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  delete c;
+  delete c;  // (every buffer, stream and event goes with its owner)
 }
 
 // ---- page-locked host memory for the asynchronous entry points ----------------------------------------------------------
@@ -1366,6 +1185,7 @@ int fsdp_upload(fsdp_ctx* c, int n_frames, const int32_t* off, const double* con
   Batch b;
   if (int rc = check_batch(c, n_frames, off, cones, poses, nullptr, &b)) return rc;
   if (int rc = sync_all(c)) return rc;  // passes in flight still read the old inputs
+  c->resident = false;  // (until the new batch stands: a failed upload leaves no batch to plan)
   if (int rc = ensure_slots(c, n_frames > 0 ? n_frames : 1)) return rc;
   if (int rc = upload_inputs(c, c->res, c->stream, b)) return rc;
   c->resident = true;
@@ -1385,19 +1205,15 @@ int fsdp_set_overlap(fsdp_ctx* c, int depth) {
   // flight planned 3.9 instead of 5.1 M frames/s until those queues were released)
   for (int i = depth; i < FSDP_MAX_OVERLAP; i++) {
     Work& w = c->slot[i];
-    if (!w.stream && !w.d_sort && !w.h_trailer) continue;
-    free_work(w);
-    if (w.stream) (void)hipStreamDestroy(w.stream);
-    const int idx = w.index;
-    w = Work();
-    w.index = idx;
+    if (!w.stream && !w.buf.d_sort && !w.h_trailer) continue;
+    release_slot(w);
   }
   c->overlap = depth;
   c->turn = 0;
   if (c->last.slot >= depth) c->last = fsdp_ctx::LastPass();  // (released above)
   c->last_ticket_slot = -1;
   for (bool& p : c->primed) p = false;  // the kernels of a pass depend on the frames in flight (launch_path)
-  return ensure_slots(c, std::max(1, c->slot[0].cap_frames));
+  return ensure_slots(c, std::max(1, (int)c->slot[0].buf.frames()));
 }
 
 int fsdp_run(fsdp_ctx* c) {
@@ -1443,7 +1259,7 @@ int fsdp_download(fsdp_ctx* c, fsdp_frame_result* results) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
   Work& q = c->slot[c->last.slot];  // the most recent pass
-  HIP_TRY(c, hipMemcpyAsync(results, q.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
+  HIP_TRY(c, hipMemcpyAsync(results, q.buf.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   return 0;
 }
@@ -1461,7 +1277,7 @@ int fsdp_set_previous_paths(fsdp_ctx* c, const double* prev_paths) {
     return 1;
   }
   if (int rc = sync_all(c)) return rc;
-  if (int rc = ensure_inputs(c, c->res, c->res.n_frames, c->res.cap_cones, true)) return rc;
+  HIP_TRY(c, c->res.reserve((size_t)c->res.n_frames, c->res.cone_rows(), true));
   HIP_TRY(c, copy_sync(c, c->res.d_prev, prev_paths, sizeof(double) * PATH_POINTS * 4 * (size_t)c->res.n_frames, hipMemcpyHostToDevice));
   c->res.use_prev = true;
   c->res_checked = false;
@@ -1473,12 +1289,11 @@ int fsdp_set_global_path(fsdp_ctx* c, const double* xy, int n) {
   if (c->outstanding) return busy_error(c, "fsdp_set_global_path");
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
-  if (c->d_gpath) (void)hipFree(c->d_gpath);
-  c->d_gpath = nullptr;
+  c->d_gpath.reset();
   c->n_gpath = 0;
   c->res_checked = false;
   if (n == 0) return 0;
-  HIP_TRY(c, hipMalloc(&c->d_gpath, sizeof(double) * 2 * (size_t)n));
+  HIP_TRY(c, c->d_gpath.reserve(2 * (size_t)n));
   HIP_TRY(c, copy_sync(c, c->d_gpath, xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice));
   c->n_gpath = n;
   return 0;
@@ -1509,31 +1324,13 @@ constexpr size_t SMALL_BATCH_BYTES = 256 * 1024;
 // ---- sequence tickets ---------------------------------------------------------------------------------------------------------
 constexpr size_t SEQ_PREV_DOUBLES = (size_t)PATH_POINTS * 4;  // one planner's row of initial_prev / final_prev
 
-// a frame count the device has no room for is an error code: whatever was replaced on the way is replaced again next time
-static void seq_no_room(Work& q) {
-  q.cap_frames = q.in.cap_frames = q.in.cap_prev = 0;
-  q.seq_cap_frames = q.seq_cap_planners = 0;
-  q.seqc_cap_frames = q.seqc_cap_planners = 0;
-  (void)hipGetLastError();
-}
-
 // the run-head list and the planners' rows of slot q for a sequence pass of `frames` frames (the slot's stream is idle where
 // something has to grow: enqueue_ticket)
 static int ensure_sequence(fsdp_ctx* c, Work& q, const Work::SeqPass& sq, size_t frames) {
-  // `count` elements behind p where the slot has had room for `cap` < `want` frames (or planners) so far; false: out of memory
-  auto grown = [&](auto*& p, size_t cap, size_t want, size_t count) {
-    if (want <= cap) return true;
-    const hipError_t e = regrow(p, count);
-    if (e != hipSuccess) c->err = std::string(sq.who) + ": " + hipGetErrorString(e);
-    return e == hipSuccess;
-  };
-  const size_t np = (size_t)sq.s.n;
-  if (!grown(q.d_seq, q.seq_cap_frames, frames, (size_t)SEQ_LIST + 2 * frames) || !grown(q.d_seq_init, q.seq_cap_planners, np, SEQ_PREV_DOUBLES * np) ||
-      !grown(q.d_seq_final, q.seq_cap_planners, np, SEQ_PREV_DOUBLES * np))
-    return 2;
-  q.seq_cap_frames = std::max(q.seq_cap_frames, frames);
-  q.seq_cap_planners = std::max(q.seq_cap_planners, np);
-  return 0;
+  const hipError_t e = q.seq_buf.reserve(frames, (size_t)sq.s.n);
+  if (e == hipSuccess) return 0;
+  c->err = std::string(sq.who) + ": " + hipGetErrorString(e);
+  return 2;
 }
 
 // The rows of the caller's arrays a planner slice touches, first to last: n_steps segments `total` frames apart
@@ -1569,8 +1366,8 @@ static int pack_slice(fsdp_ctx* c, Work::Ticket& t, Batch* b) {
   const SeqSlice& s = sq.s;
   const size_t nf = (size_t)s.frames(), rows = (size_t)t.h_seg[s.n_steps].dst;
   const size_t off_bytes = (sizeof(int32_t) * (nf + 1) + 15) & ~(size_t)15, cone_bytes = sizeof(double) * 3 * rows, pose_bytes = sizeof(double) * 4 * nf;
-  HIP_TRY(c, grow_pinned(t.h_in, t.cap_in, off_bytes + cone_bytes + pose_bytes, hipHostMallocMapped, 16384));
-  int32_t* so = (int32_t*)t.h_in;
+  HIP_TRY(c, t.h_in.reserve(off_bytes + cone_bytes + pose_bytes, 16384, Pin::Mapped));
+  int32_t* so = (int32_t*)t.h_in.get();
   double* sc = (double*)(t.h_in + off_bytes);
   double* sp = (double*)(t.h_in + off_bytes + cone_bytes);
   for (int step = 0; step < s.n_steps; step++) {
@@ -1607,8 +1404,7 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     pass.sort.kind = SortVariant::SPEC;
   }
   // a bigger batch than the slot has seen: its buffers are replaced — not under the feet of the passes queued on the stream
-  if (n > q.cap_frames || n > q.in.cap_frames || b.total > q.in.cap_cones || (b.prev && n > q.in.cap_prev) ||
-      (sq && ((size_t)n > q.seq_cap_frames || (size_t)sq->s.n > q.seq_cap_planners)))
+  if ((size_t)n > q.buf.frames() || !q.in.fits((size_t)n, b.total, b.prev != nullptr) || (sq && !q.seq_buf.fits((size_t)n, (size_t)sq->s.n)))
     HIP_TRY(c, hipStreamSynchronize(q.stream));
   if (int rc = ensure_work(c, q, n > 0 ? n : 1)) return rc;
   if (sq)
@@ -1618,7 +1414,7 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
   SliceExtent ext;
   if (sliced) {
     // (the segments again, from the arrays the submit checked: a repeated pass reads them like the batch itself)
-    HIP_TRY(c, grow_pinned(t.h_seg, t.cap_seg, (size_t)sq->s.n_steps + 1, hipHostMallocMapped, 64));
+    HIP_TRY(c, t.h_seg.reserve((size_t)sq->s.n_steps + 1, 64, Pin::Mapped));
     if (seq_slice_segments(sq->s, sq->off, t.h_seg, nullptr) != 0 || (size_t)t.h_seg[sq->s.n_steps].dst != b.total) {
       c->err = std::string(sq->who) + ": cone_offsets changed between submit and collect";
       return 1;
@@ -1634,8 +1430,8 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
   const size_t in_bytes = off_bytes + cone_bytes + pose_bytes + prev_bytes;
   if (!in_pinned && n > 0 && in_bytes <= SMALL_BATCH_BYTES) {
     // (the block's previous user — this ticket entry's previous batch — was collected before the entry was handed out again)
-    HIP_TRY(c, grow_pinned(t.h_in, t.cap_in, in_bytes, hipHostMallocMapped, 16384));
-    int32_t* so = (int32_t*)t.h_in;
+    HIP_TRY(c, t.h_in.reserve(in_bytes, 16384, Pin::Mapped));
+    int32_t* so = (int32_t*)t.h_in.get();
     double* sc = (double*)(t.h_in + off_bytes);
     double* sp = (double*)(t.h_in + off_bytes + cone_bytes);
     double* sv = (double*)(t.h_in + off_bytes + cone_bytes + pose_bytes);
@@ -1662,7 +1458,7 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     a.dst_off = q.in.d_off;
     a.dst_cones = q.in.d_cones;
     a.dst_poses = q.in.d_poses;
-    a.dst_init = q.d_seq_init;
+    a.dst_init = q.seq_buf.d_seq_init;
     if (!a.seg || !a.src_off || !a.src_cones || !a.src_poses) {
       c->err = "internal: a slice's page-locked arrays are not mapped into the device's address space";
       return 2;
@@ -1689,7 +1485,7 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     return rc;
   }
   // (the initial_prev rows of a sequence pass: adjacent also for a slice; seq_slice_in_kernel brought a page-locked slice's along)
-  if (sq && sq->init && !slice_in) HIP_TRY(c, hipMemcpyAsync(q.d_seq_init, sq->init, init_bytes, hipMemcpyHostToDevice, q.stream));
+  if (sq && sq->init && !slice_in) HIP_TRY(c, hipMemcpyAsync(q.seq_buf.d_seq_init, sq->init, init_bytes, hipMemcpyHostToDevice, q.stream));
   t.via_stage = false;
   if (n > 0) {
     // Results always leave the GPU inside the pass's last kernel, written over PCIe into page-locked memory: the caller's own buffer,
@@ -1700,16 +1496,16 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     char* slice_dst = sliced ? (char*)t.user_results + t.rec_bytes() * (size_t)sq->s.lo : nullptr;
     const bool slice_out = sliced && is_pinned(slice_dst, t.rec_bytes() * ext.span_frames) && (!sq->final_prev || is_pinned(sq->final_prev, init_bytes));
     if (!slice_out)  // (a slice that cannot go out in place is staged whatever its array is: NULL is never page-locked)
-      if (int rc = host_target(c, sliced ? nullptr : t.user_results, t.rec_bytes() * (size_t)n, t.h_stage, t.cap_stage, (size_t)n, 64, "result block",
+      if (int rc = host_target(c, sliced ? nullptr : t.user_results, t.rec_bytes() * (size_t)n, t.h_stage, (size_t)n, 64, "result block",
                                &pass.host, &t.via_stage))
         return rc;
     if (sq) {
       // final_prev leaves the GPU inside seq_final_kernel, written into page-locked memory like the records: the caller's rows, or
       // the ticket's block (the slot's d_seq_final serves the slot's next ticket before this one is collected)
       sq->fin_staged = false;
-      sq->final_dev = slice_out ? q.d_seq_final : nullptr;
+      sq->final_dev = slice_out ? q.seq_buf.d_seq_final : nullptr;
       if (sq->final_prev && !slice_out)
-        if (int rc = host_target(c, sq->final_prev, init_bytes, t.h_fin, t.cap_fin, SEQ_PREV_DOUBLES * (size_t)sq->s.n, 64 * SEQ_PREV_DOUBLES,
+        if (int rc = host_target(c, sq->final_prev, init_bytes, t.h_fin, SEQ_PREV_DOUBLES * (size_t)sq->s.n, 64 * SEQ_PREV_DOUBLES,
                                  "final_prev block", &sq->final_dev, &sq->fin_staged))
           return rc;
     }
@@ -1721,9 +1517,9 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
       fsdp_seq_slice_out_args a;
       a.s = sq->s;
       a.rec_bytes = (int)t.rec_bytes();
-      a.src_records = q.d_result;
+      a.src_records = q.buf.d_result;
       a.dst_records = device_view(slice_dst);
-      a.src_final = q.d_seq_final;
+      a.src_final = q.seq_buf.d_seq_final;
       a.dst_final = sq->final_prev ? (double*)device_view(sq->final_prev) : nullptr;
       if (!a.dst_records || (sq->final_prev && !a.dst_final)) {
         c->err = "internal: a slice's result arrays are not mapped into the device's address space";
@@ -1737,7 +1533,7 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
     if (sliced) c->last = fsdp_ctx::LastPass();
     HIP_TRY(c, hipGetLastError());
   }
-  if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
+  if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done.h, hipEventDisableTiming));
   HIP_TRY(c, hipEventRecord(t.done, q.stream));
   return 0;
 }
@@ -1796,7 +1592,7 @@ struct TicketSpec {
 // description and is enqueued.  0: issued as t.id and counted as outstanding (a blocking call collects it and gives the number
 // back: c->next_ticket).  Else no ticket went out, and an error return means the buffers are the caller's again: part of the batch
 // may already be queued on the slot's stream — kernels that read his buffers or write his page-locked results — so it is waited
-// for here (round-3 advisor); a sequence pass that found no room has its slot's buffers replaced again next time (seq_no_room).
+// for here (round-3 advisor).  (A pass that found no room left the buffers that failed to grow empty: the next one grows them again.)
 static int issue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, const TicketSpec& spec) {
   t.batch = spec.batch;
   t.skid = false;
@@ -1810,7 +1606,6 @@ static int issue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, const TicketSpec&
     (void)hipStreamSynchronize(q.stream);
     (void)hipGetLastError();
     t.release();
-    if (spec.sq.on) seq_no_room(q);
     return rc;
   }
   t.id = c->next_ticket++;
@@ -1909,7 +1704,7 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
       const SeqSlice& s = t.sq.s;
       const size_t rec = t.rec_bytes(), seg = rec * (size_t)s.n;
       for (int step = 0; step < s.n_steps; step++)
-        memcpy((char*)t.user_results + rec * (size_t)seq_rec_frame(s, step, 0), (const char*)t.h_stage + seg * (size_t)step, seg);
+        memcpy((char*)t.user_results + rec * (size_t)seq_rec_frame(s, step, 0), (const char*)t.h_stage.get() + seg * (size_t)step, seg);
     } else if (t.via_stage) {
       memcpy(t.user_results, t.h_stage, t.rec_bytes() * (size_t)n);
     }
@@ -1933,7 +1728,6 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
       }
     }
   }
-  if (rc != 0 && t.sq.on) seq_no_room(q);  // (a repeated pass that found no room: see issue_ticket)
   t.release();
   c->outstanding--;
   return rc;
@@ -2155,25 +1949,13 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
   if (int rc = sync_all(c)) return rc;
   c->last = fsdp_ctx::LastPass();
   Work& q = c->slot[0];
-  if (int rc = ensure_work(c, q, n)) {
-    seq_no_room(q);
-    return rc;
-  }
+  if (int rc = ensure_work(c, q, n)) return rc;
   if (cached) {
-    auto grown = [&](auto*& p, size_t cap, size_t want, size_t count) {
-      if (want <= cap) return true;
-      const hipError_t e = regrow(p, count);
-      if (e != hipSuccess) c->err = std::string(who) + ": " + hipGetErrorString(e);
-      return e == hipSuccess;
-    };
-    const size_t nf = (size_t)n, np = (size_t)n_planners;
-    if (!grown(q.d_seqc_rec, q.seqc_cap_frames, nf, nf) || !grown(q.d_seqc_hits, q.seqc_cap_frames, nf, 2 * nf) ||
-        !grown(q.d_seqc_resorted, q.seqc_cap_planners, np, np)) {
-      seq_no_room(q);
+    const hipError_t e = q.seqc_buf.reserve((size_t)n, (size_t)n_planners);
+    if (e != hipSuccess) {
+      c->err = std::string(who) + ": " + hipGetErrorString(e);
       return 2;
     }
-    q.seqc_cap_frames = std::max(q.seqc_cap_frames, nf);
-    q.seqc_cap_planners = std::max(q.seqc_cap_planners, np);
     // the buffer the call writes gets room for every planner's largest frame of the sequence (cache_prepare, step by step)
     for (int s = 0; s < n_steps; s++)
       if (int rc = cache_prepare(c, n_planners, off + (size_t)s * n_planners, who)) return rc;
@@ -2184,8 +1966,8 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
   if (rc != 0) return rc;
   if (cached) {
     std::vector<int32_t> resorted((size_t)n_planners);
-    HIP_TRY(c, copy_sync(c, resorted.data(), q.d_seqc_resorted, sizeof(int32_t) * resorted.size(), hipMemcpyDeviceToHost));
-    if (hits) HIP_TRY(c, copy_sync(c, hits, q.d_seqc_hits, 2 * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, copy_sync(c, resorted.data(), q.seqc_buf.d_seqc_resorted, sizeof(int32_t) * resorted.size(), hipMemcpyDeviceToHost));
+    if (hits) HIP_TRY(c, copy_sync(c, hits, q.seqc_buf.d_seqc_hits, 2 * (size_t)n, hipMemcpyDeviceToHost));
     if (int rc = cache_finish(c)) return rc;  // (the last step's codes; the entries become the previous ones)
     long long sum = 0;
     for (int32_t v : resorted) sum += v;
@@ -2272,18 +2054,12 @@ int fsdp_sort_cache_reset(fsdp_ctx* c, int n_planners) {
   cache_free(c);
   if (n_planners == 0) return 0;
   const size_t n = (size_t)n_planners;
+  HIP_TRY(c, c->cache.reserve(n));
   for (int b = 0; b < 2; b++) {
-    HIP_TRY(c, regrow(c->d_cache_hdr[b], n));
-    HIP_TRY(c, hipMemsetAsync(c->d_cache_hdr[b], 0, sizeof(SortCacheHdr) * n, c->stream));  // (valid = 0: no entry)
-    HIP_TRY(c, regrow(c->d_cache_off[b], n + 1));
-    HIP_TRY(c, hipMemsetAsync(c->d_cache_off[b], 0, sizeof(int32_t) * (n + 1), c->stream));
-    HIP_TRY(c, regrow(c->d_cache_xyt[b], 3));
-    c->cache_rows[b] = 1;
-    c->cache_layout[b].assign(n + 1, 0);
+    HIP_TRY(c, hipMemsetAsync(c->cache.d_hdr[b], 0, sizeof(SortCacheHdr) * n, c->stream));  // (valid = 0: no entry)
+    HIP_TRY(c, hipMemsetAsync(c->cache.d_off[b], 0, sizeof(int32_t) * (n + 1), c->stream));
   }
-  HIP_TRY(c, regrow(c->d_cache_hits, 2 * n));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->cache_region.assign(n, 0);
   c->cache_hits.assign(2 * n, (int8_t)-1);
   c->n_cache = n_planners;
   return 0;
@@ -2350,26 +2126,14 @@ int fsdp_pcie_probe(fsdp_ctx* c, size_t bytes, int iters, double* h2d_GBps, doub
   if (c->outstanding) return busy_error(c, "fsdp_pcie_probe");
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
-  void *h_up = nullptr, *h_dn = nullptr, *d_up = nullptr, *d_dn = nullptr;
-  hipStream_t s2 = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-  auto cleanup = [&]() {
-    if (h_up) (void)hipHostFree(h_up);
-    if (h_dn) (void)hipHostFree(h_dn);
-    (void)hipFree(d_up);
-    (void)hipFree(d_dn);
-    if (s2) (void)hipStreamDestroy(s2);
-    for (hipEvent_t e : {e0, e1, e2})
-      if (e) (void)hipEventDestroy(e);
-  };
-  hipError_t e = hipHostMalloc(&h_up, bytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc(&h_dn, bytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(&d_up, bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_dn, bytes);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
-  if (e == hipSuccess) e = hipEventCreate(&e2);
+  PinnedBuf<char> h_up, h_dn;
+  DeviceBuf<char> d_up, d_dn;
+  Stream s2;
+  hipError_t e = h_up.reserve(bytes);
+  if (e == hipSuccess) e = h_dn.reserve(bytes);
+  if (e == hipSuccess) e = d_up.reserve(bytes);
+  if (e == hipSuccess) e = d_dn.reserve(bytes);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&s2.h, hipStreamNonBlocking);
   if (e == hipSuccess) {
     memset(h_up, 1, bytes);
     e = hipMemsetAsync(d_dn, 2, bytes, c->stream);
@@ -2393,7 +2157,6 @@ int fsdp_pcie_probe(fsdp_ctx* c, size_t bytes, int iters, double* h2d_GBps, doub
   if (e == hipSuccess) e = run(true, false, h2d_GBps);
   if (e == hipSuccess) e = run(false, true, d2h_GBps);
   if (e == hipSuccess) e = run(true, true, both_each_GBps);
-  cleanup();
   HIP_TRY(c, e);
   return 0;
 }
@@ -2404,17 +2167,11 @@ constexpr int TIMING_EPP = MAX_STAGES + 1;
 static int reserve_timing(fsdp_ctx* c, int iters) {
   const size_t need = (size_t)TIMING_EPP * (size_t)iters + 2;
   while (c->tev.size() < need) {
-    hipEvent_t e;
-    HIP_TRY(c, hipEventCreate(&e));
-    c->tev.push_back(e);
+    Event e;
+    HIP_TRY(c, hipEventCreate(&e.h));
+    c->tev.push_back(std::move(e));
   }
-  if (iters > c->kclock_cap) {
-    (void)hipFree(c->d_kclock);
-    c->d_kclock = nullptr;
-    c->kclock_cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_kclock, sizeof(unsigned long long) * 2 * (size_t)iters));
-    c->kclock_cap = iters;
-  }
+  HIP_TRY(c, c->d_kclock.reserve(2 * (size_t)iters));
   return 0;
 }
 
@@ -2493,8 +2250,9 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
   if (rc) return rc;
   hipEvent_t ev_begin = c->tev[need - 2], ev_end = c->tev[need - 1];
   // the refit kernel's own clock readings: atomicMin over "all ones", atomicMax over zero (set before the region begins)
-  HIP_TRY(c, hipMemsetAsync(c->d_kclock, 0xff, sizeof(unsigned long long) * (size_t)c->kclock_cap, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_kclock + c->kclock_cap, 0, sizeof(unsigned long long) * (size_t)c->kclock_cap, c->stream));
+  const size_t kcap = c->d_kclock.capacity() / 2;  // (passes the block has room for: first readings, then last readings)
+  HIP_TRY(c, hipMemsetAsync(c->d_kclock, 0xff, sizeof(unsigned long long) * kcap, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_kclock + kcap, 0, sizeof(unsigned long long) * kcap, c->stream));
   HIP_TRY(c, hipEventRecord(ev_begin, c->stream));
   int last_of_slot[FSDP_MAX_OVERLAP];
   bool started[FSDP_MAX_OVERLAP];
@@ -2515,7 +2273,7 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
     // (opt-in, fsdp_time_detail bit 1: the readings are two atomics per workgroup on one address — the launches of a region
     // timed without them are the production launches)
     t.clock_first = c->time_kernel_clock ? c->d_kclock + it : nullptr;
-    t.clock_last = c->time_kernel_clock ? c->d_kclock + c->kclock_cap + it : nullptr;
+    t.clock_last = c->time_kernel_clock ? c->d_kclock + kcap + it : nullptr;
     Pass timed;
     timed.events = &t;
     if ((rc = launch_pass(c, q, c->res, timed))) return rc;
@@ -2551,10 +2309,11 @@ int fsdp_time_kernel_clock(fsdp_ctx* c, double* ms_sum, int* launches) {
   int khz = 0;
   HIP_TRY(c, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device));
   if (khz <= 0) return 0;
-  std::vector<unsigned long long> h(2 * (size_t)c->kclock_cap);
+  const size_t kcap = c->d_kclock.capacity() / 2;
+  std::vector<unsigned long long> h(2 * kcap);
   HIP_TRY(c, hipMemcpy(h.data(), c->d_kclock, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-  for (int it = 0; it < c->timed_iters && it < c->kclock_cap; it++) {
-    const unsigned long long a = h[(size_t)it], b = h[(size_t)c->kclock_cap + (size_t)it];
+  for (int it = 0; it < c->timed_iters && (size_t)it < kcap; it++) {
+    const unsigned long long a = h[(size_t)it], b = h[kcap + (size_t)it];
     if (a == ~0ull || b == 0ull || b < a) continue;  // (a pass whose path stage was not the three-kernel form)
     *ms_sum += (double)(b - a) / (double)khz;
     (*launches)++;
@@ -2589,18 +2348,9 @@ struct RankCall {
   int32_t* configs = nullptr;
   double* costs = nullptr;
   double* terms = nullptr;
-  int32_t* d_counts = nullptr;
-  int32_t* d_configs = nullptr;
-  double* d_costs = nullptr;
-  double* d_terms = nullptr;
-  SortRankScratchBig* d_scratch = nullptr;
-  ~RankCall() {
-    (void)hipFree(d_counts);
-    (void)hipFree(d_configs);
-    (void)hipFree(d_costs);
-    (void)hipFree(d_terms);
-    (void)hipFree(d_scratch);
-  }
+  DeviceBuf<int32_t> d_counts, d_configs;
+  DeviceBuf<double> d_costs, d_terms;
+  DeviceBuf<SortRankScratchBig> d_scratch;
 };
 
 // indices of a frame planned without its UNKNOWN cones back into the caller's cone list (what assemble_kernel does for a full
@@ -2642,27 +2392,26 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
   Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
   if (int rc = upload_inputs(c, q.in, q.stream, b)) return rc;
-  Inputs fin;
+  Inputs in = q.in.view();
   const bool filtered = !c->params.use_unknown_cones;
   if (filtered)
-    if (int rc = launch_filter(c, q, q.in, &fin)) return rc;
-  const Inputs& in = filtered ? fin : q.in;
+    if (int rc = launch_filter(c, q, q.in, &in)) return rc;
   const size_t rows = rk ? (size_t)n_frames * 2 * (size_t)rk->top_k : 0;
   SortRankView v;
   SortVariant var;
   if (rk) {
-    HIP_TRY(c, hipMalloc(&rk->d_counts, sizeof(int32_t) * 2 * (size_t)n_frames));
-    HIP_TRY(c, hipMalloc(&rk->d_configs, sizeof(int32_t) * rows * MAX_LEN));
-    HIP_TRY(c, hipMalloc(&rk->d_costs, sizeof(double) * rows));
-    if (rk->terms) HIP_TRY(c, hipMalloc(&rk->d_terms, sizeof(double) * rows * COST_TERMS));
-    HIP_TRY(c, hipMalloc(&rk->d_scratch, sizeof(SortRankScratchBig) * SORT_BIG_BLOCKS));
+    HIP_TRY(c, rk->d_counts.reserve(2 * (size_t)n_frames));
+    HIP_TRY(c, rk->d_configs.reserve(rows * MAX_LEN));
+    HIP_TRY(c, rk->d_costs.reserve(rows));
+    if (rk->terms) HIP_TRY(c, rk->d_terms.reserve(rows * COST_TERMS));
+    HIP_TRY(c, rk->d_scratch.reserve(SORT_BIG_BLOCKS));
     // unused rows: -1 indices, NaN costs and terms; a side without a result writes nothing
     HIP_TRY(c, hipMemsetAsync(rk->d_counts, 0, sizeof(int32_t) * 2 * (size_t)n_frames, q.stream));
     HIP_TRY(c, hipMemsetAsync(rk->d_configs, 0xff, sizeof(int32_t) * rows * MAX_LEN, q.stream));
     HIP_TRY(c, hipMemsetAsync(rk->d_costs, 0xff, sizeof(double) * rows, q.stream));
     if (rk->terms) HIP_TRY(c, hipMemsetAsync(rk->d_terms, 0xff, sizeof(double) * rows * COST_TERMS, q.stream));
     if (c->poison) {
-      HIP_TRY(c, hipMemsetAsync(q.d_sort, 0xff, sizeof(SortOut) * (size_t)n_frames, q.stream));
+      HIP_TRY(c, hipMemsetAsync(q.buf.d_sort, 0xff, sizeof(SortOut) * (size_t)n_frames, q.stream));
       HIP_TRY(c, hipMemsetAsync(rk->d_scratch, 0xff, sizeof(SortRankScratchBig) * SORT_BIG_BLOCKS, q.stream));
     }
     v.top_k = rk->top_k;
@@ -2682,9 +2431,9 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
   names += ',';
   if (int rc = launch_sort_big(c, q, in, names, var)) return rc;
   if (rk) c->stage_names = names;  // (fsdp_sort_batch leaves the names of the most recent pass in place)
-  HIP_TRY(c, hipMemsetAsync(q.d_big, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
-  HIP_TRY(c, grow_pinned(c->h_sort, c->cap_sort, (size_t)n_frames, hipHostMallocDefault, 64));
-  HIP_TRY(c, hipMemcpyAsync(c->h_sort, q.d_sort, sizeof(SortOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
+  HIP_TRY(c, hipMemsetAsync(q.buf.d_big, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
+  HIP_TRY(c, c->h_sort.reserve((size_t)n_frames, 64));
+  HIP_TRY(c, hipMemcpyAsync(c->h_sort, q.buf.d_sort, sizeof(SortOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
   std::vector<int32_t> map, moff;
   if (rk) {
     HIP_TRY(c, hipMemcpyAsync(rk->counts, rk->d_counts, sizeof(int32_t) * 2 * (size_t)n_frames, hipMemcpyDeviceToHost, q.stream));
@@ -2695,8 +2444,8 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
   if (filtered) {  // indices back into the caller's index space (what assemble_kernel does for a full pass)
     map.resize(b.total ? b.total : 1);
     moff.resize((size_t)n_frames + 1);
-    HIP_TRY(c, hipMemcpyAsync(map.data(), q.f_map, sizeof(int32_t) * b.total, hipMemcpyDeviceToHost, q.stream));
-    HIP_TRY(c, hipMemcpyAsync(moff.data(), q.f_off, sizeof(int32_t) * ((size_t)n_frames + 1), hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(map.data(), q.filt.f_map, sizeof(int32_t) * b.total, hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(moff.data(), q.filt.f_off, sizeof(int32_t) * ((size_t)n_frames + 1), hipMemcpyDeviceToHost, q.stream));
   }
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   if (cached)
@@ -2773,10 +2522,10 @@ int fsdp_match_batch(fsdp_ctx* c, int n_frames, const double* sorted_left, const
   Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
   if (int rc = upload_inputs(c, q.in, q.stream, Batch{n_frames, off.data(), cones.data(), poses, nullptr, cones.size() / 3, 2 * MAX_LEN})) return rc;
-  HIP_TRY(c, hipMemcpyAsync(q.d_sort, so.data(), sizeof(SortOut) * n_frames, hipMemcpyHostToDevice, q.stream));
-  launch_match(c, q, q.in);
-  HIP_TRY(c, grow_pinned(c->h_match, c->cap_match, (size_t)n_frames, hipHostMallocDefault, 64));
-  HIP_TRY(c, hipMemcpyAsync(c->h_match, q.d_match, sizeof(MatchOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
+  HIP_TRY(c, hipMemcpyAsync(q.buf.d_sort, so.data(), sizeof(SortOut) * n_frames, hipMemcpyHostToDevice, q.stream));
+  launch_match(c, q, q.in.view());
+  HIP_TRY(c, c->h_match.reserve((size_t)n_frames, 64));
+  HIP_TRY(c, hipMemcpyAsync(c->h_match, q.buf.d_match, sizeof(MatchOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   for (int i = 0; i < n_frames; i++) {
     memset(&results[i], 0, sizeof(fsdp_frame_result));
@@ -2796,21 +2545,19 @@ static int path_batch_impl(fsdp_ctx* c, int n_frames, const double* poses, const
   // the centre points leave the kernels through a buffer the device copy of the parameters points to for this one call
   struct CentersScope {
     fsdp_ctx* c;
-    double* d_xy = nullptr;
-    int32_t* d_n = nullptr;
+    DeviceBuf<double> d_xy;
+    DeviceBuf<int32_t> d_n;
     ~CentersScope() {
       if (!d_xy && !d_n) return;
       c->params.centers = nullptr;
       c->params.n_centers = nullptr;
       c->params.centers_cap = 0;
       (void)hipMemcpy(c->d_params, &c->params, sizeof(Params), hipMemcpyHostToDevice);
-      (void)hipFree(d_xy);
-      (void)hipFree(d_n);
     }
   } cs{c};
   if (centers) {
-    HIP_TRY(c, hipMalloc(&cs.d_xy, sizeof(double) * 2 * (size_t)centers_cap * (size_t)n_frames));
-    HIP_TRY(c, hipMalloc(&cs.d_n, sizeof(int32_t) * (size_t)n_frames));
+    HIP_TRY(c, cs.d_xy.reserve(2 * (size_t)centers_cap * (size_t)n_frames));
+    HIP_TRY(c, cs.d_n.reserve((size_t)n_frames));
     HIP_TRY(c, hipMemset(cs.d_n, 0, sizeof(int32_t) * (size_t)n_frames));
     c->params.centers = cs.d_xy;
     c->params.n_centers = cs.d_n;
@@ -2819,7 +2566,7 @@ static int path_batch_impl(fsdp_ctx* c, int n_frames, const double* poses, const
   }
   Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
-  if (int rc = ensure_inputs(c, q.in, n_frames, 1, prev_paths != nullptr)) return rc;
+  HIP_TRY(c, q.in.reserve((size_t)n_frames, 1, prev_paths != nullptr));
   std::vector<MatchOut> mo(n_frames);
   for (int f = 0; f < n_frames; f++) {
     memset(&mo[f], 0, sizeof(MatchOut));
@@ -2838,17 +2585,17 @@ static int path_batch_impl(fsdp_ctx* c, int n_frames, const double* poses, const
   q.in.n_frames = n_frames;
   q.in.max_cones = 0;
   q.in.use_prev = prev_paths != nullptr;
-  HIP_TRY(c, hipMemcpyAsync(q.d_match, mo.data(), sizeof(MatchOut) * n_frames, hipMemcpyHostToDevice, q.stream));
+  HIP_TRY(c, hipMemcpyAsync(q.buf.d_match, mo.data(), sizeof(MatchOut) * n_frames, hipMemcpyHostToDevice, q.stream));
   HIP_TRY(c, hipMemcpyAsync(q.in.d_poses, poses, sizeof(double) * 4 * (size_t)n_frames, hipMemcpyHostToDevice, q.stream));
   if (prev_paths)
     HIP_TRY(c, hipMemcpyAsync(q.in.d_prev, prev_paths, sizeof(double) * PATH_POINTS * 4 * (size_t)n_frames, hipMemcpyHostToDevice, q.stream));
   std::string names;
-  launch_path(c, q, q.in, nullptr, names, n_frames);
-  launch_path_retry(c, q, q.in);
-  HIP_TRY(c, hipMemsetAsync(q.d_retry, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
+  launch_path(c, q, q.in.view(), nullptr, names, n_frames);
+  launch_path_retry(c, q, q.in.view());
+  HIP_TRY(c, hipMemsetAsync(q.buf.d_retry, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
   c->stage_names = names + "path_retry_kernel";
-  HIP_TRY(c, grow_pinned(c->h_path, c->cap_path, (size_t)n_frames, hipHostMallocDefault, 64));
-  HIP_TRY(c, hipMemcpyAsync(c->h_path, q.d_path, sizeof(PathOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
+  HIP_TRY(c, c->h_path.reserve((size_t)n_frames, 64));
+  HIP_TRY(c, hipMemcpyAsync(c->h_path, q.buf.d_path, sizeof(PathOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   for (int i = 0; i < n_frames; i++) {
     results[i].status = 0;
@@ -2884,24 +2631,24 @@ int fsdp_profile_select(fsdp_ctx* c, int sort_kernel_instead_of_path) {
 // profiling build only (tools/section_profile.py): per-frame per-section cycle sums of the path kernel, resident batch
 int fsdp_profile_path(fsdp_ctx* c, long long* out32_per_frame) {
   if (!c || !c->resident || c->res.n_frames == 0) return 1;
-  long long* d = nullptr;
+  DeviceBuf<long long> buf;
   size_t bytes = sizeof(long long) * 32 * (size_t)c->res.n_frames;
-  HIP_TRY(c, hipMalloc(&d, bytes));
+  HIP_TRY(c, buf.reserve(32 * (size_t)c->res.n_frames));
+  long long* d = buf;
   HIP_TRY(c, hipMemsetAsync(d, 0, bytes, c->stream));
   HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(fsdp::g_prof), &d, sizeof(d)));
   Work& q = c->slot[0];
   std::string names;
   if (c->profile_sort)
-    launch_sort(c, q, c->res, StageIn(), names);
+    launch_sort(c, q, c->res.view(), StageIn(), names, SortVariant());
   else
-    launch_path(c, q, c->res, nullptr, names, frames_in_flight(c, c->res.n_frames, false));
-  HIP_TRY(c, hipMemsetAsync(q.d_big, 0, sizeof(int), q.stream));
-  HIP_TRY(c, hipMemsetAsync(q.d_retry, 0, sizeof(int), q.stream));
+    launch_path(c, q, c->res.view(), nullptr, names, frames_in_flight(c, c->res.n_frames, false));
+  HIP_TRY(c, hipMemsetAsync(q.buf.d_big, 0, sizeof(int), q.stream));
+  HIP_TRY(c, hipMemsetAsync(q.buf.d_retry, 0, sizeof(int), q.stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, copy_sync(c, out32_per_frame, d, bytes, hipMemcpyDeviceToHost));
   long long* z = nullptr;
   HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(fsdp::g_prof), &z, sizeof(z)));
-  (void)hipFree(d);
   return 0;
 }
 #endif
@@ -2917,27 +2664,22 @@ int fsdp_skidpad_set_tables(fsdp_ctx* c, const double* table_xy, int n_table, co
     half.push_back(table_xy[2 * i]);
     half.push_back(table_xy[2 * i + 1]);
   }
-  if (c->d_table) (void)hipFree(c->d_table);
-  if (c->d_noise) (void)hipFree(c->d_noise);
-  c->d_table = c->d_noise = nullptr;
+  c->d_table.reset();
+  c->d_noise.reset();
   c->have_tables = false;
-  HIP_TRY(c, hipMalloc(&c->d_table, sizeof(double) * half.size()));
-  HIP_TRY(c, hipMalloc(&c->d_noise, sizeof(double) * (size_t)n_noise));
+  HIP_TRY(c, c->d_table.reserve(half.size()));
+  HIP_TRY(c, c->d_noise.reserve((size_t)n_noise));
   HIP_TRY(c, copy_sync(c, c->d_table, half.data(), sizeof(double) * half.size(), hipMemcpyHostToDevice));
   HIP_TRY(c, copy_sync(c, c->d_noise, noise, sizeof(double) * (size_t)n_noise, hipMemcpyHostToDevice));
   // the two reference centres and the table spacing are derived from the table on the device (skid_centers_kernel)
-  double *d_full = nullptr, *d_scratch = nullptr, *d_out = nullptr;
-  HIP_TRY(c, hipMalloc(&d_full, sizeof(double) * 2 * (size_t)n_table));
-  HIP_TRY(c, hipMalloc(&d_scratch, sizeof(double) * 3 * (size_t)n_table));
-  HIP_TRY(c, hipMalloc(&d_out, sizeof(double) * 5));
+  DeviceBuf<double> d_full, d_scratch, d_out;
+  HIP_TRY(c, d_full.reserve(2 * (size_t)n_table));
+  HIP_TRY(c, d_scratch.reserve(3 * (size_t)n_table));
+  HIP_TRY(c, d_out.reserve(5));
   HIP_TRY(c, hipMemcpyAsync(d_full, table_xy, sizeof(double) * 2 * (size_t)n_table, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(skid_centers_kernel, dim3(1), dim3(WAVE), 0, c->stream, d_full, n_table, d_scratch, d_out);
-  hipError_t e = hipMemcpyAsync(c->skid_consts, d_out, sizeof(double) * 5, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_full);
-  (void)hipFree(d_scratch);
-  (void)hipFree(d_out);
-  HIP_TRY(c, e);
+  HIP_TRY(c, hipMemcpyAsync(c->skid_consts, d_out, sizeof(double) * 5, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->tables.path = c->d_table;
   c->tables.n_path = (int)(half.size() / 2);
   c->tables.noise = c->d_noise;
@@ -2964,12 +2706,12 @@ int fsdp_skidpad_reset(fsdp_ctx* c, int n_instances) {
   if (c->outstanding) return busy_error(c, "fsdp_skidpad_reset");
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
-  if (n_instances != c->n_instances) {
-    HIP_TRY(c, regrow(c->d_skid, (size_t)n_instances));
-    HIP_TRY(c, regrow(c->d_skid_backup, (size_t)n_instances));
-    HIP_TRY(c, regrow(c->d_skid_sync, (size_t)n_instances + 1));
-    c->n_instances = n_instances;
-  }
+  // (n_instances says what the planners' state holds room for: 0 until all three blocks stand)
+  c->n_instances = 0;
+  HIP_TRY(c, c->d_skid.reserve((size_t)n_instances));
+  HIP_TRY(c, c->d_skid_backup.reserve((size_t)n_instances));
+  HIP_TRY(c, c->d_skid_sync.reserve((size_t)n_instances + 1));
+  c->n_instances = n_instances;
   // fresh planners: nothing latched, previous path = the constant initial path
   std::vector<SkidState> init(n_instances);
   double def[PATH_POINTS][4];
@@ -3008,7 +2750,7 @@ static SkidGroup skid_group_of(fsdp_ctx* c, const int* slots, int n_steps, int s
   memset(&g, 0, sizeof(g));
   for (int k = 0; k < n_steps; k++) {
     Work& q = c->slot[slots[k]];
-    g.step[k] = SkidStep{q.in.d_poses, q.skid_attempted ? q.d_skid_status : nullptr, q.d_arena, q.d_path, q.d_skid_info};
+    g.step[k] = SkidStep{q.in.d_poses, q.skid_attempted ? q.buf.d_skid_status : nullptr, q.buf.d_arena, q.buf.d_path, q.buf.d_skid_info};
   }
   g.n_steps = n_steps;
   g.step0 = step0;
@@ -3029,22 +2771,15 @@ static void launch_skid_path(fsdp_ctx* c, const int* slots, int n_steps, int ste
 static int launch_skid_packed(fsdp_ctx* c, const int* slots, int n_steps, int step0) {
   const int n = c->n_instances;
   const int frames = n * n_steps;
-  if ((size_t)frames > c->g_cap) {
+  if ((size_t)frames > c->group.frames()) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    // (room for the groups this context forms: 16 384 frames with 1024 planners ~ 1.4 GB, most of it fit workspace)
-    const size_t m = std::max((size_t)frames, (size_t)n * (size_t)skid_group_size(c));
-    HIP_TRY(c, regrow(c->d_g_arena, (size_t)ARENA_DOUBLES * m));
-    HIP_TRY(c, regrow(c->d_g_mid, m));
-    HIP_TRY(c, regrow(c->d_g_out, m));
-    HIP_TRY(c, regrow(c->d_g_retry, m + 1));
-    HIP_TRY(c, regrow(c->d_g_sel, m));
-    c->g_cap = m;
+    HIP_TRY(c, c->group.reserve((size_t)frames, (size_t)n, (size_t)skid_group_size(c)));
   }
   const SkidGroup g = skid_group_of(c, slots, n_steps, step0);
   hipStream_t xs = c->stream;
-  HIP_TRY(c, hipMemsetAsync(c->d_g_retry, 0, sizeof(int), xs));  // (the packed kernels' list of frames they hand on; the commit kernel goes by the frames' records)
+  HIP_TRY(c, hipMemsetAsync(c->group.d_g_retry, 0, sizeof(int), xs));  // (the packed kernels' list of frames they hand on; the commit kernel goes by the frames' records)
   skid_group_mark(c);
-  hipLaunchKernelGGL(skid_select_kernel, dim3((unsigned)n), dim3(WAVE), 0, xs, n, g, c->d_skid, c->tables, c->d_g_sel);
+  hipLaunchKernelGGL(skid_select_kernel, dim3((unsigned)n), dim3(WAVE), 0, xs, n, g, c->d_skid, c->tables, c->group.d_g_sel);
   if (frames >= PACK_FRAMES) {
     if (c->fit_g == 4)
       launch_skid_packed_kernels<8, 4>(c, frames);
@@ -3053,8 +2788,8 @@ static int launch_skid_packed(fsdp_ctx* c, const int* slots, int n_steps, int st
   } else {
     launch_skid_packed_kernels<16, 16>(c, frames);
   }
-  hipLaunchKernelGGL(skid_commit_kernel, dim3((unsigned)n), dim3(WAVE), 0, xs, n, g, c->d_skid, c->tables, c->d_chord, c->d_g_sel, c->d_g_mid, c->d_g_out,
-                     c->d_g_arena, c->d_skid_sync);
+  hipLaunchKernelGGL(skid_commit_kernel, dim3((unsigned)n), dim3(WAVE), 0, xs, n, g, c->d_skid, c->tables, c->d_chord, c->group.d_g_sel, c->group.d_g_mid, c->group.d_g_out,
+                     c->group.d_g_arena, c->d_skid_sync);
   skid_group_mark(c);
   if (c->skid_time_groups) c->skid_group_frames.push_back(frames);
   return 0;
@@ -3089,11 +2824,11 @@ static int flush_skid(fsdp_ctx* c) {
       CopySegs segs;
       segs.n = 0;
       segs.rebase = 0;
-      if (direct) segs.seg[segs.n++] = CopySeg{q.d_path, direct, sizeof(PathOut) * (unsigned long long)n};
-      if (t.user_info) segs.seg[segs.n++] = CopySeg{q.d_skid_info, device_view(t.h_info), sizeof(SkidInfo) * (unsigned long long)n};
+      if (direct) segs.seg[segs.n++] = CopySeg{q.buf.d_path, direct, sizeof(PathOut) * (unsigned long long)n};
+      if (t.user_info) segs.seg[segs.n++] = CopySeg{q.buf.d_skid_info, device_view(t.h_info), sizeof(SkidInfo) * (unsigned long long)n};
       if (segs.n) hipLaunchKernelGGL(stage_in_kernel, dim3(128), dim3(256), 0, xs, segs);
       HIP_TRY(c, hipGetLastError());
-      if (t.via_stage) HIP_TRY(c, hipMemcpyAsync(t.h_stage, q.d_path, sizeof(PathOut) * (size_t)n, hipMemcpyDeviceToHost, xs));
+      if (t.via_stage) HIP_TRY(c, hipMemcpyAsync(t.h_stage, q.buf.d_path, sizeof(PathOut) * (size_t)n, hipMemcpyDeviceToHost, xs));
       HIP_TRY(c, hipEventRecord(t.done, xs));
       continue;
     }
@@ -3104,7 +2839,7 @@ static int flush_skid(fsdp_ctx* c) {
       launch_assemble(c, q, t.user_results ? n : 0, pass, true);
     }
     HIP_TRY(c, hipGetLastError());
-    if (t.via_stage) HIP_TRY(c, hipMemcpyAsync(t.h_stage, q.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, xs));
+    if (t.via_stage) HIP_TRY(c, hipMemcpyAsync(t.h_stage, q.buf.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, xs));
     HIP_TRY(c, hipEventRecord(t.done, xs));
   }
   return 0;
@@ -3152,13 +2887,13 @@ static int skidpad_submit_impl(fsdp_ctx* c, int n_instances, const int32_t* off,
     return rc;
   }
   q.skid_attempted = attempt;
-  if (info) HIP_TRY(c, grow_pinned(t.h_info, t.cap_info, (size_t)n_instances, hipHostMallocDefault));
+  if (info) HIP_TRY(c, t.h_info.reserve((size_t)n_instances));
   const bool direct = results && is_pinned(results, (compact ? sizeof(PathOut) : sizeof(fsdp_frame_result)) * (size_t)n_instances);
-  if (results && !direct) HIP_TRY(c, grow_pinned(t.h_stage, t.cap_stage, (size_t)n_instances, hipHostMallocDefault));
-  if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
+  if (results && !direct) HIP_TRY(c, t.h_stage.reserve((size_t)n_instances));
+  if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done.h, hipEventDisableTiming));
   if (attempt)
     hipLaunchKernelGGL(skid_reloc_kernel, dim3((unsigned)n_instances), dim3(WAVE), 0, c->stream, n_instances, q.in.d_off, q.in.d_cones, q.in.d_poses,
-                       c->d_skid, c->tables, q.d_arena, q.d_skid_status, c->skid_step_no);
+                       c->d_skid, c->tables, q.buf.d_arena, q.buf.d_skid_status, c->skid_step_no);
   HIP_TRY(c, hipGetLastError());
   c->skid_step_no++;
   q.pass_in = &q.in;
@@ -3204,7 +2939,6 @@ int fsdp_skidpad_step(fsdp_ctx* c, int n_instances, const int32_t* off, const do
 // Timing of the packed path-stage kernels of the groups of steps a replay forms (fsdp_skidpad_submit): enable, replay, read.
 int fsdp_skidpad_time_groups(fsdp_ctx* c, int enable) {
   if (!c) return 1;
-  for (hipEvent_t e : c->skid_group_ev) (void)hipEventDestroy(e);
   c->skid_group_ev.clear();
   c->skid_group_frames.clear();
   c->skid_group_names.clear();
@@ -3283,9 +3017,9 @@ extern "C" int fsdp_debug_refit(fsdp_ctx* c, int32_t* n_knots, double* knots34, 
   std::vector<FitRec> recs((size_t)n);
   std::vector<PathMid> mids((size_t)n);
   const size_t fit_off = (size_t)ARENA_FIT * sizeof(double);  // frame_arena(): A.fit
-  HIP_TRY(c, hipMemcpy2DAsync(recs.data(), sizeof(FitRec), (const char*)q.d_arena + fit_off, sizeof(double) * ARENA_DOUBLES,
+  HIP_TRY(c, hipMemcpy2DAsync(recs.data(), sizeof(FitRec), (const char*)q.buf.d_arena.get() + fit_off, sizeof(double) * ARENA_DOUBLES,
                               sizeof(FitRec), (size_t)n, hipMemcpyDeviceToHost, q.stream));
-  HIP_TRY(c, hipMemcpyAsync(mids.data(), q.d_mid, sizeof(PathMid) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
+  HIP_TRY(c, hipMemcpyAsync(mids.data(), q.buf.d_mid, sizeof(PathMid) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   for (int i = 0; i < n; i++) {
     // only frames that went prep -> fit -> finish hold a record (the others took the exact route or ended earlier)
@@ -3304,14 +3038,14 @@ extern "C" int fsdp_debug_arena(fsdp_ctx* c, int frame, int offset, int count, d
   if (int rc = sync_all(c)) return rc;
   Work* q = debug_slot(c, "fsdp_debug_arena");
   if (!q || frame >= c->last.n) return 1;
-  HIP_TRY(c, copy_sync(c, out, q->d_arena + (size_t)frame * ARENA_DOUBLES + offset, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
+  HIP_TRY(c, copy_sync(c, out, q->buf.d_arena + (size_t)frame * ARENA_DOUBLES + offset, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
   return 0;
 }
 
 // ---- device arithmetic self-test ------------------------------------------------------------------------------------------
 // One routine behind the five entry points: n elements, inputs of `per` doubles per element each, an output of out_per doubles
 // per element.  Device blocks for all of them, inputs in, launch(device inputs, device output) on the context's stream, output
-// back, wait — and every block freed again on every way out.
+// back, wait.
 struct SelftestIn {
   const double* host;
   int per;
@@ -3320,12 +3054,14 @@ static int run_selftest(fsdp_ctx* c, int n, std::initializer_list<SelftestIn> in
                         const std::function<void(double* const*, double*)>& launch) {
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = sizeof(double) * (size_t)n;
-  std::vector<double*> d(ins.size() + 1, nullptr);  // the inputs in order, then the output
+  std::vector<DeviceBuf<double>> own(ins.size() + 1);  // the inputs in order, then the output
+  std::vector<double*> d(own.size(), nullptr);
   hipError_t e = hipSuccess;
   size_t k = 0;
   for (const SelftestIn& in : ins)
-    if (e == hipSuccess) e = hipMalloc(&d[k++], in.per * bytes);
-  if (e == hipSuccess) e = hipMalloc(&d.back(), out_per * bytes);
+    if (e == hipSuccess) e = own[k++].reserve((size_t)in.per * (size_t)n);
+  if (e == hipSuccess) e = own.back().reserve((size_t)out_per * (size_t)n);
+  for (k = 0; k < own.size(); k++) d[k] = own[k];
   k = 0;
   for (const SelftestIn& in : ins) {
     if (e == hipSuccess) e = hipMemcpyAsync(d[k], in.host, in.per * bytes, hipMemcpyHostToDevice, c->stream);
@@ -3336,7 +3072,6 @@ static int run_selftest(fsdp_ctx* c, int n, std::initializer_list<SelftestIn> in
     e = hipMemcpyAsync(out, d.back(), out_per * bytes, hipMemcpyDeviceToHost, c->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  for (double* p : d) (void)hipFree(p);
   HIP_TRY(c, e);
   return 0;
 }
@@ -3493,12 +3228,7 @@ int fsdp_comm_rank(fsdp_ctx* c) {
 }
 
 static int comm_staging(fsdp_ctx* c, size_t bytes) {
-  if (bytes <= c->comm.cap) return 0;
-  if (c->comm.d_buf) (void)hipFree(c->comm.d_buf);
-  c->comm.d_buf = nullptr;
-  c->comm.cap = 0;
-  HIP_TRY(c, hipMalloc(&c->comm.d_buf, bytes));
-  c->comm.cap = bytes;
+  HIP_TRY(c, c->comm.d_buf.reserve(bytes));
   return 0;
 }
 
@@ -3509,7 +3239,7 @@ int fsdp_comm_broadcast(fsdp_ctx* c, void* host_buf, size_t bytes, int root) {
   int rc = comm_staging(c, bytes);
   if (rc) return rc;
   if (c->comm.rank == root) HIP_TRY(c, hipMemcpyAsync(c->comm.d_buf, host_buf, bytes, hipMemcpyHostToDevice, c->stream));
-  NCCL_TRY(c, fsdp_comm::api().Broadcast(c->comm.d_buf, c->comm.d_buf, bytes, ncclUint8, root, c->comm.comm, c->stream));
+  NCCL_TRY(c, fsdp_comm::api().Broadcast(c->comm.d_buf.get(), c->comm.d_buf.get(), bytes, ncclUint8, root, c->comm.comm, c->stream));
   if (c->comm.rank != root) HIP_TRY(c, hipMemcpyAsync(host_buf, c->comm.d_buf, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -3524,7 +3254,7 @@ int fsdp_comm_allreduce(fsdp_ctx* c, double* values, int n, int op) {
   if (rc) return rc;
   const ncclRedOp_t ops[3] = {ncclSum, ncclMax, ncclMin};
   HIP_TRY(c, hipMemcpyAsync(c->comm.d_buf, values, bytes, hipMemcpyHostToDevice, c->stream));
-  NCCL_TRY(c, fsdp_comm::api().AllReduce(c->comm.d_buf, c->comm.d_buf, (size_t)n, ncclFloat64, ops[op], c->comm.comm, c->stream));
+  NCCL_TRY(c, fsdp_comm::api().AllReduce(c->comm.d_buf.get(), c->comm.d_buf.get(), (size_t)n, ncclFloat64, ops[op], c->comm.comm, c->stream));
   HIP_TRY(c, hipMemcpyAsync(values, c->comm.d_buf, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -3552,9 +3282,7 @@ int fsdp_comm_destroy(fsdp_ctx* c) {
     (void)fsdp_comm::api().CommDestroy(c->comm.comm);
     c->comm.comm = nullptr;
   }
-  if (c->comm.d_buf) (void)hipFree(c->comm.d_buf);
-  c->comm.d_buf = nullptr;
-  c->comm.cap = 0;
+  c->comm.d_buf.reset();
   c->comm.rank = 0;
   c->comm.world = 1;
   return 0;
