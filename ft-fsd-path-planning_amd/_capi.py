@@ -217,6 +217,21 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     lib.fsdp_route_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)]
     lib.fsdp_sort_cache_reset.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.fsdp_sort_cache_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.fsdp_device_alloc.restype = ctypes.c_void_p
+    lib.fsdp_device_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    lib.fsdp_device_free.restype = None
+    lib.fsdp_device_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.fsdp_device_write.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    lib.fsdp_device_read.argtypes = lib.fsdp_device_write.argtypes
+    lib.fsdp_device_owns.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    lib.fsdp_stream_create.restype = ctypes.c_void_p
+    lib.fsdp_stream_create.argtypes = [ctypes.c_void_p]
+    lib.fsdp_stream_destroy.restype = None
+    lib.fsdp_stream_destroy.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.fsdp_stream_wait_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    # (ctx, n_frames, cone_capacity, counts, cones, poses, prev_paths, paths, status, next_prev, records, after_stream, ticket)
+    lib.fsdp_submit_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.POINTER(ctypes.c_longlong)]
+    lib.fsdp_ticket_stream_wait.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
     got = (ctypes.c_int32 * 4)()
     lib.fsdp_shapes(got)
     want = [shapes.max_len, shapes.max_neighbors, shapes.max_match, shapes.path_points]
@@ -240,6 +255,8 @@ EXPORTED_SYMBOLS = [
     "fsdp_skidpad_submit", "fsdp_route_stats", "fsdp_ticket_capacity", "fsdp_selftest_det3", "fsdp_debug_arena", "fsdp_selftest_absminmax", "fsdp_selftest_libm", "fsdp_selftest_givens",
     "fsdp_sort_cache_reset", "fsdp_sort_cache_hits", "fsdp_sort_batch_ranked", "fsdp_plan_sequence", "fsdp_plan_sequence_compact",
     "fsdp_plan_sequence_cached", "fsdp_plan_sequence_cached_compact", "fsdp_submit_sequence", "fsdp_submit_sequence_compact",
+    "fsdp_device_alloc", "fsdp_device_free", "fsdp_device_write", "fsdp_device_read", "fsdp_device_owns", "fsdp_stream_create", "fsdp_stream_destroy",
+    "fsdp_stream_wait_stream", "fsdp_submit_device", "fsdp_ticket_stream_wait",
 ]
 RANK_MAX, COST_TERMS = 64, 7  # include/fsdp.h FSDP_RANK_MAX, FSDP_COST_TERMS
 COST_TERM_NAMES = ("angle", "residual_distance", "number_of_cones", "initial_direction", "change_of_direction", "cones_on_either",
@@ -433,7 +450,15 @@ class Context:
             pass
 
     @staticmethod
+    def _host_arrays(*arrays):
+        """The host entry points take host arrays: a device array is refused here, by name, before NumPy tries to convert it."""
+        for a in arrays:
+            if not isinstance(a, np.ndarray) and hasattr(a, "__cuda_array_interface__"):
+                raise TypeError(f"{type(a).__name__} is a device array; this call takes host arrays (device arrays go through submit_device)")
+
+    @staticmethod
     def _prep(offsets, cones, poses):
+        Context._host_arrays(offsets, cones, poses)
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         cones = np.ascontiguousarray(cones, dtype=np.float64).reshape(-1, 3)
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
@@ -528,6 +553,7 @@ class Context:
     @staticmethod
     def _prep_any_base(offsets, cones, poses):
         """_prep for the entry points that document cone_offsets[0] >= 0 (rows [offsets[0], offsets[-1]) of cones)."""
+        Context._host_arrays(offsets, cones, poses)
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         cones = np.ascontiguousarray(cones, dtype=np.float64).reshape(-1, 3)
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
@@ -663,9 +689,65 @@ class Context:
                        ctypes.byref(again), ctypes.byref(t)), "fsdp_submit_sequence")
         return SequenceTicket(int(t.value), out, final_prev_out, again, (offsets, cones, poses, init))
 
+    # device tickets: batches and results in the caller's GPU memory (fsdp_submit_device; device.py)
+    def submit_device(self, counts, cones, poses, prev=None, paths=None, status=None, next_prev=None, records=False, after_stream=None,
+                      cone_capacity: int | None = None) -> Ticket:
+        """fsdp_submit_device: one batch whose arrays are device memory of this context's GPU — DeviceArrays or any objects with
+        ``__cuda_array_interface__``: counts (n) int32, cones (n, cone_capacity, 3) float64 (None with cone_capacity = 0), poses (n, 4),
+        prev (n, path_points, 4) or None.  Missing outputs are allocated as DeviceArrays: paths (n, path_points, 4), status (n) int32;
+        next_prev only when given (it may be ``prev``); records: True, or a device array of n compact records (uint8 (n, itemsize)).
+        after_stream: the producer's hipStream_t (int) or None — the ONLY ordering against the arrays' producer: the `stream` entry of an
+        array's ``__cuda_array_interface__`` is not read (with None the inputs must be complete when the call is made).  collect() returns the dict of the output arrays.  Every array must
+        stay alive until collect (the ticket holds them)."""
+        from .device import DeviceArray, DeviceTicket, as_device_ptr
+
+        if isinstance(counts, np.ndarray) or not hasattr(counts, "__cuda_array_interface__"):
+            raise TypeError("submit_device takes device arrays (DeviceArray / __cuda_array_interface__); host arrays go through submit")
+        n = int(counts.__cuda_array_interface__["shape"][0])
+        if cone_capacity is None:
+            cone_capacity = 0 if cones is None else int(cones.__cuda_array_interface__["shape"][1])
+        cap, rows, rec = int(cone_capacity), self.shapes.path_points, self.compact_dtype.itemsize
+        if paths is None:
+            paths = DeviceArray(self, (n, rows, 4))
+        if status is None:
+            status = DeviceArray(self, (n,), np.int32)
+        if records is True:
+            records = DeviceArray(self, (n, rec), np.uint8)
+        elif records is False:
+            records = None
+        ptr = lambda a, shape, dt, writable=False: None if a is None else as_device_ptr(a, shape, dt, writable=writable)
+        t = ctypes.c_longlong(-1)
+        self._check(self._lib.fsdp_submit_device(
+            self._h, n, cap, ptr(counts, (n,), np.int32), ptr(cones if cap > 0 else None, (n, cap, 3), np.float64), ptr(poses, (n, 4), np.float64),
+            ptr(prev, (n, rows, 4), np.float64), ptr(paths, (n, rows, 4), np.float64, True), ptr(status, (n,), np.int32, True),
+            ptr(next_prev, (n, rows, 4), np.float64, True), ptr(records, (n, rec), np.uint8, True), after_stream, ctypes.byref(t)), "fsdp_submit_device")
+        out = {"paths": paths, "status": status, "next_prev": next_prev, "records": records}
+        return DeviceTicket(int(t.value), out, None, (counts, cones, poses, prev))
+
+    def stream_wait(self, ticket: Ticket, stream):
+        """fsdp_ticket_stream_wait: whatever is enqueued on ``stream`` (a hipStream_t as an int) afterwards runs behind the ticket."""
+        self._check(self._lib.fsdp_ticket_stream_wait(self._h, ctypes.c_longlong(ticket.id), ctypes.c_void_p(stream)), "fsdp_ticket_stream_wait")
+
+    def stream_create(self) -> int:
+        s = self._lib.fsdp_stream_create(self._h)
+        if not s:
+            raise FsdpError("fsdp_stream_create failed")
+        return int(s)
+
+    def stream_destroy(self, stream):
+        self._lib.fsdp_stream_destroy(self._h, ctypes.c_void_p(stream))
+
+    def stream_wait_stream(self, stream, after):
+        """fsdp_stream_wait_stream: ``stream`` waits for what ``after`` holds now."""
+        self._check(self._lib.fsdp_stream_wait_stream(self._h, ctypes.c_void_p(stream), ctypes.c_void_p(after)), "fsdp_stream_wait_stream")
+
+    def device_owns(self, ptr: int, nbytes: int) -> bool:
+        return bool(self._lib.fsdp_device_owns(self._h, ctypes.c_void_p(ptr), ctypes.c_size_t(int(nbytes))))
+
     def collect(self, ticket: Ticket):
         """Wait for this ticket only; returns its result array — for a ticket of submit_sequence (results, final_prev,
-        n_replanned), the first two being the recording's arrays the call wrote its rows of."""
+        n_replanned), the first two being the recording's arrays the call wrote its rows of; for a device ticket the dict of its
+        output device arrays (FsdpError when a count was outside [0, cone_capacity])."""
         self._check(self._lib.fsdp_collect(self._h, ctypes.c_longlong(ticket.id)), "fsdp_collect")
         ticket._keep = None
         if isinstance(ticket, SequenceTicket):

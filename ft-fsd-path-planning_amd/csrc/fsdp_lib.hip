@@ -30,6 +30,7 @@
 #include "sort_rank_kernels.h"  // (behind the pass kernels: the kernels in front of it keep their order in the code object)
 #include "sequence_launch.h"    // (the chain kernels of fsdp_plan_sequence are a translation unit of their own: sequence_lib.hip)
 #include "host_buffers.h"       // (no kernels: DeviceBuf / PinnedBuf and the stores a slot and a context own)
+#include "device_io_launch.h"   // (the kernels of a device ticket are a translation unit of their own: device_io_lib.hip)
 
 using namespace fsdp;
 
@@ -119,6 +120,20 @@ struct Work {
     double* final_dev = nullptr;    // where seq_final_kernel writes: page-locked host memory (the caller's rows or the ticket's h_fin), or the slot's d_seq_final
     bool fin_staged = false;        // final_prev goes through h_fin (fsdp_collect copies it out)
   };
+  // A device ticket's pass (fsdp_submit_device): the caller's arrays in the memory of the context's GPU.  The pass runs with both
+  // route kernels and is never repeated, so what it wrote is final when the ticket's event fires.
+  struct DevPass {
+    bool on = false;
+    int cap = 0;                       // cone_capacity: rows per frame of `cones`
+    const int32_t* counts = nullptr;
+    const double* cones = nullptr;
+    const double* poses = nullptr;
+    const double* prev = nullptr;      // or NULL
+    double* paths = nullptr;
+    int32_t* status = nullptr;
+    double* next_prev = nullptr;       // or NULL; may be `prev`
+    fsdp_compact_result* records = nullptr;  // or NULL
+  };
   // tickets of fsdp_submit / fsdp_skidpad_submit / fsdp_submit_sequence queued on this slot's stream (id -1: free entry).  A ticket
   // holds the whole description of its pass: enqueue_ticket launches the first pass and fsdp_collect's rerun from it alone.
   struct Ticket {
@@ -144,6 +159,9 @@ struct Work {
     SeqPass sq;                            // a sequence ticket's pass
     int cache_lo = -1;                     // >= 0: a chunk of a lock-step call that advances the sorting cache (the _cached sorting
                                            // kernels); its frame 0 is this planner
+    DevPass dev;                           // a device ticket's pass
+    PinnedBuf<int32_t> h_bad;              // pinned + mapped: the lowest frame of a device ticket whose count was out of range, or -1
+    Event after;                           // a device ticket: recorded on the producer's stream, waited for by the slot's
     Event done;                            // recorded behind the ticket's last command
     // the entry is free again: what the caller owned, and what described his pass, is forgotten
     void release() {
@@ -152,6 +170,7 @@ struct Work {
       user_info = nullptr;
       compact = false;
       sq = SeqPass();
+      dev = DevPass();
       cache_lo = -1;
     }
   } tk[SLOT_QUEUE];
@@ -332,6 +351,52 @@ static bool inputs_pinned(const Batch& b) {
   return b.n > 0 && is_pinned(b.off, sizeof(int32_t) * (n + 1)) && is_pinned(b.poses, sizeof(double) * 4 * n) &&
          (b.total == 0 || is_pinned(b.cones + 3 * (size_t)b.off[0], sizeof(double) * 3 * b.total)) &&
          (!b.prev || is_pinned(b.prev, sizeof(double) * PATH_POINTS * 4 * n));
+}
+
+// ---- device memory: the counterpart of is_pinned for the arrays of a device ticket --------------------------------------------
+// [p, p + bytes) lies in ONE allocation of plain device memory on the context's GPU (not managed, not another GPU's, not host
+// memory of any kind, and known to the runtime this library links)
+static bool device_owns(const fsdp_ctx* c, const void* p, size_t bytes) {
+  if (!p) return false;
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof(a));
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (a.type != hipMemoryTypeDevice || a.isManaged || a.device != c->device) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  const char* lo = (const char*)base;
+  return (const char*)p >= lo && bytes <= size && (size_t)((const char*)p - lo) <= size - bytes;
+}
+// p is device memory (any GPU's): what a host entry point must not dereference
+static bool is_device_memory(const void* p) {
+  if (!p) return false;
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof(a));
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice && !a.isManaged;
+}
+struct NamedPtr {
+  const char* name;
+  const void* p;
+};
+// the host entry points' mirror of fsdp_submit_device's pointer rule: an error code instead of a host crash in check_batch
+static int refuse_device_pointers(fsdp_ctx* c, const char* who, std::initializer_list<NamedPtr> ptrs) {
+  for (const NamedPtr& x : ptrs)
+    if (is_device_memory(x.p)) {
+      c->err = std::string(who) + ": " + x.name + " is device memory; this entry point takes host pointers (device arrays go through fsdp_submit_device)";
+      return 1;
+    }
+  return 0;
 }
 
 // ---- the kernels of one pass ----------------------------------------------------------------------------------------------
@@ -607,6 +672,8 @@ struct Pass {
                                       // replayed through every slot of the overlap depth
   SortVariant sort;                   // the sorting kernels' instantiation: PLAIN, CACHED, or SPEC (its arguments are made by launch_pass)
   const Work::SeqPass* sq = nullptr;  // a sequence pass: the chain kernels between the path stage and the assembly
+  bool device = false;                // a device ticket's pass: `host` (or NULL: the slot's block) is device memory, the results are handed
+                                      // out by device_out_kernel, and path_retry_kernel's grid is always sized from the retry hint
 };
 
 // skid: a skidpad step's records (path stage only, on the context's stream)
@@ -614,7 +681,7 @@ static void launch_assemble(fsdp_ctx* c, Work& q, int n, const Pass& pass, bool 
   long long blocks = ((long long)n + 3) / 4;  // one wavefront per frame, four per workgroup (grid-stride beyond the cap)
   // results that go straight to host memory leave at the link's pace: a few hundred wavefronts keep it busy, more would
   // only sit on the SIMDs' wavefront slots with their stores pending while the other slots' kernels wait for a place
-  const long long cap = pass.host ? 128 : 16384;  // (32 / 128 / 512 workgroups towards host memory: 5.1 / 5.2 / 5.4 M frames/s streamed, inside the noise: profiles/r06_streaming_probe.txt)
+  const long long cap = pass.host && !pass.device ? 128 : 16384;  // (32 / 128 / 512 workgroups towards host memory: 5.1 / 5.2 / 5.4 M frames/s streamed, inside the noise: profiles/r06_streaming_probe.txt)
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   q.seq++;
@@ -725,7 +792,7 @@ static int launch_pass(fsdp_ctx* c, Work& q, const InputStore<>& in_, const Pass
   if (with_retry) {
     mark(q, t, after_path);
     after_path = MARK_PLAIN;
-    launch_path_retry(c, q, in, !pass.force_routes || c->retry_hint > 0);
+    launch_path_retry(c, q, in, !pass.force_routes || c->retry_hint > 0 || pass.device);
     names += "path_retry_kernel,";
   }
   if (pass.sq) {  // (fsdp_plan_sequence: never timed)
@@ -742,7 +809,7 @@ static int launch_pass(fsdp_ctx* c, Work& q, const InputStore<>& in_, const Pass
   q.ran_retry = with_retry;
   q.unverified = pass.trailer == SLOT_QUEUE;  // (a ticket's pass is settled by fsdp_collect, through the ticket's own trailer)
   q.pass_skid = false;
-  c->last = fsdp_ctx::LastPass{q.index, in.n_frames, pass.host == nullptr, true};
+  c->last = fsdp_ctx::LastPass{q.index, in.n_frames, pass.host == nullptr && !pass.device, true};
   return 0;
 }
 
@@ -1626,6 +1693,8 @@ static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const doub
     return 1;
   }
   HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = refuse_device_pointers(c, "fsdp_submit", {{"cone_offsets", off}, {"cones_xyt", cones}, {"poses", poses}, {"prev_paths", prev_paths}, {"results", results}}))
+    return rc;
   Batch b;
   if (int rc = check_batch(c, n_frames, off, cones, poses, prev_paths, &b)) return rc;
   Work* qp = nullptr;
@@ -1688,6 +1757,16 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
     if (tr.seq != t.seq) {
       c->err = "internal: trailer of ticket " + std::to_string(ticket) + " overwritten";
       rc = 2;
+    } else if (t.dev.on) {
+      // (a device ticket ran both routes: nothing is ever rerun — a consumer on the GPU has already read its results)
+      if (settle_routes(c, tr, t.ran_big, t.ran_retry, false)) {
+        c->err = "internal: device ticket " + std::to_string(ticket) + " lacked a route kernel";
+        rc = 2;
+      } else if (const int32_t bad = __atomic_load_n(t.h_bad.get(), __ATOMIC_RELAXED); bad >= 0) {
+        c->err = "fsdp_collect: counts[" + std::to_string(bad) + "] of device ticket " + std::to_string(ticket) + " lies outside [0, cone_capacity = " +
+                 std::to_string(t.dev.cap) + "] (the lowest such frame; every such frame was planned as having 0 cones: the call's outputs are not to be used)";
+        rc = 1;
+      }
     } else if (settle_routes(c, tr, t.ran_big, t.ran_retry, false)) {
       // the whole ticket once more, with both route kernels and the kernels of its first pass, behind whatever the slot's
       // stream holds by now (the caller's buffers are still his to leave alone: the batch is read again from them)
@@ -1733,6 +1812,228 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
   return rc;
 }
 
+// ---- device tickets ---------------------------------------------------------------------------------------------------------------
+void* fsdp_device_alloc(fsdp_ctx* c, size_t bytes) {
+  if (!c || hipSetDevice(c->device) != hipSuccess) return nullptr;
+  void* p = nullptr;
+  if (alloc_result(hipMalloc(&p, bytes ? bytes : 1)) != hipSuccess) return nullptr;
+  return p;
+}
+void fsdp_device_free(fsdp_ctx* c, void* p) {
+  if (!c || !p) return;
+  (void)hipSetDevice(c->device);
+  (void)hipFree(p);
+}
+int fsdp_device_write(fsdp_ctx* c, void* dst_dev, const void* src_host, size_t bytes) {
+  if (!c) return 1;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (bytes == 0) return 0;
+  if (!src_host || !device_owns(c, dst_dev, bytes)) {
+    c->err = "fsdp_device_write: dst_dev must be device memory of the context's GPU over the whole extent, src_host host memory";
+    return 1;
+  }
+  HIP_TRY(c, copy_sync(c, dst_dev, src_host, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+int fsdp_device_read(fsdp_ctx* c, void* dst_host, const void* src_dev, size_t bytes) {
+  if (!c) return 1;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (bytes == 0) return 0;
+  if (!dst_host || !device_owns(c, src_dev, bytes)) {
+    c->err = "fsdp_device_read: src_dev must be device memory of the context's GPU over the whole extent, dst_host host memory";
+    return 1;
+  }
+  HIP_TRY(c, copy_sync(c, dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+int fsdp_device_owns(fsdp_ctx* c, const void* p, size_t bytes) {
+  if (!c || !p || hipSetDevice(c->device) != hipSuccess) return 0;
+  return device_owns(c, p, bytes) ? 1 : 0;
+}
+void* fsdp_stream_create(fsdp_ctx* c) {
+  if (!c || hipSetDevice(c->device) != hipSuccess) return nullptr;
+  hipStream_t s = nullptr;
+  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return s;
+}
+void fsdp_stream_destroy(fsdp_ctx* c, void* stream) {
+  if (!c || !stream) return;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize((hipStream_t)stream);
+  (void)hipStreamDestroy((hipStream_t)stream);
+}
+int fsdp_stream_wait_stream(fsdp_ctx* c, void* stream, void* after) {
+  if (!c) return 1;
+  if (!stream || !after) {
+    c->err = "fsdp_stream_wait_stream: NULL stream";
+    return 1;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  Event e;  // (destroyed at return: the runtime keeps what the enqueued wait needs)
+  HIP_TRY(c, hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(e, (hipStream_t)after));
+  HIP_TRY(c, hipStreamWaitEvent((hipStream_t)stream, e, 0));
+  return 0;
+}
+
+// enqueue device ticket t on slot q: the producer's event, scan + gather into the slot's input copies, the pass with both routes,
+// device_out_kernel, the ticket's event.  Never called twice for a ticket.
+static int enqueue_device_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, hipStream_t after_stream) {
+  const Work::DevPass& d = t.dev;
+  const int n = t.batch.n;
+  const size_t rows = t.batch.total;
+  const bool with_prev = d.prev != nullptr;
+  // a bigger batch than the slot has seen: its buffers are replaced — not under the feet of the passes queued on the stream
+  if ((size_t)n > q.buf.frames() || !q.in.fits((size_t)n, rows, with_prev)) HIP_TRY(c, hipStreamSynchronize(q.stream));
+  if (int rc = ensure_work(c, q, n)) return rc;
+  // (rows and max_cones are upper bounds: n * cone_capacity, cone_capacity; batch.prev says whether the store holds previous paths)
+  if (int rc = take_batch(c, q.in, t.batch)) return rc;
+  HIP_TRY(c, t.h_bad.reserve(1, 16, Pin::MappedCoherent));
+  t.h_bad[0] = -1;
+  if (after_stream) {
+    if (!t.after) HIP_TRY(c, hipEventCreateWithFlags(&t.after.h, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(t.after, after_stream));
+    HIP_TRY(c, hipStreamWaitEvent(q.stream, t.after, 0));
+  }
+  fsdp_dio_in_args a;
+  a.n_frames = n;
+  a.cone_capacity = d.cap;
+  a.counts = d.counts;
+  a.cones = d.cones;
+  a.poses = d.poses;
+  a.prev = d.prev;
+  a.bad_frame = t.h_bad.device();
+  a.dst_off = q.in.d_off;
+  a.dst_cones = q.in.d_cones;
+  a.dst_poses = q.in.d_poses;
+  a.dst_prev = q.in.d_prev;
+  fsdp_dio_launch_in(q.stream, &a);
+  Pass pass;
+  pass.device = true;
+  pass.compact = true;
+  pass.host = (fsdp_frame_result*)d.records;  // (device memory; NULL: the slot's result block)
+  pass.trailer = (int)(&t - q.tk);
+  pass.force_routes = true;
+  pass.in_flight = t.in_flight;
+  if (int rc = launch_pass(c, q, q.in, pass)) return rc;
+  t.seq = q.seq;
+  t.ran_big = q.ran_big;
+  t.ran_retry = q.ran_retry;
+  t.via_stage = false;
+  fsdp_dio_out_args o;
+  o.n_frames = n;
+  o.sorted = q.buf.d_sort;
+  o.matched = q.buf.d_match;
+  o.paths = q.buf.d_path;
+  o.prev = with_prev ? q.in.d_prev.get() : nullptr;
+  o.default_path = c->d_default_path;
+  o.out_paths = d.paths;
+  o.out_status = d.status;
+  o.next_prev = d.next_prev;
+  fsdp_dio_launch_out(q.stream, &o);
+  HIP_TRY(c, hipGetLastError());
+  if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done.h, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(t.done, q.stream));
+  return 0;
+}
+
+int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
+                       const double* prev_paths, double* paths, int32_t* status, double* next_prev, fsdp_compact_result* records,
+                       void* after_stream, long long* ticket) {
+  if (!c || !ticket) return 1;
+  *ticket = -1;
+  const std::string who = "fsdp_submit_device";
+  if (c->mission == 2) {
+    c->err = who + ": a skidpad context plans through fsdp_skidpad_submit";
+    return 1;
+  }
+  if (c->n_cache > 0) {
+    c->err = who + ": the sorting cache is on (it stays a lock-step feature of the host calls: fsdp_sort_cache_reset(ctx, 0) turns it off)";
+    return 1;
+  }
+  if (n_frames < 1 || cone_capacity < 0) {
+    c->err = who + ": n_frames must be >= 1 and cone_capacity >= 0";
+    return 1;
+  }
+  if ((long long)n_frames * cone_capacity > 0x7fffffffll) {
+    c->err = who + ": n_frames x cone_capacity = " + std::to_string((long long)n_frames * cone_capacity) + " cone rows exceed the int32 offsets of a pass";
+    return 1;
+  }
+  if (!counts || !poses || !paths || !status || (cone_capacity > 0 && !cones)) {
+    c->err = who + ": counts, poses, paths and status are required" + (cone_capacity > 0 ? ", and cones with cone_capacity > 0" : "");
+    return 1;
+  }
+  if (!fsdp_dio_launch_in || !fsdp_dio_launch_out) {
+    c->err = who + ": this library was built without the device ticket kernels (csrc/device_io_lib.hip)";
+    return 2;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = (size_t)n_frames, row = sizeof(double) * PATH_POINTS * 4;
+  const struct {
+    const char* name;
+    const void* p;
+    size_t bytes;
+  } arrays[] = {{"counts", counts, sizeof(int32_t) * n},
+                {"cones", cone_capacity > 0 ? cones : nullptr, sizeof(double) * 3 * n * (size_t)cone_capacity},
+                {"poses", poses, sizeof(double) * 4 * n},
+                {"prev_paths", prev_paths, row * n},
+                {"paths", paths, row * n},
+                {"status", status, sizeof(int32_t) * n},
+                {"next_prev", next_prev, row * n},
+                {"records", records, sizeof(fsdp_compact_result) * n}};
+  for (const auto& x : arrays)
+    if (x.p && !device_owns(c, x.p, x.bytes)) {
+      c->err = who + ": " + x.name + " is not device memory of the context's GPU over its whole extent of " + std::to_string(x.bytes) +
+               " bytes (host memory, page-locked or not, goes through fsdp_submit; managed memory, another GPU's memory and memory of "
+               "another HIP runtime are not accepted)";
+      return 1;
+    }
+  Work* qp = nullptr;
+  Work::Ticket* t = nullptr;
+  if (int rc = free_ticket(c, "fsdp_submit_device", n_frames, &qp, &t)) return rc;
+  // (the batch as the slot's stores size it: counts only, and prev as the flag take_batch reads — the host never dereferences a device ticket's batch)
+  t->batch = Batch{n_frames, nullptr, nullptr, nullptr, prev_paths, n * (size_t)cone_capacity, cone_capacity};
+  t->skid = false;
+  t->in_flight = frames_in_flight(c, n_frames, true);
+  t->user_results = nullptr;
+  t->user_info = nullptr;
+  t->compact = true;
+  t->sq = Work::SeqPass();
+  t->cache_lo = -1;
+  t->dev = Work::DevPass{true, cone_capacity, counts, cone_capacity > 0 ? cones : nullptr, poses, prev_paths, paths, status, next_prev, records};
+  if (int rc = enqueue_device_ticket(c, *qp, *t, (hipStream_t)after_stream)) {
+    (void)hipStreamSynchronize(qp->stream);
+    (void)hipGetLastError();
+    t->release();
+    return rc;
+  }
+  t->id = c->next_ticket++;
+  c->outstanding++;
+  *ticket = t->id;
+  return 0;
+}
+
+int fsdp_ticket_stream_wait(fsdp_ctx* c, long long ticket, void* stream) {
+  if (!c) return 1;
+  Work::Ticket* t = find_ticket(c, ticket, nullptr);
+  if (!t || !t->done) {
+    c->err = "fsdp_ticket_stream_wait: unknown ticket " + std::to_string(ticket) + " (a collected ticket has finished: nothing to wait for)";
+    return 1;
+  }
+  if (!stream) {
+    c->err = "fsdp_ticket_stream_wait: NULL stream";
+    return 1;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (t->pending)
+    if (int rc = flush_skid(c)) return rc;
+  HIP_TRY(c, hipStreamWaitEvent((hipStream_t)stream, t->done, 0));
+  return 0;
+}
+
 int fsdp_ticket_capacity(const fsdp_ctx* c) { return c ? c->overlap * (c->mission == 2 ? 1 : SLOT_QUEUE) : 0; }
 
 int fsdp_route_stats(fsdp_ctx* c, int* expect_big, int* expect_retry, long long* reruns) {
@@ -1765,6 +2066,8 @@ static int plan_blocking(fsdp_ctx* c, int n_frames, const int32_t* off, const do
     return 1;
   }
   HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = refuse_device_pointers(c, "fsdp_plan_batch", {{"cone_offsets", off}, {"cones_xyt", cones}, {"poses", poses}, {"prev_paths", prev}, {"results", results}}))
+    return rc;
   Batch b;
   if (int rc = check_batch(c, n_frames, off, cones, poses, prev, &b)) return rc;
   const bool cached = sequential && c->n_cache > 0;
@@ -1884,7 +2187,8 @@ static int seq_refusals(fsdp_ctx* c, const std::string& who, const SeqCall& k, b
     c->err = who + ": results is NULL";
     return 1;
   }
-  return 0;
+  return refuse_device_pointers(c, who.c_str(), {{"cone_offsets", k.off}, {"cones_xyt", k.cones}, {"poses", k.poses}, {"initial_prev", k.initial_prev},
+                                                  {"results", k.results}, {"final_prev", k.final_prev}});
 }
 
 // the call's frames as a Batch: the whole call through check_batch (its arrays are the batch); a planner slice's segments

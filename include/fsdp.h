@@ -368,6 +368,73 @@ int fsdp_submit_sequence_compact(fsdp_ctx* ctx, int n_planners, int n_steps, int
                                  const double* cones_xyt, const double* poses, const double* initial_prev, fsdp_compact_result* results,
                                  double* final_prev, long long* n_replanned, long long* ticket);
 
+/* ---- device tickets: batches and results in the caller's GPU memory --------------------------------------------------------
+ * For a caller whose cones already live on the GPU (a simulator fleet, a perception network, a controller that consumes paths
+ * on the device): nothing crosses PCIe, and no host synchronisation is needed between one tick and the next.  The reference has
+ * no counterpart (it is host Python); the results are those of fsdp_plan_batch_compact / fsdp_plan_batch_sequential on the same
+ * frames, byte for byte.
+ *
+ * Input layout — a fixed-capacity tensor, not a CSR (a host that cannot read the offsets cannot check or rebase them):
+ *   counts      (n_frames) int32
+ *   cones       (n_frames, cone_capacity, 3) float64 rows [x, y, ConeTypes]; frame f's cones are its first counts[f] rows, the
+ *               rows behind them are never read and may hold anything.  cone_capacity may be 0 with cones == NULL (a context
+ *               that plans from a global path)
+ *   poses       (n_frames, 4)
+ *   prev_paths  (n_frames, FSDP_PATH_POINTS, 4) or NULL, as for fsdp_plan_batch_sequential
+ * Pointer rule: every non-NULL array pointer must be plain device memory of the context's GPU over its whole extent, inside one
+ * allocation (fsdp_device_owns; fsdp_device_alloc, hipMalloc of the runtime this library links, or another framework's array
+ * that runtime knows).  Host memory — page-locked or not — is refused with 1 and a message that points to fsdp_submit; so are
+ * managed memory, another GPU's memory, an extent that runs past its allocation and a pointer the runtime does not know.
+ * Nothing is enqueued on a refusal.  (The mirror: fsdp_submit* and fsdp_plan_batch* refuse a device pointer with 1.) */
+
+/* hipMalloc on the context's GPU; NULL on failure */
+void* fsdp_device_alloc(fsdp_ctx* ctx, size_t bytes);
+void fsdp_device_free(fsdp_ctx* ctx, void* p);
+/* host -> device and device -> host of `bytes` bytes, synchronous (on the context's own stream); the device side must satisfy
+ * fsdp_device_owns */
+int fsdp_device_write(fsdp_ctx* ctx, void* dst_dev, const void* src_host, size_t bytes);
+int fsdp_device_read(fsdp_ctx* ctx, void* dst_host, const void* src_dev, size_t bytes);
+/* 1: [p, p + bytes) lies in ONE device allocation on the context's GPU (what fsdp_submit_device requires of an array), else 0 */
+int fsdp_device_owns(fsdp_ctx* ctx, const void* p, size_t bytes);
+/* A non-blocking HIP stream on the context's GPU (a hipStream_t) for a caller without a HIP binding of its own — a producer
+ * stream, or the stream a chain of device tickets is ordered on; destroy waits for what it holds.  fsdp_stream_wait_stream:
+ * whatever is enqueued on `stream` afterwards runs after what `after` holds now (an event recorded on `after`). */
+void* fsdp_stream_create(fsdp_ctx* ctx);
+void fsdp_stream_destroy(fsdp_ctx* ctx, void* stream);
+int fsdp_stream_wait_stream(fsdp_ctx* ctx, void* stream, void* after);
+
+/* One batch as a ticket (fsdp_collect, fsdp_ticket_done and fsdp_ticket_capacity as for fsdp_submit; such tickets may be in
+ * flight next to fsdp_submit tickets).  Outputs, device memory too:
+ *   paths      (n_frames, FSDP_PATH_POINTS, 4), required: the path field of every frame's record
+ *   status     (n_frames), required: the status field
+ *   next_prev  (n_frames, FSDP_PATH_POINTS, 4) or NULL: what the frame's planner hands to its next step — the new path when the
+ *              status is 0, else prev_paths[f], else (prev_paths NULL) the context's default path (fsdp_default_path).  It may
+ *              be the prev_paths array itself: the inputs are copied into the pass slot before anything is written
+ *   records    (n_frames) fsdp_compact_result or NULL; with use_unknown_cones = 0 the sorted indices refer to the caller's rows
+ *              of the frame
+ * Stream ordering.  after_stream (a hipStream_t, or NULL): the call records an event on it and the pass waits for that event —
+ * the producer's kernels need not have finished when the call is made; with NULL the inputs must be complete by then.
+ * fsdp_ticket_stream_wait(ctx, ticket, stream) makes `stream` wait for the ticket's last kernel (hipStreamWaitEvent on the
+ * ticket's event): how a consumer — or the producer of the next tick, which reads next_prev — orders itself behind a ticket
+ * without the host.  It takes any uncollected ticket.  The library does NOT order two device tickets against each other: they
+ * run on different pass slots, and a ticket that reads what another one writes (the next tick's prev_paths) needs the producer
+ * stream between them, as above.
+ * Finality.  The outputs are final when the ticket's event fires: the pass runs with both route kernels, so fsdp_collect
+ * never runs it again (a missing route would be an internal error, 2).
+ * fsdp_collect waits, releases the ticket and returns 1 when a count was outside [0, cone_capacity]; the message names the
+ * lowest such frame.  Every such frame was planned as having 0 cones — nothing is read outside the caller's rows — and the
+ * call's outputs are then not to be used.  The arrays must stay allocated until fsdp_collect.
+ * After the pass a device ticket is to fsdp_download / fsdp_resident_frames / fsdp_debug_* what an fsdp_submit ticket is.
+ * Returns an error, nothing enqueued: a pointer outside the rule above; NULL counts, poses, paths or status; a skidpad context;
+ * a context whose sorting cache is on; n_frames < 1; cone_capacity < 0; n_frames x cone_capacity beyond 2^31 - 1 rows; every
+ * ticket entry taken (4: collect one first); memory the device does not have (2; the context stays usable).
+ * Not offered: device forms of the sequence, cached, ranked, stage-level and skidpad calls, CSR input with
+ * device offsets, peer-GPU memory. */
+int fsdp_submit_device(fsdp_ctx* ctx, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
+                       const double* prev_paths, double* paths, int32_t* status, double* next_prev, fsdp_compact_result* records,
+                       void* after_stream, long long* ticket);
+int fsdp_ticket_stream_wait(fsdp_ctx* ctx, long long ticket, void* stream);
+
 /* The resident form: one batch stays in HBM and is planned again and again (the benchmark's step; a caller that plans the
  * same frames under several global paths / previous paths). */
 int fsdp_upload(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt, const double* poses);
