@@ -90,7 +90,7 @@ double fsdo_det3(const double* xy6) {
   return det3_lu(h);
 }
 
-// decision margins of the sorting stage (oracle_internal.h MarginRec): enable / reset, read (9 classes x 6 values:
+// decision margins of the sorting stage (oracle_internal.h MarginRec): enable / reset, read (MG_CLASSES = 10 classes x 6 values:
 // min non-zero margin, decisions, below 1e-6, below 1e-9, below 1e-12, exactly zero)
 void fsdo_margins_enable(int on) {
   g_margins = MarginRec();
@@ -100,14 +100,14 @@ void fsdo_margins_enable(int on) {
     g_margins.n[i] = g_margins.below_1e6[i] = g_margins.below_1e9[i] = g_margins.below_1e12[i] = g_margins.zero[i] = 0;
   }
 }
-void fsdo_margins_get(double* out54) {
+void fsdo_margins_get(double* out60) {
   for (int i = 0; i < MG_CLASSES; i++) {
-    out54[6 * i + 0] = g_margins.min_margin[i];
-    out54[6 * i + 1] = (double)g_margins.n[i];
-    out54[6 * i + 2] = (double)g_margins.below_1e6[i];
-    out54[6 * i + 3] = (double)g_margins.below_1e9[i];
-    out54[6 * i + 4] = (double)g_margins.below_1e12[i];
-    out54[6 * i + 5] = (double)g_margins.zero[i];
+    out60[6 * i + 0] = g_margins.min_margin[i];
+    out60[6 * i + 1] = (double)g_margins.n[i];
+    out60[6 * i + 2] = (double)g_margins.below_1e6[i];
+    out60[6 * i + 3] = (double)g_margins.below_1e9[i];
+    out60[6 * i + 4] = (double)g_margins.below_1e12[i];
+    out60[6 * i + 5] = (double)g_margins.zero[i];
   }
 }
 

@@ -61,7 +61,12 @@ enum MarginClass {
   MG_WRONG_DIRECTION = 6, // cost_function.py:149-188 sign and 40 deg of the turn angles
   MG_COST_ARGMIN = 7,     // relative gap between the best and the second-best configuration cost
   MG_COMBINE = 8,         // combine_traces.py:150-257 angle signs / 5 deg
-  MG_CLASSES = 9
+  // The thresholds that hold no libm value: the start ellipse and the (6, 3) ellipse of an edge (criterion vs 1), the nearest start
+  // cone vs max_dist_to_first, the start pair vs 1.1 max_dist and 1.4, a listed neighbour's squared distance vs max_dist^2, dc / dl
+  // vs 6 and the edge length vs 4 of the search, the squared distance vs 36 of the cost's nearby-cone search, dl / dr vs 3 of the
+  // combination.  (The two ellipses rotate by an angle: sin / cos enter the criterion, which is still compared with a constant.)
+  MG_ARITHMETIC = 9,
+  MG_CLASSES = 10
 };
 struct MarginRec {
   bool on = false;

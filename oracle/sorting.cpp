@@ -29,6 +29,7 @@ static inline bool point_inside_ellipse(double px, double py, double cx, double 
   Rot r(-ang);
   Vec2 q = r.apply(px - cx, py - cy);
   double crit = (q.x * q.x) / (major * major) + (q.y * q.y) / (minor * minor);
+  margin(MG_ARITHMETIC, crit, 1.0);
   return crit < 1;
 }
 
@@ -82,6 +83,7 @@ static int select_starting_cone(const Frame& f, int cone_type, const std::vector
     }
   }
   if (best < 0) return -1;
+  margin(MG_ARITHMETIC, dist[best], g_prm.max_dist_to_first);
   if (dist[best] > g_prm.max_dist_to_first) return -1;
   return best;
 }
@@ -105,6 +107,8 @@ static std::vector<int> select_first_k(const Frame& f, int cone_type) {
   if (angle_1 > angle_2) std::swap(index_1, index_2);
   double dist = norm2(d1x, d1y);
   const double max_dist = g_prm.max_dist;
+  margin(MG_ARITHMETIC, dist, max_dist * 1.1);
+  margin(MG_ARITHMETIC, dist, 1.4);
   if (dist > max_dist * 1.1 || dist < 1.4) return {index_1};
   return {index_2, index_1};
 }
@@ -137,6 +141,7 @@ static void create_adjacency(const Frame& f, int n_neighbors, int start_idx, int
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return row[a] < row[b] || (row[b] != row[b] && row[a] == row[a]); });
     for (int q = 0; q < n_neighbors && q < n; q++) {
       int j = order[q];
+      if (row[j] < INFINITY) margin(MG_ARITHMETIC, row[j], max_dist * max_dist);
       if (!(row[j] > max_dist * max_dist)) adj[(size_t)i * n + j] = 1;
     }
   }
@@ -262,6 +267,8 @@ static void neighbor_mask(const Frame& f, int cone_type, const std::vector<int>&
       double lx = f.x[last] - f.x[nb], ly = f.y[last] - f.y[nb];
       double cx = f.x[cand] - f.x[nb], cy = f.y[cand] - f.y[nb];
       double dc = norm2(cx, cy), dl = norm2(lx, ly);
+      margin(MG_ARITHMETIC, dc, 6.0);
+      margin(MG_ARITHMETIC, dl, 6.0);
       if (dc < 6.0 && dl < 6.0) margin(MG_ACOS_THRESHOLDS, std::cos(vec_angle_between(lx, ly, cx, cy)), std::cos(deg2rad(150)));
       if (dc < 6.0 && dl < 6.0 && vec_angle_between(lx, ly, cx, cy) > deg2rad(150)) {
         can[i] = 0;
@@ -278,6 +285,7 @@ static void neighbor_mask(const Frame& f, int cone_type, const std::vector<int>&
       double difference = angle_difference(angle_2, angle_1);
       double len = norm2(l2cx, l2cy);
       margin(MG_ABS_ANGLE, std::fabs(difference), thr_abs);
+      if (!(std::fabs(difference) > thr_abs)) margin(MG_ARITHMETIC, len, 4.0);
       if (!(std::fabs(difference) > thr_abs) && !(len < 4.0)) margin(MG_DIR_ANGLE, difference, cone_type == T_LEFT ? thr_dir : -thr_dir);
       if (std::fabs(difference) > thr_abs)
         can[i] = 0;
@@ -462,6 +470,7 @@ static void cones_on_each_side(const Frame& f, const std::vector<Config>& config
   all.erase(std::unique(all.begin(), all.end()), all.end());
   auto within = [&](int i, int j) {
     double d = (i == j) ? 1e7 : cdist_sq(f.x[i], f.y[i], f.x[j], f.y[j]);
+    margin(MG_ARITHMETIC, d, search_distance * search_distance);
     return d < search_distance * search_distance;
   };
   // find_nearby_cones_for_idxs :97-103
@@ -683,6 +692,8 @@ static void handle_same_cone(const Frame& f, std::vector<int>& left, std::vector
     int pl = left[li - 1], pr = right[ri - 1], ic = left[li];
     double dl = norm2(f.x[ic] - f.x[pl], f.y[ic] - f.y[pl]);
     double dr = norm2(f.x[ic] - f.x[pr], f.y[ic] - f.y[pr]);
+    margin(MG_ARITHMETIC, dl, 3.0);
+    margin(MG_ARITHMETIC, dr, 3.0);
     bool lv = dl < 3.0, rv = dr < 3.0;
     if ((lv || rv) && !(lv && rv)) {
       have = true;

@@ -180,6 +180,43 @@ void emu_sort(int n_frames, const int32_t* offsets, const double* cones, const d
   emu_filter(n_frames, offsets, cones);
   emu_sort_plain(n_frames, g_f_off.data(), g_f_cones.data(), poses, out);
 }
+// The three sorting kernels with the sorting cache on (sort_kernel_128_cached / sort_kernel_cached / sort_big_kernel_cached: the
+// CACHE instantiation of the stage), one planner per frame, every planner's entry empty — each side that has start cones is
+// checked, misses and is searched by that instantiation's own copies of the stage's functions.  hits: (frames, 2).
+void emu_sort_cached(int n_frames, const int32_t* offsets, const double* cones, const double* poses, fsdp::SortOut* out, int8_t* hits) {
+  using namespace fsdp;
+  const int32_t* off = offsets;
+  const double* xyt = cones;
+  if (!g_prm.use_unknown_cones) {
+    emu_filter(n_frames, offsets, cones);
+    off = g_f_off.data();
+    xyt = g_f_cones.data();
+  }
+  std::vector<SortCacheHdr> prev((size_t)n_frames), next((size_t)n_frames);
+  memset((void*)prev.data(), 0, sizeof(SortCacheHdr) * prev.size());
+  memset((void*)next.data(), 0xff, sizeof(SortCacheHdr) * next.size());
+  std::vector<int32_t> prev_off((size_t)n_frames + 1, 0);
+  std::vector<double> prev_xyt(3, 0.0), next_xyt(3 * (size_t)off[n_frames] + 3, 0.0);
+  SortCacheView v;
+  v.prev = prev.data();
+  v.next = next.data();
+  v.prev_xyt = prev_xyt.data();
+  v.prev_off = prev_off.data();
+  v.next_xyt = next_xyt.data();
+  v.next_off = off;  // (a planner's region: its frame's cones)
+  v.hits = hits;
+  std::vector<int> big((size_t)n_frames + 1, 0);
+  if (emu_sort128(n_frames, off))
+    emu::launch((unsigned)n_frames, 64, [&]() { sort_kernel_128_cached(n_frames, off, xyt, poses, out, big.data(), &g_prm, StageIn(), v); });
+  else
+    emu::launch((unsigned)n_frames, 64, [&]() { sort_kernel_cached(n_frames, off, xyt, poses, out, big.data(), &g_prm, StageIn(), v); });
+  g_last_big = big[0];
+  if (big[0] > 0) {
+    std::vector<SortSharedBig> state(2);
+    emu::launch(2, 64, [&]() { sort_big_kernel_cached(off, xyt, poses, out, big.data(), state.data(), &g_prm, v); });
+  }
+  emu_sort_remap(n_frames, out);
+}
 // indices of a filtered sort back into the caller's array (assemble_kernel's remap); no-op with use_unknown_cones on
 void emu_sort_remap(int n_frames, fsdp::SortOut* out) {
   if (g_prm.use_unknown_cones) return;

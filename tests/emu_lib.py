@@ -67,6 +67,20 @@ def sort(offsets, cones, poses):
     return out
 
 
+def sort_cached(offsets, cones, poses):
+    """The sorting kernels' cache-enabled instantiation (sort_kernel_128_cached / sort_kernel_cached / sort_big_kernel_cached), one
+    planner per frame with an empty entry: every side is searched by that instantiation's own code -> (sort records, hits (n, 2))"""
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    cones = np.ascontiguousarray(cones, np.float64)
+    poses = np.ascontiguousarray(poses, np.float64)
+    n = len(offsets) - 1
+    out = np.zeros(n, SORT_DTYPE)
+    hits = np.full((n, 2), -1, np.int8)
+    lib().emu_sort_cached(ctypes.c_int(n), _p(offsets, ctypes.c_int32), _p(cones), _p(poses), ctypes.c_void_p(out.ctypes.data),
+                          ctypes.c_void_p(hits.ctypes.data))
+    return out, hits
+
+
 RANK_MAX, COST_TERMS = 64, 7
 
 

@@ -958,3 +958,78 @@ def match_degenerate_golden():
 
 if __name__ == "__main__" and "--match-degenerate-only" in sys.argv:  # (-only: without it the frame sets above are captured again first)
     match_degenerate_golden()
+
+
+def sort_constructed_golden():
+    """The constructed frames of the sorting stage (tests/sort_support.py: every member of every threshold pair with its mirrored
+    and colourless twins, the on-threshold and the structural cases, at the canonical pose) through the reference's planner:
+    left_config / right_config as calc_final_configs_for_left_and_right returns them, the start cones, the number of end
+    configurations and the best cost per side -> sort_constructed.npz.  A frame on which a later stage raises keeps its sorting
+    result (sort_ok); one on which the sorting stage itself raises has sort_ok False and the exception's class in exc.  Frames with
+    an exact tie in one of the reference's unstable argsorts (first_k_tie / knn_tie) are listed by name in tie_names.
+    knn_tie here is the condition under which the unstable argsort can change the adjacency, not refharness.knn_boundary_tie's wider
+    one (any two equal distances among a cone's eight smallest — true of every chain with equal spacings): some cone's k-th and
+    (k + 1)-th smallest squared distances, in either side's matrix (the other colour's rows and columns infinite), are equal, finite
+    and within max_dist^2, k = min(5, n - 1).  Equal distances inside the k nearest leave the set of neighbours as it is."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import sort_support as ss
+
+    refharness.load()
+    from fsd_path_planning.utils.math_utils import my_cdist_sq_euclidean
+
+    def knn_tie(xyt):
+        n = len(xyt)
+        k = min(5, n - 1)
+        if n < 3 or k >= n - 1:
+            return False
+        xy = np.ascontiguousarray(xyt[:, :2], dtype=float)
+        for other in (1.0, 2.0):
+            d = my_cdist_sq_euclidean(xy, xy).copy()
+            np.fill_diagonal(d, np.inf)
+            d[xyt[:, 2] == other, :] = np.inf
+            d[:, xyt[:, 2] == other] = np.inf
+            d.sort(axis=1)
+            if ((d[:, k - 1] == d[:, k]) & np.isfinite(d[:, k]) & (d[:, k] <= 6.5 * 6.5)).any():
+                return True
+        return False
+
+    named = []
+    for name, _obs, lo, hi in ss.all_pairs():
+        named += [(name + " below", lo), (name + " above", hi)]
+    named += ss.on_threshold() + [(n + ", mirrored", ss.mirrored(c)) for n, c in ss.on_threshold()] + ss.structural()
+    F = len(named)
+    out = dict(names=np.array([n for n, _c in named]), sort_ok=np.zeros(F, bool), exc=np.array([""] * F, dtype="U24"),
+               n_left=np.zeros(F, np.int32), n_right=np.zeros(F, np.int32), left_idx=np.full((F, MAX_LEN), -1, np.int32),
+               right_idx=np.full((F, MAX_LEN), -1, np.int32), first_k_left=np.full((F, 2), -1, np.int32), first_k_right=np.full((F, 2), -1, np.int32),
+               first_k_tie=np.zeros((F, 2), bool), knn_tie=np.zeros(F, bool), n_configs_left=np.zeros(F, np.int32), n_configs_right=np.zeros(F, np.int32),
+               best_cost_left=np.zeros(F), best_cost_right=np.zeros(F))
+    off, cones, poses = ss.as_batch([c for _n, c in named])
+    out.update(offsets=off, cones=cones, poses=poses)
+    for k, (_name, (xyt, pose)) in enumerate(named):
+        with np.errstate(all="ignore"):
+            r = refharness.run_frame(xyt, pose)
+        out["exc"][k] = "" if r["status"] == "ok" else r["status"]
+        out["knn_tie"][k] = knn_tie(xyt)
+        for si, (side, t) in enumerate((("left", 2), ("right", 1))):
+            out["first_k_tie"][k, si] = bool((r.get("first_k_tie") or {}).get(t, False))
+            fk = (r.get("first_k") or {}).get(t)
+            if fk is not None:
+                out[f"first_k_{side}"][k, : len(fk)] = fk
+            costs = r.get(f"{side}_costs")
+            if costs is not None and len(costs):
+                out[f"n_configs_{side}"][k], out[f"best_cost_{side}"][k] = len(costs), costs[0]
+        if "left_config" not in r:
+            continue
+        out["sort_ok"][k] = True
+        lc, rc = np.asarray(r["left_config"]), np.asarray(r["right_config"])
+        lc, rc = lc[lc != -1], rc[rc != -1]
+        out["n_left"][k], out["n_right"][k] = len(lc), len(rc)
+        out["left_idx"][k, : len(lc)], out["right_idx"][k, : len(rc)] = lc, rc
+    tie = out["knn_tie"] | out["first_k_tie"].any(axis=1)
+    out["tie_names"] = out["names"][tie]
+    np.savez_compressed(HERE / "sort_constructed.npz", **out)
+    print("sort_constructed frames", F, "sorted", int(out["sort_ok"].sum()), "exc", sorted(set(out["exc"].tolist()) - {""}), "argsort ties", int(tie.sum()))
+
+
+if __name__ == "__main__" and "--sort-constructed-only" in sys.argv:
+    sort_constructed_golden()

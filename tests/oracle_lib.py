@@ -155,6 +155,37 @@ def plan_batch(offsets, xyt, poses, n_threads: int = 1) -> np.ndarray:
     return out
 
 
+def sort_frame(xyt: np.ndarray, pose: np.ndarray) -> np.ndarray:
+    """The sorting stage alone (fsdo_sort_frame) -> a record whose sort fields and status are set."""
+    xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    out = np.zeros(1, dtype=RESULT_DTYPE)
+    lib().fsdo_sort_frame(_p(xyt), ctypes.c_int(len(xyt)), _p(pose), ctypes.c_void_p(out.ctypes.data))
+    return out[0]
+
+
+MARGIN_CLASSES = ("start_bearing", "second_side", "abs_angle", "dir_angle", "sign_flip", "acos_thresholds", "wrong_direction", "cost_argmin",
+                  "combine", "arithmetic")  # oracle/oracle_internal.h MarginClass, in order
+
+
+class margins:
+    """with oracle_lib.margins() as m: ... ; m.min["dir_angle"] — the sorting stage's decision margins (oracle_internal.h MarginRec)
+    of the calls made inside: per class the smallest non-zero |value - threshold| (1e300: none) and, in m.zero, how often the value was
+    the threshold bit for bit.  The recorder is process-wide and single-threaded: no n_threads > 1 inside."""
+
+    def __enter__(self):
+        lib().fsdo_margins_enable(ctypes.c_int(1))
+        self.min, self.zero, self.n = {}, {}, {}
+        return self
+
+    def __exit__(self, *a):
+        out = np.zeros(6 * len(MARGIN_CLASSES))
+        lib().fsdo_margins_get(_p(out))
+        lib().fsdo_margins_enable(ctypes.c_int(0))
+        for i, name in enumerate(MARGIN_CLASSES):
+            self.min[name], self.n[name], self.zero[name] = float(out[6 * i]), int(out[6 * i + 1]), int(out[6 * i + 5])
+
+
 def match(left, right, pose) -> np.ndarray:
     """The match stage alone (fsdo_match): sorted sides (n, 2) and the pose -> a record whose match fields are set."""
     left = np.ascontiguousarray(left, dtype=np.float64).reshape(-1, 2)

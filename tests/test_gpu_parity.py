@@ -1008,9 +1008,11 @@ def test_device_det3_sign_is_numpys(pkg, ctx):
 
 def test_device_libm_values_the_sorting_stage_decides_with(ctx):
     """The sorting stage keeps the ROCm device library's atan2 / acos where the reference compares np.arctan2 / np.arccos values
-    (search predicates, start-cone bearings, cost terms -> arg-min).  The closest such decision of 8.2 M recorded ones sits
-    3.9e-7 from its tie (profiles/r03_sort_decision_margins.txt), nine orders of magnitude above an ulp — as long as the
-    library's atan2 stays within an ulp or two of the true value.  Pinned here: against the correctly rounded det_atan2 (computed on
+    (search predicates, start-cone bearings, cost terms -> arg-min).  That the kernels decide like the oracle next to a tie no
+    longer rests on how far sampled frames stay from one: tests/test_sort_constructed_gpu.py puts a cone 1e-9 (relative) either
+    side of every threshold of the stage, and on it, on every route (tests/sort_support.py; the emulated kernels in
+    tests/test_sort_constructed_cpu.py).  Those pairs hold if the library's atan2 / acos stay within an ulp or two of the true
+    value, nine orders of magnitude below their offset.  Pinned here: against the correctly rounded det_atan2 (computed on
     the device next to it; bit-identical to the host copy that tests/test_det_math.py holds to mpmath) on 10^6 arguments —
     track-scale vectors, near-axis and near-diagonal directions, tiny and huge magnitudes — and acos against the host's on
     10^6 cosines incl. the neighbourhood of the thresholds' cosines and of +-1."""

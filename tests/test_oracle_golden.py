@@ -208,3 +208,44 @@ def test_oracle_matches_reference_on_duplicated_cone_frames(golden_dir, mode):
         p, q = res["path"][k], g["plan_path"][k]
         e = float(np.nanmax(np.abs(p - q)))
         assert e <= parity.PATH_TOL or (int(res["path_fallback"][k]) & parity.ARC_FLAG and parity.is_sample_count_flip(p, q)), (k, e)
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["libm", "detmath"])
+def test_oracle_matches_reference_on_constructed_sorting_frames(golden_dir, mode):
+    """The constructed frames of the sorting stage (tests/sort_support.py: every member of every threshold pair at the canonical pose
+    with its mirrored and colourless twins, the on-threshold and the structural cases) through the reference's planner
+    (make_golden.py --sort-constructed-only): the oracle returns the reference's sorted sides, start cones, configuration counts and
+    best costs on ALL of them — the members 1e-9 either side of a threshold included, so oracle and reference decide every pair the
+    same way — but for the frames named in tie_names (an exact tie in one of the reference's unstable argsorts: built as such),
+    which are held to the final sides only.  Where the reference raises in the sorting stage, the oracle raises."""
+    import sort_support as ss
+
+    g = np.load(golden_dir / "sort_constructed.npz")
+    named = []
+    for name, _obs, lo, hi in ss.all_pairs():
+        named += [(name + " below", lo), (name + " above", hi)]
+    named += ss.on_threshold() + [(n + ", mirrored", ss.mirrored(c)) for n, c in ss.on_threshold()] + ss.structural()
+    assert [n for n, _c in named] == g["names"].tolist()
+    off, cones, poses = ss.as_batch([c for _n, c in named])
+    assert np.array_equal(off, g["offsets"]) and np.array_equal(cones, g["cones"]) and np.array_equal(poses, g["poses"])
+    ties = set(g["tie_names"].tolist())
+    assert ties == {n for n in g["names"].tolist() if "tie" in n or n.startswith("combine: colourless")}, sorted(ties)
+    print(f"{len(named)} frames, {len(ties)} named argsort ties")
+    with oracle_lib.math_mode(mode):
+        res = np.array([oracle_lib.sort_frame(*c) for _n, c in named])
+    for k, (name, _c) in enumerate(named):
+        r = res[k]
+        if not g["sort_ok"][k]:
+            assert str(g["exc"][k]) == "IndexError" and int(r["status"]) == 102, (name, g["exc"][k], int(r["status"]))
+            continue
+        assert int(r["status"]) == 0, name
+        for s in ("left", "right"):
+            n = int(g[f"n_{s}"][k])
+            assert int(r[f"n_{s}"]) == n and np.array_equal(r[f"{s}_idx"][:n], g[f"{s}_idx"][k][:n]), (name, s, r[f"{s}_idx"], g[f"{s}_idx"][k])
+            if name in ties:
+                continue
+            assert np.array_equal(r[f"first_k_{s}"], g[f"first_k_{s}"][k]), (name, s, r[f"first_k_{s}"], g[f"first_k_{s}"][k])
+            assert int(r[f"n_configs_{s}"]) == int(g[f"n_configs_{s}"][k]), (name, s, int(r[f"n_configs_{s}"]), int(g[f"n_configs_{s}"][k]))
+            if g[f"n_configs_{s}"][k] > 0:
+                a, b = float(r[f"best_cost_{s}"]), float(g[f"best_cost_{s}"][k])
+                assert abs(a - b) <= 1e-9 * max(1.0, abs(b)), (name, s, a, b)  # (the bar of parity.compare_frame)

@@ -3,7 +3,8 @@
 value (atan2 / acos against a threshold, the arg-min over costs) ever come to its tie?  The kernels take those values from
 the device's libm (<= 1 ulp: ~4e-16 absolute on an angle), the oracle from glibc; a decision can only differ between them
 when its margin is of that order.  CPU only (the oracle, single thread); sets = the committed goldens + fresh synthetic
-frame sets of the fuzz sweep's classes.   python tools/sort_margins.py > profiles/r03_sort_decision_margins.txt"""
+frame sets of the fuzz sweep's classes.   python tools/sort_margins.py > profiles/sort_decision_margins_with_arithmetic.txt
+(profiles/r03_sort_decision_margins.txt is the table from before the arithmetic class existed)"""
 import ctypes, importlib, sys
 from pathlib import Path
 import numpy as np
@@ -14,7 +15,8 @@ pkg = importlib.import_module("ft-fsd-path-planning_amd")
 pkg._capi.DEFAULT_OPTIONS.update(pkg._capi.options_from_env())  # FSDP_PACK / FSDP_PATH_MODE / ... of this tool's shell -> fsdp_set_option
 NAMES = ["start-cone bearing (sign, pi/10, 4pi/5)", "second cone on the vehicle's side (sign, 5 deg)", "|turn| vs absolute threshold (65 deg)",
          "turn vs directional threshold (40 deg)", "sign flip of consecutive turns (signs, 1.3 rad)", "acos thresholds, in the cosine (150/90/30 deg)",
-         "wrong-direction cost terms (sign, 40 deg)", "cost arg-min: relative gap to the runner-up", "combination of the sides (turn signs)"]
+         "wrong-direction cost terms (sign, 40 deg)", "cost arg-min: relative gap to the runner-up", "combination of the sides (turn signs)",
+         "thresholds without a libm value (ellipses, distances)"]
 L = oracle_lib.lib()
 L.fsdo_margins_enable.argtypes = [ctypes.c_int]
 sets = []
@@ -33,7 +35,7 @@ frames = 0
 for name, off, cones, poses in sets:
     oracle_lib.plan_batch(off, cones, poses, n_threads=1)
     frames += len(off) - 1
-out = np.zeros(54)
+out = np.zeros(6 * len(NAMES))
 L.fsdo_margins_get(out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
 L.fsdo_margins_enable(0)
 print(f"{frames} frames in {len(sets)} sets (7 golden sets + 24 fresh synthetic sets of 1024 frames)")
@@ -44,3 +46,6 @@ for i, n in enumerate(NAMES):
 print("'exactly 0': value == threshold bit for bit — both angles come from identical operands (straight and lattice tracks of the demo")
 print("scenarios / lattice.npz), so the difference is 0.0 under any libm; the margins listed are those of all other decisions")
 print("libm error on these values: <= 1 ulp, i.e. <= 4.4e-16 absolute on an angle, <= 1.1e-16 on a cosine, ~1e-15 relative on a cost")
+print("last class: the start ellipse and the (6, 3) edge ellipse (criterion vs 1), nearest start cone vs max_dist_to_first, start pair vs 1.1 max_dist")
+print("and 1.4, listed neighbours' squared distance vs max_dist^2, dc / dl vs 6 and edge length vs 4 of the search, squared distance vs 36 of the")
+print("cost's nearby-cone search, dl / dr vs 3 of the combination; absolute margins.  tests/sort_support.py builds frames 1e-9 either side of each.")
