@@ -999,7 +999,10 @@ __device__ __forceinline__ int path_front(PS& S, const Arena& A, const MatchOut*
       use_prev = true;
     } else {
       // select_side_to_use :151-183 (<= 24 entries per side: group-uniform scalar loops)
-      int cntl = 0, cntr = 0, sl = 0, sr = 0;
+      // (the index sums in 64 bits, as NumPy's sum of an int64 array: two int32 values that are no index of anything still count
+      // and still add up — 2^31 - 1 twice must not wrap below a sum of 3)
+      int cntl = 0, cntr = 0;
+      long long sl = 0, sr = 0;
       for (int i = 0; i < nl; i++) {
         int v = mo->l2r[i];
         if (v != -1) {

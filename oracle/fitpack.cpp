@@ -139,13 +139,14 @@ void fpdisc(const double* t, int n, int k2, Band& b) {
 }
 
 // fpknot: add one knot inside the interval with the largest residual sum
-void fpknot(const double* x, double* t, int& n, double* fpint, int* nrdata, int& nrint, int istart) {
+void fpknot(const double* x, double* t, int& n, double* fpint, int* nrdata, int& nrint, int istart, unsigned* branches = nullptr) {
   int k = (n - nrint - 1) / 2;
   double fpmax = 0.;
   int jbegin = istart;
   int number = 0, maxpt = 0, maxbeg = 0;
   for (int j = 1; j <= nrint; j++) {
     int jpoint = nrdata[j];
+    if (branches && number != 0 && jpoint != 0 && fpmax == fpint[j]) *branches |= FB_KNOT_TIE;
     if (!(fpmax >= fpint[j] || jpoint == 0)) {
       fpmax = fpint[j];
       number = j;
@@ -154,6 +155,7 @@ void fpknot(const double* x, double* t, int& n, double* fpint, int* nrdata, int&
     }
     jbegin = jbegin + jpoint + 1;
   }
+  if (branches && maxpt == 1) *branches |= FB_SINGLE_POINT;
   int ihalf = maxpt / 2 + 1;
   int nrx = maxbeg + ihalf;
   int next = number + 1;
@@ -214,6 +216,7 @@ bool parcur_fit(const double* u0, const double* x0, const double* y0, int m, int
   int n = 0, ier = 0, nplus = 0, nrint = 0, nk1 = 0;
   double fp = 0, fpold = 0, fp0 = 0, fpms = 0, acc = 0;
   int nmax = 0;
+  unsigned br = 0;
 
   acc = TOL * s;
   nmax = m + k1;
@@ -327,6 +330,7 @@ bool parcur_fit(const double* u0, const double* x0, const double* y0, int m, int
       }
       fpms = fp - s;
       if (std::fabs(fpms) < acc) {
+        if (ier != -2) br |= FB_ACCEPT_AT_ONCE;
         done = true;
         break;
       }
@@ -347,7 +351,10 @@ bool parcur_fit(const double* u0, const double* x0, const double* y0, int m, int
       if (ier == 0) {
         int npl1 = nplus * 2;
         double rn = nplus;
+        br |= (fpold - fp > acc) ? FB_NPLUS_RATIO : FB_NPLUS_DOUBLE;
         if (fpold - fp > acc) npl1 = (int)(rn * fpms / (fpold - fp));
+        if (npl1 > nplus * 2) br |= FB_NPLUS_MIN;
+        if (npl1 < std::max(nplus / 2, 1)) br |= FB_NPLUS_MAX;
         nplus = std::min(nplus * 2, std::max(std::max(npl1, nplus / 2), 1));
       } else {
         nplus = 1;
@@ -393,7 +400,7 @@ bool parcur_fit(const double* u0, const double* x0, const double* y0, int m, int
       }
       fpint[nrint] = fpart;
       for (int lq = 1; lq <= nplus; lq++) {
-        fpknot(u.data(), t.data(), n, fpint.data(), nrdata.data(), nrint, 1);
+        fpknot(u.data(), t.data(), n, fpint.data(), nrdata.data(), nrint, 1, &br);
         if (n == nmax) {
           goto_interp_knots = true;
           restart = true;
@@ -410,6 +417,7 @@ bool parcur_fit(const double* u0, const double* x0, const double* y0, int m, int
   }
 
   if (to_part2 && ier != -2) {
+    br |= FB_PART2;
     // --- part 2: smoothing spline sp(u), root of f(p) = s ---
     fpdisc(t.data(), n, k2, b);
     double p1 = 0., f1 = fp0 - s, p3 = -one, f3 = fpms, p = 0.;
@@ -519,9 +527,11 @@ bool parcur_fit(const double* u0, const double* x0, const double* y0, int m, int
           finished = true;
           break;
         }
+        br |= FB_RATIONAL;
         p = fprati(p1, f1, p2, f2, p3, f3);
       }
     }
+    br |= (ich1 ? FB_ICH1 : 0u) | (ich3 ? FB_ICH3 : 0u) | ((ich1 | ich3) ? 0u : FB_NO_ICH);
     (void)finished;
   }
 
@@ -529,6 +539,8 @@ bool parcur_fit(const double* u0, const double* x0, const double* y0, int m, int
   out.n = n;
   out.ier = ier;
   out.fp = fp;
+  out.branches = br | (ier == -2 ? FB_POLYNOMIAL : 0u) | (ier == -1 ? FB_INTERPOLANT : 0u) | (ier == 1 ? FB_IER1 : 0u) | (ier == 2 ? FB_IER2 : 0u) |
+                 (ier == 3 ? FB_IER3 : 0u);
   out.t.assign(t.begin() + 1, t.begin() + 1 + n);
   out.cx.assign(c.begin() + 1, c.begin() + 1 + n);
   out.cy.assign(c.begin() + 1 + n, c.begin() + 1 + 2 * n);
@@ -585,6 +597,13 @@ int fsdo_splprep(const double* u, const double* x, const double* y, int m, int k
     cy_out[i] = sp.cy[i];
   }
   return 0;
+}
+
+// the ways parcur_fit took on this input (fitpack.h FitBranch bits); -1 where scipy would raise
+long fsdo_splprep_branches(const double* u, const double* x, const double* y, int m, int k, double s) {
+  fsdo::Spline sp;
+  if (!fsdo::parcur_fit(u, x, y, m, k, s, sp)) return -1;
+  return (long)sp.branches;
 }
 
 void fsdo_splev(const double* t, const double* cx, const double* cy, int n, int k, const double* u_eval, long n_eval,

@@ -76,6 +76,12 @@ void fsdo_match(const double* left, int nl, const double* right, int nr, const d
 // path from matched cones; returns status in out->status
 void fsdo_path(const double* left_v, int nl, const double* right_v, int nr, const int32_t* l2r, const int32_t* r2l,
                const double* pose, fsdo_frame_result* out);
+// the same with the planner's previous path and PathPlanner.global_path (NULL = none); record: fsdo_path_record_fields()
+// doubles, what the stage decided (NULL = not wanted).  (A call of its own: fsdo_path keeps its eight arguments for its callers.)
+void fsdo_path_full(const double* left_v, int nl, const double* right_v, int nr, const int32_t* l2r, const int32_t* r2l,
+                    const double* pose, fsdo_frame_result* out, const double* prev40x4, const double* gpath_xy, int n_gpath,
+                    double* record);
+int fsdo_path_record_fields(void);
 // the constant initial previous path (P11), (40,4)
 void fsdo_default_path(double* out40x4);
 

@@ -90,7 +90,7 @@ double fsdo_det3(const double* xy6) {
   return det3_lu(h);
 }
 
-// decision margins of the sorting stage (oracle_internal.h MarginRec): enable / reset, read (MG_CLASSES = 10 classes x 6 values:
+// decision margins of the sorting and the path stage (oracle_internal.h MarginRec): enable / reset, read (MG_CLASSES classes x 6 values:
 // min non-zero margin, decisions, below 1e-6, below 1e-9, below 1e-12, exactly zero)
 void fsdo_margins_enable(int on) {
   g_margins = MarginRec();
@@ -100,16 +100,19 @@ void fsdo_margins_enable(int on) {
     g_margins.n[i] = g_margins.below_1e6[i] = g_margins.below_1e9[i] = g_margins.below_1e12[i] = g_margins.zero[i] = 0;
   }
 }
-void fsdo_margins_get(double* out60) {
-  for (int i = 0; i < MG_CLASSES; i++) {
-    out60[6 * i + 0] = g_margins.min_margin[i];
-    out60[6 * i + 1] = (double)g_margins.n[i];
-    out60[6 * i + 2] = (double)g_margins.below_1e6[i];
-    out60[6 * i + 3] = (double)g_margins.below_1e9[i];
-    out60[6 * i + 4] = (double)g_margins.below_1e12[i];
-    out60[6 * i + 5] = (double)g_margins.zero[i];
+// n_classes: how many classes the caller's buffer holds (6 doubles each), from the first
+void fsdo_margins_get_n(double* out, int n_classes) {
+  for (int i = 0; i < MG_CLASSES && i < n_classes; i++) {
+    out[6 * i + 0] = g_margins.min_margin[i];
+    out[6 * i + 1] = (double)g_margins.n[i];
+    out[6 * i + 2] = (double)g_margins.below_1e6[i];
+    out[6 * i + 3] = (double)g_margins.below_1e9[i];
+    out[6 * i + 4] = (double)g_margins.below_1e12[i];
+    out[6 * i + 5] = (double)g_margins.zero[i];
   }
 }
+// the sorting stage's ten classes, 60 doubles: the call as it was before the path stage's classes joined the recorder
+void fsdo_margins_get(double* out60) { fsdo_margins_get_n(out60, MG_PATH_TOO_FAR); }
 
 void fsdo_sort_frame(const double* xyt, int n, const double* pose, fsdo_frame_result* o) {
   clear_result(o);
@@ -138,16 +141,33 @@ void fsdo_match(const double* left, int nl, const double* right, int nr, const d
   }
 }
 
-void fsdo_path(const double* left_v, int nl, const double* right_v, int nr, const int32_t* l2r, const int32_t* r2l,
-               const double* pose, fsdo_frame_result* o) {
+// prev40x4: CalculatePath.previous_paths[-1] or NULL (a fresh planner); gpath_xy (n_gpath, 2): PathPlanner.global_path or NULL;
+// record: PR_FIELDS doubles (oracle_internal.h PathRec: what the stage decided, value by value) or NULL
+void fsdo_path_full(const double* left_v, int nl, const double* right_v, int nr, const int32_t* l2r, const int32_t* r2l,
+                    const double* pose, fsdo_frame_result* o, const double* prev40x4, const double* gpath_xy, int n_gpath, double* record) {
   clear_result(o);
+  PathRec rec;
+  for (int i = 0; i < PR_FIELDS; i++) rec.v[i] = NAN;
+  rec.v[PR_N_FITS] = rec.v[PR_CURV_ZERO] = 0.0;
+  struct Guard {  // (the record goes out whichever way the frame ends)
+    PathRec& r;
+    double* out;
+    ~Guard() {
+      g_path_rec = nullptr;
+      if (out) std::memcpy(out, r.v, sizeof(r.v));
+    }
+  } guard{rec, record};
+  if (record) g_path_rec = &rec;
+  Pts gp;
+  if (gpath_xy)
+    for (int i = 0; i < n_gpath; i++) gp.push_back(Vec2{gpath_xy[2 * i], gpath_xy[2 * i + 1]});
   try {
     Pts L(nl), R(nr);
     for (int i = 0; i < nl; i++) L[i] = Vec2{left_v[2 * i], left_v[2 * i + 1]};
     for (int i = 0; i < nr; i++) R[i] = Vec2{right_v[2 * i], right_v[2 * i + 1]};
     std::vector<int> a(l2r, l2r + nl), b(r2l, r2l + nr);
     PathOut po;
-    calculate_path(L, R, a, b, Vec2{pose[0], pose[1]}, Vec2{pose[2], pose[3]}, po);
+    calculate_path(L, R, a, b, Vec2{pose[0], pose[1]}, Vec2{pose[2], pose[3]}, po, (const double(*)[4])prev40x4, gpath_xy ? &gp : nullptr);
     std::memcpy(o->path, po.p, sizeof(po.p));
     o->path_fallback = po.fallback;
   } catch (RefUndefined& e) {
@@ -155,6 +175,12 @@ void fsdo_path(const double* left_v, int nl, const double* right_v, int nr, cons
   } catch (PyValueError&) {
     o->status = FSDO_REF_UNDEFINED_PATH;
   }
+}
+int fsdo_path_record_fields(void) { return PR_FIELDS; }
+// a fresh planner, no global path, no record: the eight-argument call that callers written before fsdo_path_full make
+void fsdo_path(const double* left_v, int nl, const double* right_v, int nr, const int32_t* l2r, const int32_t* r2l,
+               const double* pose, fsdo_frame_result* o) {
+  fsdo_path_full(left_v, nl, right_v, nr, l2r, r2l, pose, o, nullptr, nullptr, 0, nullptr);
 }
 
 void fsdo_plan_frame_global(const double* xyt, int n, const double* pose, const double* prev40x4, const double* gpath_xy,

@@ -66,7 +66,22 @@ enum MarginClass {
   // vs 6 and the edge length vs 4 of the search, the squared distance vs 36 of the cost's nearby-cone search, dl / dr vs 3 of the
   // combination.  (The two ellipses rotate by an angle: sin / cos enter the criterion, which is still compared with a constant.)
   MG_ARITHMETIC = 9,
-  MG_CLASSES = 10
+  // The path stage's decisions (path.cpp; tools/path_margins.py).  None holds a libm value; each is recorded relative to its
+  // threshold (|value / threshold - 1|, or the absolute value where the threshold is 0).
+  MG_PATH_TOO_FAR = 10,       // closest dense sample vs maximal_distance_for_valid_path
+  MG_PATH_CONNECT_DIST = 11,  // first path point vs 0.5 m
+  MG_PATH_CONNECT_ANGLE = 12, // its bearing vs 90 deg
+  MG_PATH_FRONT_DOT = 13,     // dot(car -> point, direction) vs 0, every point of the path (absolute)
+  MG_PATH_PLEN = 14,          // path length in front vs mpc_path_length
+  MG_PATH_RADIUS = 15,        // fitted radius vs 10 / 80 / 100
+  MG_PATH_TRIM_ARGMIN = 16,   // remove_path_behind_car: closest vs second closest distance
+  MG_PATH_CUT = 17,           // cumulative length vs mpc_path_length at the cut and one sample before it
+  MG_PATH_SKIP_FRAC = 18,     // distance of the skip quotient from the next integer (absolute)
+  MG_PATH_DENSE_FRAC = 19,    // ... of max_u / predict_every of the parameterisation's samples
+  MG_PATH_CURV_CLAMP = 20,    // window radius vs 1 and 3000
+  MG_PATH_GLOBAL_30M = 21,    // global-path point vs 30 m
+  MG_PATH_GLOBAL_ARGMIN = 22, // global path: closest vs second closest distance
+  MG_CLASSES = 23
 };
 struct MarginRec {
   bool on = false;
@@ -88,6 +103,55 @@ static inline void margin(int cls, double value, double thr) {
   if (m < 1e-6) r.below_1e6[cls]++;
   if (m < 1e-9) r.below_1e9[cls]++;
   if (m < 1e-12) r.below_1e12[cls]++;
+}
+
+static inline void margin_rel(int cls, double value, double thr) { margin(cls, value / thr, 1.0); }
+
+// What the path stage decided on one frame, value by value (fsdo_path_full's optional record; tests/path_support.py proves with it
+// that a pair of cases straddles the threshold it is named after).  NaN = the frame did not get there.  The MPC step's entries
+// are those of its last run (the retry with the previous path, where there was one).
+enum PathRecField {
+  PR_N_CENTER = 0,     // points handed to fit #1 (before any fallback)
+  PR_TOO_FAR,          // distance of the closest dense sample
+  PR_CONNECT_DIST,     // distance of the first path point
+  PR_CONNECT_ANGLE,    // its bearing
+  PR_FIRST_FRONT,      // index of the first point in front of the car (-1: none), in the path after connect_path_to_car
+  PR_FRONT_DOT,        // the dot product of smallest magnitude
+  PR_N_IN_FRONT,       // points of mask_path_is_in_front_of_car
+  PR_PLEN,             // path length in front
+  PR_RADIUS,           // fitted radius before the clamps
+  PR_ARC_SIGN,         // +1 / -1: the arc turns left / right
+  PR_TRIM_INDEX,       // arg-min of remove_path_behind_car
+  PR_TRIM_GAP,         // second smallest distance - smallest (0: a bit-equal tie)
+  PR_N_REFIT,          // points handed to the refit
+  PR_CUT_INDEX,        // first segment whose cumulative length exceeds mpc_path_length (= points kept)
+  PR_CUT_OVER,         // that cumulative length
+  PR_CUT_UNDER,        // the one before it
+  PR_SKIP_QUOTIENT,    // predict_every / mean distance of _refit_spline
+  PR_SKIP,
+  PR_N_SKIPPED,        // points handed to fit #3
+  PR_DENSE_QUOTIENT,   // max_u / predict_every of fit #3
+  PR_N_DENSE,
+  PR_WINDOW,           // curvature window
+  PR_RADIUS_MIN,       // smallest / largest window radius before the clamps
+  PR_RADIUS_MAX,
+  PR_CURV_ZERO,        // windows whose determinant is exactly 0
+  PR_GLOBAL_ARGMIN,    // global path: index of the closest point
+  PR_GLOBAL_GAP,       // second smallest distance - smallest
+  PR_GLOBAL_KEPT,      // points within 30 m
+  PR_GLOBAL_30M,       // the distance closest to 30 m
+  PR_FIT_BRANCHES,     // FitBranch masks of the frame's fits, in call order (up to 6)
+  PR_FIT_IER = PR_FIT_BRANCHES + 6,
+  PR_FIT_KNOTS = PR_FIT_IER + 6,  // ... their numbers of knots
+  PR_N_FITS = PR_FIT_KNOTS + 6,
+  PR_FIELDS
+};
+struct PathRec {
+  double v[PR_FIELDS];
+};
+extern thread_local PathRec* g_path_rec;
+static inline void prec(int field, double value) {
+  if (g_path_rec) g_path_rec->v[field] = value;
 }
 
 // sorting.cpp

@@ -92,6 +92,7 @@ struct Fitted {
 
 // optional capture of every fit of a frame, in call order (fsdo_plan_frame_capture: per-stage intermediates for the tests)
 thread_local std::vector<Spline>* g_fit_capture = nullptr;
+thread_local PathRec* g_path_rec = nullptr;
 
 static Fitted spline_fit(const Pts& trace, double smoothing, double predict_every, int max_deg) {
   Fitted f;
@@ -116,6 +117,15 @@ static Fitted spline_fit(const Pts& trace, double smoothing, double predict_ever
   }
   if (!parcur_fit(u.data(), x.data(), y.data(), m, k, smoothing, f.sp)) throw PyValueError{1};
   if (g_fit_capture) g_fit_capture->push_back(f.sp);
+  if (g_path_rec) {
+    const int nf = (int)g_path_rec->v[PR_N_FITS];
+    if (nf < 6) {
+      g_path_rec->v[PR_FIT_BRANCHES + nf] = (double)f.sp.branches;
+      g_path_rec->v[PR_FIT_IER + nf] = (double)f.sp.ier;
+      g_path_rec->v[PR_FIT_KNOTS + nf] = (double)f.sp.n;
+    }
+    g_path_rec->v[PR_N_FITS] = nf + 1;
+  }
   f.max_u = u[m - 1];
   return f;
 }
@@ -157,12 +167,19 @@ static std::vector<double> path_curvature(const Pts& path, int window_size) {
     for (size_t q = 0; q < win.size(); q++) pts[q] = path[win[q]];
     double cx, cy, r;
     circle_fit(pts, cx, cy, r);
+    margin_rel(MG_PATH_CURV_CLAMP, r, 1.0);
+    margin_rel(MG_PATH_CURV_CLAMP, r, 3000.0);
+    if (g_path_rec) {
+      if (!(g_path_rec->v[PR_RADIUS_MIN] <= r)) g_path_rec->v[PR_RADIUS_MIN] = r;
+      if (!(g_path_rec->v[PR_RADIUS_MAX] >= r)) g_path_rec->v[PR_RADIUS_MAX] = r;
+    }
     r = py_min(py_max(r, 1.0), 3000.0);
     double c = 1 / r;
     int np_ = (int)pts.size();
     int i0 = 0, i1 = (int)(np_ / 2), i2 = np_ - 1;
     double hm[3][3] = {{1.0, pts[i0].x, pts[i0].y}, {1.0, pts[i1].x, pts[i1].y}, {1.0, pts[i2].x, pts[i2].y}};
     double sg = det3_lu(hm);
+    if (g_path_rec && sg == 0.0) g_path_rec->v[PR_CURV_ZERO] += 1.0;
     curv[i] = c * np_sign(sg);
   }
   return curv;
@@ -208,17 +225,28 @@ static void parameterize_path(const Pts& path, double out[][4]) {
       throw RefUndefined{FSDO_REF_UNDEFINED_PATH};  // OverflowError propagates
     else
       skip = std::max((int)q, 1);
+    prec(PR_SKIP_QUOTIENT, q);
+    if (std::isfinite(q) && q >= 1.0) margin(MG_PATH_SKIP_FRAC, q - std::floor(q) > 0.5 ? std::floor(q) + 1.0 - q : q - std::floor(q), 0.0);
   }
+  prec(PR_SKIP, skip);
   Pts skipped;
   for (int i = 0; i < n; i += skip) skipped.push_back(path[i]);
+  prec(PR_N_SKIPPED, (double)skipped.size());
   Fitted fit = spline_fit(skipped, 0.01, predict_every, 3);  // path_parameterization.py:155-157: max_deg = 3 here, whatever the configuration
   // _calculate_path_curvature :163-193
   std::vector<double> ue;
   Pts pts = spline_predict(fit, fit.max_u, &ue);
   int L = (int)pts.size();
+  prec(PR_N_DENSE, L);
+  if (!fit.null) {
+    const double dq = fit.max_u / predict_every;
+    prec(PR_DENSE_QUOTIENT, dq);
+    if (std::isfinite(dq)) margin(MG_PATH_DENSE_FRAC, dq - std::floor(dq) > 0.5 ? std::floor(dq) + 1.0 - dq : dq - std::floor(dq), 0.0);
+  }
   if (fit.null || L == 0) throw RefUndefined{FSDO_REF_UNDEFINED_PATH};
   int window = std::min(L / 5, 30);
   if (window % 2 == 0) window += 1;
+  prec(PR_WINDOW, window);
   std::vector<double> curv = path_curvature(pts, window);
   int fsize = std::max(2, window / 2);
   std::vector<double> filt = uniform_filter_nearest(curv, fsize);
@@ -246,6 +274,10 @@ static Pts connect_path_to_car(const Pts& path, Vec2 pos, Vec2 dir) {
   double d = norm2(pos.x - path[0].x, pos.y - path[0].y);
   double cx = path[0].x - pos.x, cy = path[0].y - pos.y;
   double ang = vec_angle_between(cx, cy, dir.x, dir.y);
+  prec(PR_CONNECT_DIST, d);
+  prec(PR_CONNECT_ANGLE, ang);
+  margin_rel(MG_PATH_CONNECT_DIST, d, 0.5);
+  margin_rel(MG_PATH_CONNECT_ANGLE, ang, PI / 2);
   if (d < 0.5 || ang > PI / 2) return path;
   double nrm = norm2(cx, cy);
   Vec2 np_{pos.x + (cx / nrm) * 0.2, pos.y + (cy / nrm) * 0.2};
@@ -259,9 +291,18 @@ static Pts connect_path_to_car(const Pts& path, Vec2 pos, Vec2 dir) {
 static Pts extend_path(const Pts& path, Vec2 pos, Vec2 dir, int* flags) {
   const int n = (int)path.size();
   std::vector<char> front(n, 0);
-  for (int i = 0; i < n; i++) front[i] = blas_dot2(path[i].x - pos.x, dir.x, path[i].y - pos.y, dir.y) > 0;
+  double dot_min = NAN;
+  for (int i = 0; i < n; i++) {
+    const double dot = blas_dot2(path[i].x - pos.x, dir.x, path[i].y - pos.y, dir.y);
+    front[i] = dot > 0;
+    margin(MG_PATH_FRONT_DOT, dot, 0.0);
+    if (!(std::fabs(dot_min) <= std::fabs(dot))) dot_min = dot;
+  }
+  prec(PR_FRONT_DOT, dot_min);
+  prec(PR_FIRST_FRONT, -1.0);
   for (int i = 0; i < n; i++)
     if (front[i]) {
+      prec(PR_FIRST_FRONT, i);
       for (int j = i; j < n; j++) front[j] = 1;
       break;
     }
@@ -269,15 +310,22 @@ static Pts extend_path(const Pts& path, Vec2 pos, Vec2 dir, int* flags) {
   Pts infront;
   for (int i = 0; i < n; i++)
     if (front[i]) infront.push_back(path[i]);
+  prec(PR_N_IN_FRONT, (double)infront.size());
   if (infront.empty()) return path;
   if (infront.size() < 2) throw RefUndefined{FSDO_REF_UNDEFINED_PATH};  // cumsum([])[-1] IndexError
   double plen = 0.0;
   for (size_t i = 0; i + 1 < infront.size(); i++)
     plen += norm2_axis(infront[i + 1].x - infront[i].x, infront[i + 1].y - infront[i].y);
+  prec(PR_PLEN, plen);
+  margin_rel(MG_PATH_PLEN, plen, MPC_PATH_LENGTH);
   if (plen > MPC_PATH_LENGTH) return path;
   Pts rel(infront.end() - std::min<size_t>(20, infront.size()), infront.end());
   double cx, cy, radius;
   circle_fit(rel, cx, cy, radius);
+  prec(PR_RADIUS, radius);
+  margin_rel(MG_PATH_RADIUS, radius, 10.0);
+  margin_rel(MG_PATH_RADIUS, radius, 80.0);
+  margin_rel(MG_PATH_RADIUS, radius, 100.0);
   double r_use = py_min(py_max(radius, 10), 100);
   Pts newp;
   if (r_use < 80) {
@@ -287,6 +335,7 @@ static Pts extend_path(const Pts& path, Vec2 pos, Vec2 dir, int* flags) {
     Vec2 t0{rel[i0].x - cx, rel[i0].y - cy}, t1{rel[i1].x - cx, rel[i1].y - cy}, t2{rel[i2].x - cx, rel[i2].y - cy};
     double hm[3][3] = {{1.0, t0.x, t0.y}, {1.0, t1.x, t1.y}, {1.0, t2.x, t2.y}};
     double sg = np_sign(det3_lu(hm));
+    prec(PR_ARC_SIGN, sg);
     double start = m_atan2(t0.y, t0.x);
     double end = start + sg * PI;
     // np.linspace(start, end) -> 50 points
@@ -317,14 +366,20 @@ static Pts extend_path(const Pts& path, Vec2 pos, Vec2 dir, int* flags) {
 // core_calculate_path.py:459-465 remove_path_behind_car
 static Pts remove_path_behind_car(const Pts& path, Vec2 pos) {
   int best = 0;
-  double bd = 0;
+  double bd = 0, second = INFINITY;
   for (size_t i = 0; i < path.size(); i++) {
     double d = norm2_axis(pos.x - path[i].x, pos.y - path[i].y);
     if (i == 0 || d < bd) {
+      if (i > 0) second = bd;
       bd = d;
       best = (int)i;
+    } else if (d < second) {
+      second = d;
     }
   }
+  prec(PR_TRIM_INDEX, best);
+  prec(PR_TRIM_GAP, second - bd);
+  if (path.size() > 1) margin_rel(MG_PATH_TRIM_ARGMIN, second, bd);
   return Pts(path.begin() + best, path.end());
 }
 
@@ -333,10 +388,13 @@ struct FourColPath {};  // marker: remove_path_not_in_prediction_horizon returne
 // core_calculate_path.py:380-417 do_all_mpc_parameter_calculations
 void do_all_mpc(const Pts& path_update, Vec2 pos, Vec2 dir, double out[][4], int* flags) {
   if (path_update.empty()) throw RefUndefined{FSDO_REF_UNDEFINED_PATH};
+  if (g_path_rec)  // (the MPC step's entries are those of its last run)
+    for (int i = PR_CONNECT_DIST; i <= PR_CURV_ZERO; i++) g_path_rec->v[i] = i == PR_CURV_ZERO ? 0.0 : NAN;
   Pts p1 = connect_path_to_car(path_update, pos, dir);
   Pts p2 = extend_path(p1, pos, dir, flags);
   Pts p3 = remove_path_behind_car(p2, pos);
   // refit_path_for_mpc_with_safety_factor :239-259
+  prec(PR_N_REFIT, (double)p3.size());
   Fitted fit = spline_fit(p3, SMOOTHING, PREDICT_EVERY, g_prm.max_deg);
   Pts p4 = spline_predict(fit, MPC_PATH_LENGTH * 1.5);
   // remove_path_not_in_prediction_horizon :467-499
@@ -347,10 +405,20 @@ void do_all_mpc(const Pts& path_update, Vec2 pos, Vec2 dir, double out[][4], int
     throw PyValueError{3};
   }
   std::vector<char> over(nseg);
-  double cum = 0.0;
+  double cum = 0.0, cum_before = 0.0;
+  bool seen = false;
   for (int i = 0; i < nseg; i++) {
+    const double last = cum;
     cum += norm2_axis(p4[i + 1].x - p4[i].x, p4[i + 1].y - p4[i].y);
     over[i] = cum > MPC_PATH_LENGTH;
+    if (over[i] && !seen) {
+      seen = true;
+      cum_before = last;
+      prec(PR_CUT_OVER, cum);
+      prec(PR_CUT_UNDER, cum_before);
+      margin_rel(MG_PATH_CUT, cum, MPC_PATH_LENGTH);
+      margin_rel(MG_PATH_CUT, cum_before, MPC_PATH_LENGTH);
+    }
   }
   int first = 0;
   bool found = false;
@@ -361,6 +429,7 @@ void do_all_mpc(const Pts& path_update, Vec2 pos, Vec2 dir, double out[][4], int
       break;
     }
   if (!found) first = nseg;
+  prec(PR_CUT_INDEX, first);
   Pts p5(p4.begin(), p4.begin() + first);
   parameterize_path(p5, out);
 }
@@ -384,9 +453,15 @@ static void build_default() {
     q.y *= np_sign(max_angle);
     chord[i] = q;
   }
+  PathRec* const rec = g_path_rec;  // (built inside the first frame that needs it: not that frame's decisions)
+  const bool margins_on = g_margins.on;
+  g_path_rec = nullptr;
+  g_margins.on = false;
   Fitted fit = spline_fit(chord, SMOOTHING, PREDICT_EVERY, g_prm.max_deg);
   Pts initial = spline_predict(fit, fit.max_u);
   parameterize_path(initial, g_default);
+  g_path_rec = rec;
+  g_margins.on = margins_on;
 }
 
 const double (*default_previous_path())[4] {
@@ -419,6 +494,21 @@ void calculate_path(const Pts& left_v, const Pts& right_v, const std::vector<int
     for (long i = 0; i < n; i++) {
       dist[i] = norm2_axis(pos.x - gp[i].x, pos.y - gp[i].y);  // np.linalg.norm(position - path, axis=1)
       if (dist[i] < dist[imin]) imin = i;                      // first smallest
+    }
+    if (g_path_rec || g_margins.on) {
+      double second = INFINITY, near30 = NAN;
+      long kept = 0;
+      for (long i = 0; i < n; i++) {
+        if (i != imin && dist[i] < second) second = dist[i];
+        if (!(std::fabs(near30 - 30) <= std::fabs(dist[i] - 30))) near30 = dist[i];
+        kept += dist[i] < 30;
+        margin_rel(MG_PATH_GLOBAL_30M, dist[i], 30.0);
+      }
+      if (n > 1) margin_rel(MG_PATH_GLOBAL_ARGMIN, second, dist[imin]);
+      prec(PR_GLOBAL_ARGMIN, (double)imin);
+      prec(PR_GLOBAL_GAP, second - dist[imin]);
+      prec(PR_GLOBAL_KEPT, (double)kept);
+      prec(PR_GLOBAL_30M, near30);
     }
     const long roll = -imin + n / 3;
     for (long k = 0; k < n; k++) {
@@ -459,6 +549,7 @@ void calculate_path(const Pts& left_v, const Pts& right_v, const std::vector<int
       out.fallback |= 1;
     }
   }
+  prec(PR_N_CENTER, (double)center.size());
   // fit_matches_as_spline :207-223
   Pts path_update;
   try {
@@ -482,6 +573,8 @@ void finish_path(Pts path_update, const Pts& prev_xy, Vec2 pos, Vec2 dir, PathOu
       double d = norm2_axis(pos.x - path_update[i].x, pos.y - path_update[i].y);
       if (i == 0 || d < md) md = d;
     }
+    prec(PR_TOO_FAR, md);
+    margin_rel(MG_PATH_TOO_FAR, md, MAX_DIST_VALID_PATH);
     if (md > MAX_DIST_VALID_PATH) {
       path_update = prev_xy;
       out.fallback |= 4;

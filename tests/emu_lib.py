@@ -133,15 +133,45 @@ def last_retries():
     return int(lib().emu_last_retries())
 
 
-def path(poses, matched, group=8):
+def path(poses, matched, group=8, prev_paths=None, global_path=None):
+    """prev_paths (n, PATH_POINTS, 4): every frame's previous path; global_path (m, 2): the context's.  None leaves what the caller set
+    with emu_set_prev_paths / emu_set_global_path as it is (nothing set: fresh planners, no global path)."""
     poses = np.ascontiguousarray(poses, np.float64)
     n = len(poses)
     assert lib().emu_sizeof_path_out() == PATH_DTYPE.itemsize
     out = np.zeros(n, PATH_DTYPE)
-    rc = lib().emu_path_g(ctypes.c_int(group), ctypes.c_int(n), _p(poses), ctypes.c_void_p(matched.ctypes.data),
-                          ctypes.c_void_p(out.ctypes.data))
+    prev = None if prev_paths is None else np.ascontiguousarray(prev_paths, np.float64)
+    assert prev is None or prev.shape == (n, PATH_POINTS, 4)
+    gp = None if global_path is None else np.ascontiguousarray(global_path, np.float64).reshape(-1, 2)
+    if prev is not None:
+        lib().emu_set_prev_paths(_p(prev))
+    if gp is not None:
+        lib().emu_set_global_path(_p(gp), ctypes.c_int(len(gp)))
+    try:
+        rc = lib().emu_path_g(ctypes.c_int(group), ctypes.c_int(n), _p(poses), ctypes.c_void_p(matched.ctypes.data),
+                              ctypes.c_void_p(out.ctypes.data))
+    finally:  # (only what this call set: a caller that set the emulator's previous or global path itself keeps it across calls)
+        if prev is not None:
+            lib().emu_set_prev_paths(None)
+        if gp is not None:
+            lib().emu_set_global_path(None, ctypes.c_int(0))
     assert rc == 0, f"no path kernel for group size {group}"
     return out
+
+
+FIT_TEST_KNOTS = 64  # knot_capacity<64>() of csrc/spline_device.h: knots fit_test_kernel's workspace keeps (status 204 beyond)
+
+
+def fit(trace, smoothing):
+    """fit_polyline<64> on one polyline (emu_fit / fit_test_kernel) -> (rc, k, n, knots (n,), cx (n,), cy (n,), ier, fp, max_u); rc 1
+    where splprep raises, 204 where the fit needs more than FIT_TEST_KNOTS knots.  Degree min(len - 1, 3)."""
+    trace = np.ascontiguousarray(trace, np.float64).reshape(-1, 2)
+    t, c = np.zeros(FIT_TEST_KNOTS), np.zeros(2 * FIT_TEST_KNOTS)
+    info, fp = np.zeros(4, np.int32), np.zeros(2)
+    lib().emu_fit(_p(trace), ctypes.c_int(len(trace)), ctypes.c_double(smoothing), _p(t), _p(c), _p(info, ctypes.c_int32), _p(fp))
+    rc, n, ier, k = (int(v) for v in info)
+    n = min(max(n, 0), FIT_TEST_KNOTS)
+    return rc, k, n, t[:n].copy(), c[:n].copy(), c[FIT_TEST_KNOTS : FIT_TEST_KNOTS + n].copy(), ier, float(fp[0]), float(fp[1])
 
 
 def default_path():

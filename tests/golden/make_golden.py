@@ -1033,3 +1033,45 @@ def sort_constructed_golden():
 
 if __name__ == "__main__" and "--sort-constructed-only" in sys.argv:
     sort_constructed_golden()
+
+
+def path_constructed_golden():
+    """The constructed inputs of the path stage (tests/path_support.py, families A-E: the canonical member of every case and of every
+    threshold pair, standard shapes) through the reference's CalculatePath stage class, a fresh object per frame, built with the
+    case's parameters and handed the case's previous path where it has one -> path_constructed.npz: the names, the exception's class
+    where the reference raises, and the path (distinct paths once).  Data only; the inputs are rebuilt from the names by the test."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import path_support as ps
+
+    refharness.load()
+    from fsd_path_planning.calculate_path.core_calculate_path import CalculatePath, PathCalculationInput
+
+    defaults = dict(smoothing=0.2, predict_every=0.1, max_deg=3, maximal_distance_for_valid_path=5, mpc_path_length=20, mpc_prediction_horizon=40)
+    cases = [c for fam in "ABCDE" for c in ps.everything()[fam][0] if ps.canonical(c)]
+    F = len(cases)
+    out = dict(names=np.array([c.name for c in cases]), ok=np.zeros(F, bool), exc=np.array([""] * F, dtype="U24"), path=np.full((F, 40, 4), np.nan))
+    assert len(set(out["names"].tolist())) == F
+    for k, c in enumerate(cases):
+        stage = CalculatePath(**{**defaults, **c.prm})
+        if c.prev is not None:
+            stage.previous_paths = [np.array(c.prev)]
+        stage.set_new_input(PathCalculationInput(c.lv, c.rv, c.l2r.astype(np.int64), c.r2l.astype(np.int64), c.pose[:2], c.pose[2:], c.gpath))
+        try:
+            with np.errstate(all="ignore"):
+                path, _centers = stage.run_path_calculation()
+        except Exception as e:  # noqa: BLE001 (which class is part of the fixture)
+            out["exc"][k] = type(e).__name__
+            continue
+        out["ok"][k] = True
+        out["path"][k, : len(path)] = path
+    # cases that share their centre points share their path: each distinct path once (paths), and which one a frame has (path_of)
+    # (and of each path the rows `rows`: every second one and the last — the fixture's size; a decision that flips moves every row)
+    out["rows"] = np.unique(np.concatenate([np.arange(0, 40, 2), [39]]))  # (all 40 rows of all cases: 181 KB)
+    uniq, inverse = np.unique(out.pop("path")[:, out["rows"]].reshape(F, -1), axis=0, return_inverse=True, equal_nan=True)
+    out["paths"], out["path_of"] = uniq.reshape(-1, len(out["rows"]), 4), inverse.astype(np.int32).reshape(F)
+    np.savez_compressed(HERE / "path_constructed.npz", **out)
+    print("path_constructed frames", F, "distinct paths", len(uniq), "ok", int(out["ok"].sum()), "exc", sorted(set(out["exc"].tolist()) - {""}))
+
+
+if __name__ == "__main__" and "--path-constructed-only" in sys.argv:
+    path_constructed_golden()

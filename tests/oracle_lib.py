@@ -165,11 +165,13 @@ def sort_frame(xyt: np.ndarray, pose: np.ndarray) -> np.ndarray:
 
 
 MARGIN_CLASSES = ("start_bearing", "second_side", "abs_angle", "dir_angle", "sign_flip", "acos_thresholds", "wrong_direction", "cost_argmin",
-                  "combine", "arithmetic")  # oracle/oracle_internal.h MarginClass, in order
+                  "combine", "arithmetic", "path_too_far", "path_connect_dist", "path_connect_angle", "path_front_dot", "path_plen", "path_radius",
+                  "path_trim_argmin", "path_cut", "path_skip_frac", "path_dense_frac", "path_curv_clamp", "path_global_30m",
+                  "path_global_argmin")  # oracle/oracle_internal.h MarginClass, in order
 
 
 class margins:
-    """with oracle_lib.margins() as m: ... ; m.min["dir_angle"] — the sorting stage's decision margins (oracle_internal.h MarginRec)
+    """with oracle_lib.margins() as m: ... ; m.min["dir_angle"] — the sorting and the path stage's decision margins (oracle_internal.h MarginRec)
     of the calls made inside: per class the smallest non-zero |value - threshold| (1e300: none) and, in m.zero, how often the value was
     the threshold bit for bit.  The recorder is process-wide and single-threaded: no n_threads > 1 inside."""
 
@@ -180,7 +182,7 @@ class margins:
 
     def __exit__(self, *a):
         out = np.zeros(6 * len(MARGIN_CLASSES))
-        lib().fsdo_margins_get(_p(out))
+        lib().fsdo_margins_get_n(_p(out), ctypes.c_int(len(MARGIN_CLASSES)))
         lib().fsdo_margins_enable(ctypes.c_int(0))
         for i, name in enumerate(MARGIN_CLASSES):
             self.min[name], self.n[name], self.zero[name] = float(out[6 * i]), int(out[6 * i + 1]), int(out[6 * i + 5])
@@ -197,9 +199,21 @@ def match(left, right, pose) -> np.ndarray:
     return out[0]
 
 
-def path(left_v, right_v, l2r, r2l, pose) -> np.ndarray:
-    """The path stage alone (fsdo_path) on a match stage's lists with virtual cones and their matches -> a record whose
-    path, path_fallback and status are set (a fresh planner: the default previous path)."""
+# oracle/oracle_internal.h PathRecField, in order: what the path stage decided on a frame, value by value (NaN: not reached)
+PATH_RECORD = ("n_center", "too_far", "connect_dist", "connect_angle", "first_front", "front_dot", "n_in_front", "plen", "radius", "arc_sign",
+               "trim_index", "trim_gap", "n_refit", "cut_index", "cut_over", "cut_under", "skip_quotient", "skip", "n_skipped", "dense_quotient",
+               "n_dense", "window", "radius_min", "radius_max", "curv_zero", "global_argmin", "global_gap", "global_kept", "global_30m")
+PATH_RECORD_FITS = 6
+# oracle/fitpack.h FitBranch, bit by bit
+FIT_BRANCHES = ("polynomial", "interpolant", "accept_at_once", "part2", "rational", "ier1", "ier2", "ier3", "nplus_ratio", "nplus_double",
+                "nplus_min", "nplus_max", "ich1", "ich3", "no_ich", "single_point", "knot_tie")
+
+
+def path(left_v, right_v, l2r, r2l, pose, prev=None, global_path=None, record=False):
+    """The path stage alone (fsdo_path_full) on a match stage's lists with virtual cones and their matches -> a record whose
+    path, path_fallback and status are set.  prev: the planner's previous path (PATH_POINTS, 4) (None: a fresh planner, the
+    default one); global_path (n, 2): PathPlanner.global_path.  record=True: -> (record, dict of PATH_RECORD values plus
+    "fit_branches" / "fit_ier" / "fit_knots" (one entry per fit, in call order) and "n_fits")."""
     left_v = np.ascontiguousarray(left_v, dtype=np.float64).reshape(-1, 2)
     right_v = np.ascontiguousarray(right_v, dtype=np.float64).reshape(-1, 2)
     l2r = np.ascontiguousarray(l2r, dtype=np.int32)
@@ -207,9 +221,25 @@ def path(left_v, right_v, l2r, r2l, pose) -> np.ndarray:
     pose = np.ascontiguousarray(pose, dtype=np.float64)
     assert len(l2r) == len(left_v) <= MAX_MATCH and len(r2l) == len(right_v) <= MAX_MATCH and pose.size == 4
     out = np.zeros(1, dtype=RESULT_DTYPE)
-    lib().fsdo_path(_p(left_v), ctypes.c_int(len(left_v)), _p(right_v), ctypes.c_int(len(right_v)), _p(l2r, ctypes.c_int32),
-                    _p(r2l, ctypes.c_int32), _p(pose), ctypes.c_void_p(out.ctypes.data))
-    return out[0]
+    pp = None if prev is None else np.ascontiguousarray(prev, dtype=np.float64)
+    assert pp is None or pp.shape == (PATH_POINTS, 4)
+    gp = None if global_path is None else np.ascontiguousarray(global_path, dtype=np.float64).reshape(-1, 2)
+    nrec = len(PATH_RECORD) + 3 * PATH_RECORD_FITS + 1
+    assert lib().fsdo_path_record_fields() == nrec
+    rec = np.full(nrec, np.nan)
+    lib().fsdo_path_full(_p(left_v), ctypes.c_int(len(left_v)), _p(right_v), ctypes.c_int(len(right_v)), _p(l2r, ctypes.c_int32),
+                    _p(r2l, ctypes.c_int32), _p(pose), ctypes.c_void_p(out.ctypes.data), None if pp is None else _p(pp),
+                    None if gp is None else _p(gp), ctypes.c_int(0 if gp is None else len(gp)), _p(rec) if record else None)
+    if not record:
+        return out[0]
+    d = {k: float(rec[i]) for i, k in enumerate(PATH_RECORD)}
+    nf = int(rec[-1])
+    b = len(PATH_RECORD)
+    d["n_fits"] = nf
+    d["fit_branches"] = [int(rec[b + i]) for i in range(min(nf, PATH_RECORD_FITS))]
+    d["fit_ier"] = [int(rec[b + PATH_RECORD_FITS + i]) for i in range(min(nf, PATH_RECORD_FITS))]
+    d["fit_knots"] = [int(rec[b + 2 * PATH_RECORD_FITS + i]) for i in range(min(nf, PATH_RECORD_FITS))]
+    return out[0], d
 
 
 def default_path() -> np.ndarray:
@@ -248,6 +278,15 @@ def splprep(trace: np.ndarray, s: float, k: int):
         ctypes.byref(n), ctypes.byref(ier), ctypes.byref(fp),
     )
     return rc, u, t[: n.value], cx[: n.value], cy[: n.value], ier.value, fp.value
+
+
+def splprep_branches(trace: np.ndarray, s: float, k: int) -> int:
+    """The ways parcur_fit takes on this polyline (FIT_BRANCHES bits); -1 where splprep raises."""
+    trace = np.ascontiguousarray(trace, dtype=np.float64)
+    u = np.concatenate(([0.0], np.cumsum(np.linalg.norm(np.diff(trace, axis=0), axis=1))))
+    lib().fsdo_splprep_branches.restype = ctypes.c_long
+    return int(lib().fsdo_splprep_branches(_p(u), _p(np.ascontiguousarray(trace[:, 0])), _p(np.ascontiguousarray(trace[:, 1])),
+                                           ctypes.c_int(len(trace)), ctypes.c_int(k), ctypes.c_double(s)))
 
 
 def splev(t, cx, cy, k, u_eval):

@@ -249,3 +249,39 @@ def test_oracle_matches_reference_on_constructed_sorting_frames(golden_dir, mode
             if g[f"n_configs_{s}"][k] > 0:
                 a, b = float(r[f"best_cost_{s}"]), float(g[f"best_cost_{s}"][k])
                 assert abs(a - b) <= 1e-9 * max(1.0, abs(b)), (name, s, a, b)  # (the bar of parity.compare_frame)
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["libm", "detmath"])
+def test_oracle_matches_reference_on_constructed_path_inputs(golden_dir, mode):
+    """tests/path_support.py's canonical cases of families A-E (every branch of the path stage, both members of every threshold pair)
+    through the reference's CalculatePath (make_golden.py path_constructed_golden): the oracle raises where the reference raises,
+    with the status the case was built for, and gives its path elsewhere, within the 1e-5 this file holds paths to (the arc
+    extension's libm values; 0 is expected outside arc frames and printed).  The cases are rebuilt from their names: none may be missing."""
+    import path_support as ps
+
+    g = np.load(golden_dir / "path_constructed.npz")
+    cases = {c.name: c for fam in "ABCDE" for c in ps.everything()[fam][0]}
+    canonical = {n for n, c in cases.items() if ps.canonical(c)}
+    assert len(g["names"]) >= 250 and set(g["names"].tolist()) == canonical, sorted(canonical ^ set(g["names"].tolist()))[:5]  # none unpinned
+    rows = g["rows"]
+    worst = worst_plain = 0.0
+    for k, name in enumerate(g["names"]):
+        c = cases[name]
+        with oracle_lib.params(c.prm), oracle_lib.math_mode(mode):
+            r = oracle_lib.path(c.lv, c.rv, c.l2r, c.r2l, c.pose, prev=ps._pad_prev(oracle_lib, c.prev), global_path=c.gpath)
+        if not g["ok"][k]:
+            # (IndexError: a match index outside the other side, 104 — family A — or cumsum([])[-1] of a single point in front, 103)
+            assert r["status"] == (104 if g["exc"][k] == "IndexError" and name.startswith("A/") else 103), (name, int(r["status"]), str(g["exc"][k]))
+            assert c.expect in (None, int(r["status"])), (name, c.expect)
+            continue
+        assert r["status"] == 0 and c.expect in (None, 0), (name, int(r["status"]), c.expect)
+        want = g["paths"][g["path_of"][k]]
+        h = int(c.prm.get("mpc_prediction_horizon", 40))
+        got = r["path"][rows]
+        assert np.array_equal(np.isnan(got), np.isnan(want)) and np.isnan(r["path"][h:]).all(), name  # (an exactly straight path: NaN curvature, in both)
+        err = float(np.nan_to_num(np.abs(got - want)).max())
+        assert err <= 1e-5, (name, err)
+        worst = max(worst, err)
+        if not int(r["path_fallback"]) & parity.ARC_FLAG:
+            worst_plain = max(worst_plain, err)
+    print(f"constructed path inputs, mode {mode}: {int(g['ok'].sum())} paths, max |oracle - reference| = {worst:.3e} ({worst_plain:.3e} outside arc frames)")
