@@ -349,6 +349,8 @@ __device__ __forceinline__ double wave_uniform(double v) {
 
 // argmin over (value, index) pairs with "first smallest" semantics (lowest index on ties);
 // lanes holding no candidate pass idx = -1.
+// (skid_reloc_kernel's 20-nearest selection depends on the tie rule: it walks the cones in (distance, index) order, and a tie
+// that went to the higher index would leave the lower one behind for good — a later round would then find no candidate.)
 __device__ __forceinline__ void wave_argmin(double& v, int& idx) {
   for (int off = 32; off >= 1; off >>= 1) {
     double ov = __shfl_xor(v, off, WAVE);

@@ -196,28 +196,43 @@ __global__ void __launch_bounds__(64) skid_reloc_kernel(int n_inst, const int32_
   // ---- 20 closest cones, in argsort order (stable) ----
   const int m = n < SKID_NEAR ? n : SKID_NEAR;
   {
-    // distances into the arena (n may exceed 64); repeated wave arg-min with the taken ones masked by +inf
-    for (int i = lane; i < n; i += WAVE) A.u[i] = norm_axis(cones[3 * i] - px, cones[3 * i + 1] - py);
-    __syncthreads();
+    // np.argsort order: distances that are not NaN ascending (+inf among them), the lowest index first among equal ones,
+    // then the NaN distances in index order.  Round k takes the smallest (NaN?, distance, index) key behind the key of
+    // round k - 1; the distances are formed again in every round (the same bits each time), so the selection keeps
+    // nothing per cone: no scratch whose size depends on n, no mark for a taken cone.  n >= m cones leave a candidate
+    // in every round.
+    bool have_last = false, last_nan = false;
+    double last_d = 0.0;
+    int last_i = -1;
     for (int k = 0; k < m; k++) {
       double bv = 0.0;
-      int bi = -1;
+      int bi = -1;            // best candidate of this lane whose distance is not NaN
+      int bn = 0x7fffffff;    // lowest candidate index of this lane whose distance is NaN
       for (int i = lane; i < n; i += WAVE) {
-        double d = A.u[i];
-        if (d >= 0 && (bi < 0 || d < bv)) {  // taken entries are marked negative
-          bv = d;
-          bi = i;
+        const double d = norm_axis(cones[3 * i] - px, cones[3 * i + 1] - py);
+        if (d != d) {
+          if ((!have_last || !last_nan || i > last_i) && i < bn) bn = i;
+        } else if (!have_last || (!last_nan && (d > last_d || (d == last_d && i > last_i)))) {
+          if (bi < 0 || d < bv) {
+            bv = d;
+            bi = i;
+          }
         }
       }
       wave_argmin(bv, bi);
-      __syncthreads();
+      bn = wave_min_int(bn);
+      const bool take_nan = bi < 0;
+      const int pick = take_nan ? bn : bi;  // (wave-uniform; 0 <= pick < n)
+      have_last = true;
+      last_nan = take_nan;
+      last_d = bv;
+      last_i = pick;
       if (lane == 0) {
-        S.nx[k] = cones[3 * bi];
-        S.ny[k] = cones[3 * bi + 1];
-        A.u[bi] = -1.0;
+        S.nx[k] = cones[3 * pick];
+        S.ny[k] = cones[3 * pick + 1];
       }
-      __syncthreads();
     }
+    __syncthreads();
   }
   // ---- circle_fit_powerset: every 3-subset, one per lane, accepted centres compacted in subset order ----
   const int n_sub = (m >= 3) ? m * (m - 1) * (m - 2) / 6 : 0;
@@ -285,7 +300,7 @@ __global__ void __launch_bounds__(64) skid_reloc_kernel(int n_inst, const int32_
   if (n_centers < 3) return;
   // ---- DBSCAN(eps = 3, min_samples = 1): connected components by min-label propagation; label = smallest member index ----
   const int C = n_centers;
-  int32_t* label = (int32_t*)A.u;  // the distance scratch is dead
+  int32_t* label = (int32_t*)A.u;  // C <= C(20,3) = 1140 labels; the centres fill A.x / A.y up to the same count (< PATH_CAP)
   for (int i = lane; i < C; i += WAVE) label[i] = i;
   __syncthreads();
   for (int iter = 0; iter < C; iter++) {

@@ -586,7 +586,12 @@ int fsdp_skidpad_set_tables(fsdp_ctx* ctx, const double* table_xy, int n_table, 
 int fsdp_skidpad_constants(fsdp_ctx* ctx, double* out5);
 /* (re)create n_instances fresh planners (PathPlanner.__init__ / "reset = construct a new object", README.md:153-154) */
 int fsdp_skidpad_reset(fsdp_ctx* ctx, int n_instances);
-/* one frame for every instance; results[i].path is in the caller's (original) frame like the reference's return value */
+/* one frame for every instance; results[i].path is in the caller's (original) frame like the reference's return value.
+ * Cones per instance: any number (cone_offsets is the only bound).  The relocalization takes the 20 nearest in np.argsort
+ * order — distances that are not NaN ascending, the lower index first among equal ones, then NaN distances in index order —
+ * and keeps nothing per cone: no workspace grows with the count, and an instance's result does not depend on the cones of
+ * the instances around it.  Coordinates and poses that are not finite are input like any other (the reference's arithmetic
+ * on them is followed; a position that is not finite fails the step with 103). */
 int fsdp_skidpad_step(fsdp_ctx* ctx, int n_instances, const int32_t* cone_offsets, const double* cones_xyt,
                       const double* poses, fsdp_frame_result* results, fsdp_skidpad_info* info);
 /* The same as a ticket (fsdp_collect / fsdp_ticket_done as above; one ticket per pass slot, fsdp_set_overlap).  A replay

@@ -154,6 +154,39 @@ static inline void prec(int field, double value) {
   if (g_path_rec) g_path_rec->v[field] = value;
 }
 
+// What a skidpad step decided (skidpad.cpp relocalize / skidpad_step), value by value; NaN: not reached.  Kept per planner,
+// overwritten by every step, read through fsdo_skidpad_record.  A "margin" is the signed distance of a value to its
+// threshold, positive on the accepting side; over many subsets / pairs the one of smallest magnitude is kept.
+constexpr int SKR_MAX_SIZES = 16;
+enum SkidRecField {
+  SKR_ATTEMPT = 0,      // 1: the step attempted a relocalization
+  SKR_SUCCESS,          // ... and it succeeded
+  SKR_M,                // cones selected, min(n, 20)
+  SKR_SELECT_GAP,       // distance of the 21st nearest cone - that of the 20th (n > 20)
+  SKR_N_ACCEPTED,       // subsets accepted by circle_fit_powerset
+  SKR_RADIUS_MARGIN,    // 1 - |radius - 7.625|
+  SKR_SPACING_MARGIN,   // 1.5 - |mean nearest distance - 2.4|
+  SKR_RESIDUAL_MARGIN,  // 0.4 - residual
+  SKR_N_CENTERS,
+  SKR_EPS_MARGIN,       // 3 - distance of a pair of centres
+  SKR_N_CLUSTERS,
+  SKR_CLUSTER_SIZE0,    // sizes of the first SKR_MAX_SIZES clusters, in label order
+  SKR_BEST_DISTANCE = SKR_CLUSTER_SIZE0 + SKR_MAX_SIZES,  // |18.25 - d| of the chosen pair
+  SKR_RUNNER_UP,        // the next smallest one (inf: one pair only)
+  SKR_PAIR_A,           // labels of the chosen pair
+  SKR_PAIR_B,
+  SKR_SIDE0,            // v.y of the two centres in the latched car frame
+  SKR_SIDE1,
+  SKR_LO,               // window of the known path: [lo, hi)
+  SKR_HI,
+  SKR_ARGMIN,           // its closest point
+  SKR_ARGMIN_GAP,       // second smallest distance - smallest (0: a bit-equal tie)
+  SKR_N1,               // points of the path update
+  SKR_MEDIAN_SPLIT0,    // per cluster (the first SKR_MAX_SIZES): 1 if the members that hold the x median (the middle one, or the
+                        // middle two of an even size) are not the members that hold the y median, 0 if they are the same
+  SKR_COUNT = SKR_MEDIAN_SPLIT0 + SKR_MAX_SIZES
+};
+
 // sorting.cpp
 SideResult configs_for_one_side(const Frame& f, int cone_type);
 void sort_frame(const Frame& f, std::vector<int>& left, std::vector<int>& right, SideResult* l = nullptr,

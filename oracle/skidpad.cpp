@@ -26,7 +26,14 @@ struct SkidpadPlanner {
   double rotation = 0.0;
   int index_along_path = 0;
   double prev[FSDO_PATH_POINTS][4];
+  double rec[SKR_COUNT];  // what the last step decided, value by value (NaN: not reached)
 };
+
+// the entry of rec whose |value| is smallest so far (a signed distance to a threshold: positive on the accepting side)
+static void rec_nearest(double& slot, double margin) {
+  if (std::isnan(margin)) return;
+  if (std::isnan(slot) || std::fabs(margin) < std::fabs(slot)) slot = margin;
+}
 
 static Vec2 rot_point(double theta_cos, double theta_sin, double x, double y) {
   return Vec2{blas_dot2(x, theta_cos, y, -theta_sin), blas_dot2(x, theta_sin, y, theta_cos)};
@@ -43,6 +50,10 @@ static bool relocalize(SkidpadPlanner& P, const double* xyt, int n, Vec2 pos) {
   for (int i = 0; i < n; i++) dist[i] = norm2_axis(xyt[3 * i] - pos.x, xyt[3 * i + 1] - pos.y);
   std::vector<int> order = argsort(dist);
   int m = std::min(n, 20);
+  P.rec[SKR_ATTEMPT] = 1.0;
+  P.rec[SKR_M] = m;
+  if (n > 20) P.rec[SKR_SELECT_GAP] = dist[order[20]] - dist[order[19]];
+  P.rec[SKR_N_ACCEPTED] = 0.0;
   Pts pts(m);
   for (int i = 0; i < m; i++) pts[i] = Vec2{xyt[3 * order[i]], xyt[3 * order[i] + 1]};
   // circle_fit_powerset :31-64 (only 3-subsets are ever enumerated: the loop variable shadows `idxs`)
@@ -82,9 +93,13 @@ static bool relocalize(SkidpadPlanner& P, const double* xyt, int n, Vec2 pos) {
           double res[3];
           for (int r = 0; r < 3; r++) res[r] = std::fabs(norm2_axis(cx - q[r].x, cy - q[r].y) - rad);
           double residual = np_sum(res, 3) / 3.0;
+          rec_nearest(P.rec[SKR_RADIUS_MARGIN], 1.0 - std::fabs(rad - 7.625));
+          rec_nearest(P.rec[SKR_SPACING_MARGIN], 1.5 - std::fabs(mean_distance - 2.4));
+          rec_nearest(P.rec[SKR_RESIDUAL_MARGIN], 0.4 - residual);
           if (std::fabs(rad - 7.625) < 1.0 && std::fabs(mean_distance - 2.4) < 1.5 && residual < 0.4) centers.push_back(Vec2{cx, cy});
         }
   }
+  P.rec[SKR_N_ACCEPTED] = P.rec[SKR_N_CENTERS] = (double)centers.size();
   if (centers.size() < 3) return false;
   // calculate_circle_centers :67-98 — DBSCAN(eps=3, min_samples=1) = connected components of the <= 3 m graph,
   // labels numbered by first occurrence
@@ -109,6 +124,27 @@ static bool relocalize(SkidpadPlanner& P, const double* xyt, int n, Vec2 pos) {
     }
     n_labels++;
   }
+  for (int i = 0; i < C; i++)
+    for (int j = i + 1; j < C; j++) {
+      double dx = centers[i].x - centers[j].x, dy = centers[i].y - centers[j].y;
+      rec_nearest(P.rec[SKR_EPS_MARGIN], 3.0 - std::sqrt(dx * dx + dy * dy));
+    }
+  P.rec[SKR_N_CLUSTERS] = n_labels;
+  for (int l = 0; l < n_labels && l < SKR_MAX_SIZES; l++) {
+    P.rec[SKR_CLUSTER_SIZE0 + l] = (double)std::count(label.begin(), label.end(), l);
+    // who holds the medians: members ordered by x and by y (index on ties, as the kernel's rank counting)
+    std::vector<int> bx, by;
+    for (int i = 0; i < C; i++)
+      if (label[i] == l) bx.push_back(i);
+    by = bx;
+    std::stable_sort(bx.begin(), bx.end(), [&](int a, int b) { return centers[a].x < centers[b].x; });
+    std::stable_sort(by.begin(), by.end(), [&](int a, int b) { return centers[a].y < centers[b].y; });
+    const size_t k = bx.size(), lo = (k % 2 == 1) ? k / 2 : k / 2 - 1, hi = k / 2;
+    std::vector<int> hx{bx[lo], bx[hi]}, hy{by[lo], by[hi]};
+    std::sort(hx.begin(), hx.end());
+    std::sort(hy.begin(), hy.end());
+    P.rec[SKR_MEDIAN_SPLIT0 + l] = hx == hy ? 0.0 : 1.0;
+  }
   if (!(n_labels > 1)) return false;  // AssertionError
   auto median_of = [&](int lab) {
     std::vector<double> xs, ys;
@@ -128,16 +164,24 @@ static bool relocalize(SkidpadPlanner& P, const double* xyt, int n, Vec2 pos) {
   };
   double best_distance = 1000;
   Vec2 bc0{0, 0}, bc1{0, 0};
+  double runner_up = INFINITY;
   for (int l1 = 0; l1 < n_labels; l1++)
     for (int l2 = l1 + 1; l2 < n_labels; l2++) {
       Vec2 c0 = median_of(l1), c1 = median_of(l2);
       double d = std::fabs(18.25 - norm2(c0.x - c1.x, c0.y - c1.y));
       if (d < best_distance) {
+        if (best_distance < 1000) runner_up = best_distance;
         best_distance = d;
         bc0 = c0;
         bc1 = c1;
+        P.rec[SKR_PAIR_A] = l1;
+        P.rec[SKR_PAIR_B] = l2;
+      } else if (d < runner_up || std::isnan(d)) {
+        runner_up = d;
       }
     }
+  P.rec[SKR_BEST_DISTANCE] = best_distance;
+  P.rec[SKR_RUNNER_UP] = runner_up;
   if (best_distance > 0.5) return false;  // ValueError
   // calculate_transformation :101-169 (uses the pose latched at the FIRST attempt)
   double yaw0 = m_atan2(P.orig_dir.y, P.orig_dir.x);
@@ -147,6 +191,7 @@ static bool relocalize(SkidpadPlanner& P, const double* xyt, int n, Vec2 pos) {
   for (int i = 0; i < 2; i++) {
     Vec2 v = rot_point(c, s, cc[i].x - P.orig_pos.x, cc[i].y - P.orig_pos.y);
     is_right[i] = v.y < 0.0;
+    P.rec[SKR_SIDE0 + i] = v.y;
   }
   int ir = -1, il = -1;
   for (int i = 0; i < 2; i++) {
@@ -166,6 +211,8 @@ static bool relocalize(SkidpadPlanner& P, const double* xyt, int n, Vec2 pos) {
 
 static void skidpad_step(SkidpadPlanner& P, const double* xyt, int n, const double* pose, fsdo_frame_result* o, double* info) {
   Vec2 pos{pose[0], pose[1]}, dir{pose[2], pose[3]};
+  for (double& v : P.rec) v = NAN;
+  P.rec[SKR_ATTEMPT] = 0.0;
   // Relocalizer.attempt_relocalization_calculation (relocalization_base_class.py:50-75)
   if (!P.relocalized) {
     if (!P.has_original) {
@@ -176,7 +223,7 @@ static void skidpad_step(SkidpadPlanner& P, const double* xyt, int n, const doub
     if (n == 0) {
       // np.row_stack of five empty (0,2) arrays works; argsort of empty -> no subsets -> < 3 circles
     }
-    relocalize(P, xyt, n, pos);
+    P.rec[SKR_SUCCESS] = relocalize(P, xyt, n, pos) ? 1.0 : 0.0;
   }
   Pts path_update;
   if (P.relocalized) {
@@ -205,10 +252,20 @@ static void skidpad_step(SkidpadPlanner& P, const double* xyt, int n, const doub
         best = i;
       }
     }
+    P.rec[SKR_LO] = min_index;
+    P.rec[SKR_HI] = max_index;
+    if (max_index > min_index) {
+      P.rec[SKR_ARGMIN] = best;
+      double second = INFINITY;
+      for (int i = min_index; i < max_index; i++)
+        if (i != best) second = std::min(second, norm2_axis(pos.x - g[i].x, pos.y - g[i].y));
+      P.rec[SKR_ARGMIN_GAP] = second - bd;
+    }
     if (max_index <= min_index) throw RefUndefined{FSDO_REF_UNDEFINED_PATH};  // argmin of empty
     P.index_along_path = best;
     int final_index = std::min(best + (int)(25 / mean_distance), (int)g.size());
     path_update.assign(g.begin() + best, g.begin() + final_index);
+    P.rec[SKR_N1] = final_index - best;
   } else {
     // calculate_trivial_path (core_calculate_path.py:127-134): chord[1:] rotated by the car yaw + position
     Pts chord = almost_straight_path();
@@ -281,6 +338,7 @@ void* fsdo_skidpad_create(const double* table_xy, int n_table, const double* noi
   circle_fit(posy, cx, cy, r);
   P->ref_left = Vec2{cx, cy};
   std::memcpy(P->prev, default_previous_path(), sizeof(P->prev));
+  for (double& v : P->rec) v = NAN;
   return P;
 }
 
@@ -312,6 +370,13 @@ void fsdo_skidpad_transform(void* h, double* out5) {
   out5[2] = P->rotation;
   out5[3] = P->right_calc.x;
   out5[4] = P->right_calc.y;
+}
+
+// the decision record of the last step (oracle_internal.h SkidRecField): the first n of SKR_COUNT values; returns SKR_COUNT
+int fsdo_skidpad_record(void* h, double* out, int n) {
+  SkidpadPlanner* P = (SkidpadPlanner*)h;
+  for (int i = 0; i < n && i < SKR_COUNT; i++) out[i] = P->rec[i];
+  return SKR_COUNT;
 }
 
 void fsdo_skidpad_reference_centers(void* h, double* out4) {

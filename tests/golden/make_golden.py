@@ -1075,3 +1075,50 @@ def path_constructed_golden():
 
 if __name__ == "__main__" and "--path-constructed-only" in sys.argv:
     path_constructed_golden()
+
+
+def skidpad_constructed_golden():
+    """The constructed inputs of the skidpad stage (tests/skidpad_constructed_support.py, families A-F: every case and both members of
+    every threshold pair in the canonical frame), each through a reference PathPlanner(MissionTypes.skidpad) of its own, step by step,
+    exceptions caught the way a caller would -> skidpad_constructed.npz: the names, the inputs (cones as CSR over (case, step), poses),
+    per step the exception's class where the reference raises, the path, relocalized, the relocalization information and
+    index_along_path as the planner holds it after the step.  Data only."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import skidpad_constructed_support as sc
+
+    m = refharness.load()
+    cases = [c for c in sc.build()[0] if c.frame == "canonical"]
+    steps = [(k, s) for k, c in enumerate(cases) for s in range(c.n_steps)]
+    F = len(steps)
+    out = dict(names=np.array([c.name for c in cases]), case_of=np.array([k for k, _ in steps], np.int32), step_of=np.array([s for _, s in steps], np.int32),
+               ok=np.zeros(F, bool), exc=np.array([""] * F, dtype="U24"), path=np.full((F, 40, 4), np.nan), relocalized=np.zeros(F, bool),
+               info=np.full((F, 3), np.nan), index_along_path=np.zeros(F, np.int32), poses=np.zeros((F, 4)))
+    cones, off = [], [0]
+    f = 0
+    for c in cases:
+        pp = m["PathPlanner"](m["MissionTypes"].skidpad)
+        for xyt, pose in c.steps:
+            by_type = [xyt[:, :2].copy()] + [np.zeros((0, 2)) for _ in range(4)]
+            try:
+                with np.errstate(all="ignore"):
+                    out["path"][f] = pp.calculate_path_in_global_frame(by_type, pose[:2].copy(), pose[2:].copy())
+                out["ok"][f] = True
+            except Exception as e:  # noqa: BLE001 (which class is part of the fixture)
+                out["exc"][f] = type(e).__name__
+            ri = pp.relocalization_info
+            out["relocalized"][f] = ri is not None
+            if ri is not None:
+                out["info"][f] = [ri.translation[0], ri.translation[1], ri.rotation]
+            out["index_along_path"][f] = pp.pathing.index_along_path
+            out["poses"][f] = pose
+            cones.append(xyt)
+            off.append(off[-1] + len(xyt))
+            f += 1
+    out["offsets"], out["cones"] = np.array(off, np.int32), np.concatenate(cones)
+    np.savez_compressed(HERE / "skidpad_constructed.npz", **out)
+    print("skidpad_constructed cases", len(cases), "steps", F, "ok", int(out["ok"].sum()), "exc", sorted(set(out["exc"].tolist()) - {""}),
+          "relocalized", int(out["relocalized"].sum()))
+
+
+if __name__ == "__main__" and "--skidpad-constructed-only" in sys.argv:
+    skidpad_constructed_golden()

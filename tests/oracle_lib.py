@@ -300,6 +300,14 @@ def splev(t, cx, cy, k, u_eval):
     return np.column_stack([ox, oy])
 
 
+SKID_RECORD_SIZES = 16
+# oracle/oracle_internal.h SkidRecField, in order
+SKID_RECORD = (("attempt", "success", "m", "select_gap", "n_accepted", "radius_margin", "spacing_margin", "residual_margin", "n_centers",
+                "eps_margin", "n_clusters") + tuple(f"cluster_size_{i}" for i in range(SKID_RECORD_SIZES))
+               + ("best_distance", "runner_up", "pair_a", "pair_b", "side0", "side1", "lo", "hi", "argmin", "argmin_gap", "n1")
+               + tuple(f"median_split_{i}" for i in range(SKID_RECORD_SIZES)))
+
+
 class SkidpadPlanner:
     """Stateful skidpad-mission oracle (oracle/skidpad.cpp).  table: BASE_SKIDPAD_PATH (n,2); noise: RandomState(42).randn(1140,3,2)."""
 
@@ -317,6 +325,30 @@ class SkidpadPlanner:
         info = np.zeros(5)
         lib().fsdo_skidpad_step(self._h, _p(xyt), ctypes.c_int(len(xyt)), _p(pose), ctypes.c_void_p(out.ctypes.data), _p(info))
         return out[0], info
+
+    def index(self):
+        """index_along_path as the planner holds it (a step that raised reports nothing, but may have moved it)"""
+        lib().fsdo_skidpad_index.restype = ctypes.c_int
+        return int(lib().fsdo_skidpad_index(self._h))
+
+    def transform(self):
+        """translation x, y, rotation, calculated right centre x, y"""
+        out = np.zeros(5)
+        lib().fsdo_skidpad_transform(self._h, _p(out))
+        return out
+
+    def record(self):
+        """What the last step decided (oracle/oracle_internal.h SkidRecField) as a dict; NaN: not reached."""
+        out = np.full(len(SKID_RECORD), np.nan)
+        lib().fsdo_skidpad_record.restype = ctypes.c_int
+        assert lib().fsdo_skidpad_record(self._h, _p(out), ctypes.c_int(len(out))) == len(SKID_RECORD)
+        rec = {k: float(v) for k, v in zip(SKID_RECORD, out) if not k.startswith(("cluster_size_", "median_split_"))}
+        n = 0 if np.isnan(rec["n_clusters"]) else min(int(rec["n_clusters"]), SKID_RECORD_SIZES)
+        i0 = SKID_RECORD.index("cluster_size_0")
+        rec["cluster_sizes"] = [int(v) for v in out[i0 : i0 + n]]
+        j0 = SKID_RECORD.index("median_split_0")
+        rec["median_split"] = [int(v) for v in out[j0 : j0 + n]]  # per cluster: the x and the y median are held by different members
+        return rec
 
     def reference_centers(self):
         out = np.zeros(4)
