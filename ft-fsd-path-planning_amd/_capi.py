@@ -7,6 +7,7 @@ from here.)
 from __future__ import annotations
 
 import ctypes
+import enum
 import os
 from pathlib import Path
 
@@ -256,8 +257,26 @@ EXPORTED_SYMBOLS = [
     "fsdp_sort_cache_reset", "fsdp_sort_cache_hits", "fsdp_sort_batch_ranked", "fsdp_plan_sequence", "fsdp_plan_sequence_compact",
     "fsdp_plan_sequence_cached", "fsdp_plan_sequence_cached_compact", "fsdp_submit_sequence", "fsdp_submit_sequence_compact",
     "fsdp_device_alloc", "fsdp_device_free", "fsdp_device_write", "fsdp_device_read", "fsdp_device_owns", "fsdp_stream_create", "fsdp_stream_destroy",
-    "fsdp_stream_wait_stream", "fsdp_submit_device", "fsdp_ticket_stream_wait",
+    "fsdp_stream_wait_stream", "fsdp_submit_device", "fsdp_ticket_stream_wait", "fsdp_sort_batch_history",
 ]
+
+
+class CandVerdict(enum.IntEnum):
+    """include/fsdp.h FSDP_CAND_*: why a neighbour of the popped cone was not pushed — the first predicate, in the order the
+    reference evaluates them (end_configurations.py:108-223), that rejects it"""
+
+    ADDED = 0
+    IN_ATTEMPT = 1
+    OUTSIDE_ELLIPSE = 2
+    WRONG_SIDE = 3
+    SKIPS_NEIGHBOUR = 4
+    ABSOLUTE_ANGLE = 5
+    DIRECTIONAL_ANGLE = 6
+    ZIGZAG = 7
+    BEHIND_START = 8
+    CROSSES_CAR = 9
+
+
 RANK_MAX, COST_TERMS = 64, 7  # include/fsdp.h FSDP_RANK_MAX, FSDP_COST_TERMS
 COST_TERM_NAMES = ("angle", "residual_distance", "number_of_cones", "initial_direction", "change_of_direction", "cones_on_either",
                    "wrong_direction")  # cost_function.py:287-296
@@ -586,6 +605,27 @@ class Context:
                                                      ctypes.c_void_p(costs.ctypes.data), ctypes.c_void_p(tm.ctypes.data) if terms else None),
                     "fsdp_sort_batch_ranked")
         return out, counts, configs, costs, tm
+
+    def sort_batch_history(self, offsets, cones, poses, rows_cap: int = 256, verdicts: bool = True):
+        """fsdp_sort_batch_history: sort_batch plus, per frame and side (0 left, 1 right), the search history -> (results, dict of
+        n_rows (n,2) never truncated, target_length (n,2), rows (n,2,rows_cap,max_len) -1 padded in visiting order, is_end
+        (n,2,rows_cap), and with `verdicts` cand (n,2,rows_cap,max_neighbors) -1 padded / verdict (same shape, CandVerdict codes,
+        0xFF padded), else None for both).  Entries beyond min(n_rows, rows_cap) rows hold -1 / 0xFF."""
+        offsets, cones, poses, n = self._prep(offsets, cones, poses)
+        k = max(1, int(rows_cap))  # (array shapes only: the library refuses a rows_cap below 1)
+        if n * 2 * k > 2**31 - 1:
+            raise ValueError("n_frames * 2 * rows_cap exceeds 2^31 - 1")
+        out = np.zeros(n, dtype=self.result_dtype)
+        h = dict(n_rows=np.zeros((n, 2), np.int32), target_length=np.zeros((n, 2), np.int32),
+                 rows=np.full((n, 2, k, self.shapes.max_len), -1, np.int32), is_end=np.full((n, 2, k), 0xFF, np.uint8), cand=None, verdict=None)
+        if verdicts:
+            h["cand"] = np.full((n, 2, k, self.shapes.max_neighbors), -1, np.int32)
+            h["verdict"] = np.full((n, 2, k, self.shapes.max_neighbors), 0xFF, np.uint8)
+        ptr = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        self._check(self._lib.fsdp_sort_batch_history(self._h, n, _ip(offsets), _dp(cones), _dp(poses), ctypes.c_void_p(out.ctypes.data), int(rows_cap),
+                                                      ptr(h["n_rows"]), ptr(h["target_length"]), ptr(h["rows"]), ptr(h["is_end"]), ptr(h["cand"]),
+                                                      ptr(h["verdict"])), "fsdp_sort_batch_history")
+        return out, h
 
     def match_batch(self, sorted_left, n_left, sorted_right, n_right, poses) -> np.ndarray:
         sorted_left = np.ascontiguousarray(sorted_left, np.float64).reshape(-1, self.shapes.max_len, 2)

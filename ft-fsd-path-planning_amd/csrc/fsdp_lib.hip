@@ -31,6 +31,7 @@
 #include "sequence_launch.h"    // (the chain kernels of fsdp_plan_sequence are a translation unit of their own: sequence_lib.hip)
 #include "host_buffers.h"       // (no kernels: DeviceBuf / PinnedBuf and the stores a slot and a context own)
 #include "device_io_launch.h"   // (the kernels of a device ticket are a translation unit of their own: device_io_lib.hip)
+#include "sort_history_launch.h"  // (the history instantiations of the sorting kernels likewise: sort_history_lib.hip)
 
 using namespace fsdp;
 
@@ -466,15 +467,17 @@ static fsdp_seqc_launch_args seqc_args(const fsdp_ctx* c, Work& q, const Inputs&
 
 // Which instantiation of the three sorting kernels (sort_kernel_128 | sort_kernel, sort_big_kernel) a launch takes, and what that
 // instantiation needs.  Whoever describes the launch chooses it, once: the cached one for a lock-step call that advances the sorting
-// cache, the speculative one for a pass of fsdp_plan_sequence_cached, the ranked one for fsdp_sort_batch_ranked, else the plain one.
+// cache, the speculative one for a pass of fsdp_plan_sequence_cached, the ranked one for fsdp_sort_batch_ranked, the history
+// one for fsdp_sort_batch_history, else the plain one.
 struct SortVariant {
-  enum Kind { PLAIN, CACHED, SPEC, RANKED } kind = PLAIN;
+  enum Kind { PLAIN, CACHED, SPEC, RANKED, HISTORY } kind = PLAIN;
   SortCacheView cache;                    // CACHED: the cache buffers and the planner of the launch's frame 0
   fsdp_seqc_launch_args* seqc = nullptr;  // SPEC: the pass's launch arguments (launch_pass: seqc_args)
   const SortRankView* rank = nullptr;     // RANKED: where the rows go ...
   SortRankScratchBig* scratch = nullptr;  // ... and sort_big_kernel_ranked's block for the cost terms (SORT_BIG_BLOCKS of them)
+  fsdp_sort_hist_launch_args* hist = nullptr;  // HISTORY: the call's launch arguments (sort_history_lib.hip)
   const char* suffix() const {
-    static const char* const names[] = {"", "_cached", "_spec", "_ranked"};
+    static const char* const names[] = {"", "_cached", "_spec", "_ranked", "_history"};
     return names[kind];
   }
 };
@@ -492,7 +495,10 @@ static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& s
                        in.d_poses, q.buf.d_sort, q.buf.d_big, c->d_params, st, var.cache);
   else if (var.kind == SortVariant::SPEC)
     fsdp_seqc_launch_sort(q.stream, var.seqc);
-  else
+  else if (var.kind == SortVariant::HISTORY) {
+    var.hist->small = small;
+    fsdp_sort_hist_launch(q.stream, var.hist);
+  } else
     hipLaunchKernelGGL((small ? sort_kernel_128 : sort_kernel), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones, in.d_poses,
                        q.buf.d_sort, q.buf.d_big, c->d_params, st);
   names += std::string(small ? "sort_kernel_128" : "sort_kernel") + var.suffix();
@@ -509,6 +515,9 @@ static int launch_sort_big(fsdp_ctx* c, Work& q, const Inputs& in, std::string& 
   else if (var.kind == SortVariant::SPEC) {
     var.seqc->big_state = q.d_sort_big;
     fsdp_seqc_launch_sort_big(q.stream, var.seqc);
+  } else if (var.kind == SortVariant::HISTORY) {
+    var.hist->big_state = q.d_sort_big;
+    fsdp_sort_hist_launch_big(q.stream, var.hist);
   } else
     hipLaunchKernelGGL(sort_big_kernel, grid, block, 0, q.stream, in.d_off, in.d_cones, in.d_poses, q.buf.d_sort, q.buf.d_big, q.d_sort_big,
                        c->d_params);
@@ -2664,11 +2673,51 @@ static void map_back(int32_t* idx, size_t n, const int32_t* map) {
     if (idx[k] >= 0) idx[k] = map[idx[k]];
 }
 
-// fsdp_sort_batch, and with rk fsdp_sort_batch_ranked (the ranked kernels instead of the plain ones, never the sorting cache)
+// The history outputs of fsdp_sort_batch_history on the device for the duration of one call (a diagnostic route: allocated per call)
+struct HistCall {
+  int rows_cap = 0;
+  int32_t* n_rows = nullptr;  // caller's arrays
+  int32_t* target_length = nullptr;
+  int32_t* rows = nullptr;
+  uint8_t* is_end = nullptr;
+  int32_t* cand = nullptr;
+  uint8_t* verdict = nullptr;
+  DeviceBuf<int32_t> d_n_rows, d_target, d_rows, d_cand;
+  DeviceBuf<uint8_t> d_is_end, d_verdict;
+};
+
+// fsdp_sort_batch, with rk fsdp_sort_batch_ranked and with hk fsdp_sort_batch_history (the ranked / history kernels instead of the
+// plain ones, never the sorting cache)
 static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
-                           fsdp_frame_result* results, RankCall* rk) {
-  const char* who = rk ? "fsdp_sort_batch_ranked" : "fsdp_sort_batch";
+                           fsdp_frame_result* results, RankCall* rk, HistCall* hk = nullptr) {
+  const char* who = hk ? "fsdp_sort_batch_history" : rk ? "fsdp_sort_batch_ranked" : "fsdp_sort_batch";
   if (!c) return 1;
+  if (hk) {
+    if (c->mission == 2) {
+      c->err = "fsdp_sort_batch_history: a skidpad context never sorts cones";
+      return 1;
+    }
+    if (hk->rows_cap < 1) {
+      c->err = "fsdp_sort_batch_history: rows_cap must be at least 1";
+      return 1;
+    }
+    if (!hk->n_rows || !hk->target_length || !hk->rows || !hk->is_end) {
+      c->err = "fsdp_sort_batch_history: NULL n_rows / target_length / rows / is_end";
+      return 1;
+    }
+    if ((hk->cand == nullptr) != (hk->verdict == nullptr)) {
+      c->err = "fsdp_sort_batch_history: cand and verdict are given together or not at all";
+      return 1;
+    }
+    if (n_frames > 0 && (long long)n_frames * 2 * (long long)hk->rows_cap > 2147483647ll) {
+      c->err = "fsdp_sort_batch_history: n_frames * 2 * rows_cap exceeds 2^31 - 1";
+      return 1;
+    }
+    if (!fsdp_sort_hist_launch || !fsdp_sort_hist_launch_big) {
+      c->err = "fsdp_sort_batch_history: this library was built without csrc/sort_history_lib.hip";
+      return 1;
+    }
+  }
   if (rk) {
     if (c->mission == 2) {
       c->err = "fsdp_sort_batch_ranked: a skidpad context never sorts cones";
@@ -2685,14 +2734,30 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
   }
   if (c->outstanding) return busy_error(c, who);
   HIP_TRY(c, hipSetDevice(c->device));
+  if (hk)
+    if (int rc = refuse_device_pointers(c, who, {{"cone_offsets", off}, {"cones_xyt", cones}, {"poses", poses}, {"results", results},
+                                                 {"n_rows", hk->n_rows}, {"target_length", hk->target_length}, {"rows", hk->rows},
+                                                 {"is_end", hk->is_end}, {"cand", hk->cand}, {"verdict", hk->verdict}}))
+      return rc;
   Batch b;
   if (int rc = check_batch(c, n_frames, off, cones, poses, nullptr, &b)) return rc;
-  const bool cached = !rk && c->n_cache > 0;
+  const bool cached = !rk && !hk && c->n_cache > 0;
   if (cached && n_frames != c->n_cache) return cache_prepare(c, n_frames, off, "fsdp_sort_batch");
   if (n_frames == 0) return 0;
   if (int rc = sync_all(c)) return rc;
   if (cached)
     if (int rc = cache_prepare(c, n_frames, off, "fsdp_sort_batch")) return rc;
+  const size_t hrows = hk ? (size_t)n_frames * 2 * (size_t)hk->rows_cap : 0;
+  if (hk) {  // (first: a call whose outputs do not fit returns with nothing planned, and its buffers go with it)
+    HIP_TRY(c, hk->d_rows.reserve(hrows * MAX_LEN));
+    if (hk->cand) {
+      HIP_TRY(c, hk->d_cand.reserve(hrows * KNN));
+      HIP_TRY(c, hk->d_verdict.reserve(hrows * KNN));
+    }
+    HIP_TRY(c, hk->d_is_end.reserve(hrows));
+    HIP_TRY(c, hk->d_n_rows.reserve(2 * (size_t)n_frames));
+    HIP_TRY(c, hk->d_target.reserve(2 * (size_t)n_frames));
+  }
   Work& q = stage_slot(c);
   if (int rc = ensure_work(c, q, n_frames)) return rc;
   if (int rc = upload_inputs(c, q.in, q.stream, b)) return rc;
@@ -2730,11 +2795,43 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
     var.kind = SortVariant::CACHED;
     var.cache = cache_view(c, 0);  // (frame i is planner i)
   }
+  fsdp_sort_hist_launch_args ha;
+  if (hk) {
+    // unused entries: -1 indices, 0xFF flags and codes, zero counts; a side that is not searched writes nothing
+    HIP_TRY(c, hipMemsetAsync(hk->d_n_rows, 0, sizeof(int32_t) * 2 * (size_t)n_frames, q.stream));
+    HIP_TRY(c, hipMemsetAsync(hk->d_target, 0, sizeof(int32_t) * 2 * (size_t)n_frames, q.stream));
+    HIP_TRY(c, hipMemsetAsync(hk->d_rows, 0xff, sizeof(int32_t) * hrows * MAX_LEN, q.stream));
+    HIP_TRY(c, hipMemsetAsync(hk->d_is_end, 0xff, hrows, q.stream));
+    if (hk->cand) {
+      HIP_TRY(c, hipMemsetAsync(hk->d_cand, 0xff, sizeof(int32_t) * hrows * KNN, q.stream));
+      HIP_TRY(c, hipMemsetAsync(hk->d_verdict, 0xff, hrows * KNN, q.stream));
+    }
+    if (c->poison) HIP_TRY(c, hipMemsetAsync(q.buf.d_sort, 0xff, sizeof(SortOut) * (size_t)n_frames, q.stream));
+    ha.n_frames = in.n_frames;
+    ha.off = in.d_off;
+    ha.cones = in.d_cones;
+    ha.poses = in.d_poses;
+    ha.sorted = q.buf.d_sort;
+    ha.big = q.buf.d_big;
+    ha.big_state = nullptr;  // (launch_sort_big allocates the blocks on first use)
+    ha.big_blocks = SORT_BIG_BLOCKS;
+    ha.small = false;        // (launch_sort decides)
+    ha.prm = c->d_params;
+    ha.view.rows_cap = hk->rows_cap;
+    ha.view.n_rows = hk->d_n_rows;
+    ha.view.target_length = hk->d_target;
+    ha.view.rows = hk->d_rows;
+    ha.view.is_end = hk->d_is_end;
+    ha.view.cand = hk->d_cand;
+    ha.view.verdict = hk->d_verdict;
+    var.kind = SortVariant::HISTORY;
+    var.hist = &ha;
+  }
   std::string names;
   launch_sort(c, q, in, StageIn(), names, var);
   names += ',';
   if (int rc = launch_sort_big(c, q, in, names, var)) return rc;
-  if (rk) c->stage_names = names;  // (fsdp_sort_batch leaves the names of the most recent pass in place)
+  if (rk || hk) c->stage_names = names;  // (fsdp_sort_batch leaves the names of the most recent pass in place)
   HIP_TRY(c, hipMemsetAsync(q.buf.d_big, 0, sizeof(int), q.stream));  // (no assemble_kernel follows to reset the list)
   HIP_TRY(c, c->h_sort.reserve((size_t)n_frames, 64));
   HIP_TRY(c, hipMemcpyAsync(c->h_sort, q.buf.d_sort, sizeof(SortOut) * n_frames, hipMemcpyDeviceToHost, q.stream));
@@ -2744,6 +2841,16 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
     HIP_TRY(c, hipMemcpyAsync(rk->configs, rk->d_configs, sizeof(int32_t) * rows * MAX_LEN, hipMemcpyDeviceToHost, q.stream));
     HIP_TRY(c, hipMemcpyAsync(rk->costs, rk->d_costs, sizeof(double) * rows, hipMemcpyDeviceToHost, q.stream));
     if (rk->terms) HIP_TRY(c, hipMemcpyAsync(rk->terms, rk->d_terms, sizeof(double) * rows * COST_TERMS, hipMemcpyDeviceToHost, q.stream));
+  }
+  if (hk) {
+    HIP_TRY(c, hipMemcpyAsync(hk->n_rows, hk->d_n_rows, sizeof(int32_t) * 2 * (size_t)n_frames, hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(hk->target_length, hk->d_target, sizeof(int32_t) * 2 * (size_t)n_frames, hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(hk->rows, hk->d_rows, sizeof(int32_t) * hrows * MAX_LEN, hipMemcpyDeviceToHost, q.stream));
+    HIP_TRY(c, hipMemcpyAsync(hk->is_end, hk->d_is_end, hrows, hipMemcpyDeviceToHost, q.stream));
+    if (hk->cand) {
+      HIP_TRY(c, hipMemcpyAsync(hk->cand, hk->d_cand, sizeof(int32_t) * hrows * KNN, hipMemcpyDeviceToHost, q.stream));
+      HIP_TRY(c, hipMemcpyAsync(hk->verdict, hk->d_verdict, hrows * KNN, hipMemcpyDeviceToHost, q.stream));
+    }
   }
   if (filtered) {  // indices back into the caller's index space (what assemble_kernel does for a full pass)
     map.resize(b.total ? b.total : 1);
@@ -2767,6 +2874,11 @@ static int sort_batch_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const 
         const size_t per_frame = 2 * (size_t)rk->top_k * MAX_LEN;
         map_back(rk->configs + (size_t)i * per_frame, per_frame, fmap);
       }
+      if (hk) {
+        const size_t per_frame = 2 * (size_t)hk->rows_cap;
+        map_back(hk->rows + (size_t)i * per_frame * MAX_LEN, per_frame * MAX_LEN, fmap);
+        if (hk->cand) map_back(hk->cand + (size_t)i * per_frame * KNN, per_frame * KNN, fmap);
+      }
     }
   }
   return 0;
@@ -2786,6 +2898,20 @@ int fsdp_sort_batch_ranked(fsdp_ctx* c, int n_frames, const int32_t* off, const 
   rk.costs = costs;
   rk.terms = terms;
   return sort_batch_impl(c, n_frames, off, cones, poses, results, &rk);
+}
+
+int fsdp_sort_batch_history(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses,
+                            fsdp_frame_result* results, int rows_cap, int32_t* n_rows, int32_t* target_length, int32_t* rows,
+                            uint8_t* is_end, int32_t* cand, uint8_t* verdict) {
+  HistCall hk;
+  hk.rows_cap = rows_cap;
+  hk.n_rows = n_rows;
+  hk.target_length = target_length;
+  hk.rows = rows;
+  hk.is_end = is_end;
+  hk.cand = cand;
+  hk.verdict = verdict;
+  return sort_batch_impl(c, n_frames, off, cones, poses, results, nullptr, &hk);
 }
 
 int fsdp_match_batch(fsdp_ctx* c, int n_frames, const double* sorted_left, const int32_t* n_left, const double* sorted_right,

@@ -20,6 +20,7 @@
 #include "fsdp_device.h"
 #include "sort_cache.h"
 #include "sort_rank.h"
+#include "sort_history.h"
 
 namespace fsdp {
 
@@ -233,6 +234,60 @@ __device__ inline bool candidate_can_be_added(const SH& S, const Params& P, int 
     can = !segments_intersect(lx, ly, cx, cy, csx, csy, cex, cey);
   }
   return can;
+}
+
+// The same tests for the kernels that report the search history (sort_history.h): which predicate rejects the candidate, as the
+// first one in the order the reference evaluates them (end_configurations.py:126, :129-132, :134-141, then per remaining candidate
+// :152-160, :184, :186-189, :194-205, :207-211, :213-221); CAND_ADDED where candidate_can_be_added returns true.  `between` is
+// evaluated up front for every candidate here, so it ranks behind the three masks the reference applies before its loop.
+template <class SH>
+__device__ inline int candidate_verdict(const SH& S, const Params& P, int side, int cone_type, int pos, int node, int cand, bool between,
+                                        double px, double py, double dx, double dy, double dnx, double dny, double a_car, double ang_sl,
+                                        double ang_tl, double& ang_cand) {
+  const double lx = S.x[node], ly = S.y[node];
+  const double cx = S.x[cand], cy = S.y[cand];
+  const double l2cx = cx - lx, l2cy = cy - ly;
+  ang_cand = atan2(l2cy, l2cx);
+  for (int q = 0; q <= pos; q++)
+    if (S.attempt[side][q] == cand) return CAND_IN_ATTEMPT;
+  int sl = (pos >= 1) ? S.attempt[side][pos - 1] : 0;
+  if (pos >= 1) {
+    if (!inside_ellipse_of_edge(cx, cy, lx, ly, lx - S.x[sl], ly - S.y[sl], ang_sl, 6, 3)) return CAND_OUTSIDE_ELLIPSE;
+  }
+  if (pos == 0) {
+    double a_n = atan2(cy - py, cx - px);
+    double diff = angle_difference(a_n, a_car);
+    double want = (cone_type == T_LEFT) ? 1.0 : -1.0;
+    if (!((sign_of(diff) == want) || (fabs(diff) < 5 * FSDP_DEG))) return CAND_WRONG_SIDE;
+  }
+  if (between) return CAND_SKIPS_NEIGHBOUR;
+  if (pos >= 1) {
+    double angle_1 = ang_sl;
+    double angle_2 = ang_cand;
+    double difference = angle_difference(angle_2, angle_1);
+    double len = norm_blas(l2cx, l2cy);
+    if (fabs(difference) > P.threshold_absolute_angle) return CAND_ABSOLUTE_ANGLE;
+    bool can;
+    if (cone_type == T_LEFT)
+      can = (difference < P.threshold_directional_angle) || (len < 4.0);
+    else
+      can = (difference > -P.threshold_directional_angle) || (len < 4.0);
+    if (!can) return CAND_DIRECTIONAL_ANGLE;
+    if (pos >= 2) {
+      double angle_3 = ang_tl;
+      double difference_2 = angle_difference(angle_1, angle_3);
+      if (sign_of(difference) != sign_of(difference_2) && fabs(difference - difference_2) > 1.3) return CAND_ZIGZAG;
+    }
+  }
+  if (pos == 1) {
+    int st = S.attempt[side][0];
+    if (!acos_less(cos_between(dx, dy, cx - S.x[st], cy - S.y[st]), FSDP_PI / 2, 0.0)) return CAND_BEHIND_START;
+  }
+  const double car_size = 2.1;
+  double csx = px - dnx * car_size / 2, csy = py - dny * car_size / 2;
+  double cex = px + dnx * car_size, cey = py + dny * car_size;
+  if (segments_intersect(lx, ly, cx, cy, csx, csy, cex, cey)) return CAND_CROSSES_CAR;
+  return CAND_ADDED;
 }
 
 // NumPy pairwise sum of the first n (<= MAX_LEN - 1 <= 15: below the 16 of the unrolled loop's second block) entries of a
@@ -576,8 +631,9 @@ struct PairMask<true> {
 // Phase 2 (S8): DFS over the cost tree (end_configurations.py:320-431) of BOTH sides at once, one half-wavefront per
 // side.  A pop keeps at most 5 candidate lanes and 25 (candidate, neighbour) lanes busy, so the two independent searches
 // share every instruction; the loop runs until both stacks are empty.
-template <class SH, bool CACHE = false, bool RANKED = false>
-__device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double py, double dx, double dy) {
+// HIST: every pop is one row of the search history (sort_history.h); the row counter is side-uniform.
+template <class SH, bool CACHE = false, bool RANKED = false, bool HIST = false>
+__device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double py, double dx, double dy, const SortHistFrame* hist = nullptr) {
   const int lane = lane_id();
   const int side = lane >> 5, sl = lane & 31;
   const int cone_type = (side == 0) ? T_LEFT : T_RIGHT;
@@ -589,6 +645,9 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
   const double a_car = atan2(dny, dnx);
   int sp = 0, n_ends = 0;
   int status = ST_OK;
+  int n_hist = 0, code = 0;
+  (void)n_hist;
+  (void)code;
   PROF_MARK_DECL(3);
   if (active && sl < MAX_LEN) S.attempt[side][sl] = -1;
   __syncthreads();
@@ -649,12 +708,21 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
     if (sl < n_nb) {
       const bool between = ((bm >> (sl * n_nb)) & (((pair_mask_t)1 << n_nb) - 1u)) != 0u;
       const double ang_tl = (pos >= 2) ? S.attempt_ang[side][pos - 1] : 0.0;
+      if constexpr (HIST) {
+        code = candidate_verdict(S, P, side, cone_type, pos, node, S.nbr[adj][node][sl], between, px, py, dx, dy, dnx, dny, a_car, node_ang, ang_tl,
+                                 cand_ang);
+        can = code == CAND_ADDED;
+      } else
       can = candidate_can_be_added<SH, CACHE, RANKED>(S, P, side, cone_type, pos, node, S.nbr[adj][node][sl], between, px, py, dx, dy, dnx, dny, a_car,
                                    node_ang, ang_tl, cand_ang);
     }
     const unsigned m = (unsigned)(__ballot(can) >> (32 * side));
     if (go) {
       const bool has_valid = (pos < target_length - 1) && (m != 0u);
+      if constexpr (HIST) {
+        sort_hist_store(*hist, side, sl, n_hist, S.attempt[side], !has_valid, n_nb, sl < n_nb ? (int)S.nbr[adj][node][sl] : -1, code);
+        n_hist++;
+      }
       if (has_valid) {
         if (can) {
           int slot = sp + __popc(m & ((1u << sl) - 1u));
@@ -676,6 +744,7 @@ __device__ inline void sort_dfs_both(SH& S, const Params& P, double px, double p
   if (sl == 0) {
     S.ctl[side].n_ends = n_ends;
     S.ctl[side].status = status;
+    if constexpr (HIST) sort_hist_close(*hist, side, n_hist, target_length);
   }
   __syncthreads();
 }
@@ -1346,11 +1415,12 @@ __device__ inline void sort_cache_commit(const SH& S, const SortCacheFrame& cf, 
 // raised (with the cache on a left hit never raises), the per-side results and the frame's similarity to its planner's previous
 // step into spec->rec[frame] (sort_cache.h SeqSpecRec).  The SortOut is the plain kernels' but for one thing: a capacity refusal
 // of either side sends the frame to sort_big_kernel_spec.
-template <class SH, bool CACHE = false, bool RANKED = false, bool SPEC = false>
+// HIST: the search history of both sides goes to hist's arrays (sort_history.h); nothing else differs.
+template <class SH, bool CACHE = false, bool RANKED = false, bool SPEC = false, bool HIST = false>
 __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
                                   const double* __restrict__ poses, SortOut* __restrict__ out, const StageIn& stage = StageIn(),
                                   const SortCacheView* cache = nullptr, const SortRankFrame* rank = nullptr,
-                                  const SeqSpecView* spec = nullptr) {
+                                  const SeqSpecView* spec = nullptr, const SortHistFrame* hist = nullptr) {
   const int lane = lane_id();
   const bool staging = stage.src_off != nullptr;
   const int32_t* offs = staging ? stage.src_off : cone_offsets;
@@ -1379,6 +1449,12 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
     rk = *rank;
     rk.frame = frame;
   }
+  SortHistFrame hf;
+  if constexpr (HIST) {
+    hf = *hist;
+    hf.frame = frame;
+  }
+  (void)hf;
   if (n > SH::MAX_N) {
     status = ST_OVERFLOW_CONES;
     n = 0;
@@ -1479,7 +1555,7 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
     // (the left call returns before building the adjacency when it finds no start cone or n < 3, or reuses the cached result)
     const bool left_built = S.adj_built != 0;
     sort_side_prepare<SH, CACHE, RANKED>(S, P, n, T_RIGHT, 1, px, py, dx, dy, colourless && left_built, &cf);
-    if (FSDP_SORT_STOP > 2) sort_dfs_both<SH, CACHE, RANKED>(S, P, px, py, dx, dy);
+    if (FSDP_SORT_STOP > 2) sort_dfs_both<SH, CACHE, RANKED, HIST>(S, P, px, py, dx, dy, HIST ? &hf : nullptr);
     if (FSDP_SORT_STOP > 3) {
       status = sort_side_finish<SH, CACHE, RANKED>(S, n, T_LEFT, 0, px, py, dx, dy, &rk);
       __syncthreads();
@@ -1554,21 +1630,21 @@ __device__ inline void sort_frame(SH& S, const Params& P, int frame, const int32
 // One workgroup (= one wavefront) per frame, frame state in LDS.  big (optional): [0] = counter, [1..] = frames beyond
 // the LDS capacities (more cones than the state holds, more than 64 raw end configurations), planned again by
 // sort_big_kernel.
-template <class SH, bool CACHE = false, bool RANKED = false>
+template <class SH, bool CACHE = false, bool RANKED = false, bool HIST = false>
 __device__ __forceinline__ void sort_kernel_body(SH& S, int n_frames, const int32_t* __restrict__ cone_offsets,
                                                  const double* __restrict__ cones_xyt, const double* __restrict__ poses,
                                                  SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
                                                  const StageIn& stage, const SortCacheView* cache = nullptr,
-                                                 const SortRankFrame* rank = nullptr) {
+                                                 const SortRankFrame* rank = nullptr, const SortHistFrame* hist = nullptr) {
   const int frame = blockIdx.x;
   if (frame >= n_frames) return;
   PROF_INIT();
-  sort_frame<SH, CACHE, RANKED>(S, *prm, frame, cone_offsets, cones_xyt, poses, out, stage, cache, rank);
+  sort_frame<SH, CACHE, RANKED, false, HIST>(S, *prm, frame, cone_offsets, cones_xyt, poses, out, stage, cache, rank, nullptr, hist);
   if (big != nullptr && lane_id() == 0 && (out[frame].status == ST_OVERFLOW_CONES || out[frame].status == ST_OVERFLOW_ENDS))
     big[1 + atomicAdd(&big[0], 1)] = frame;
   PROF_FLUSH();
 }
-#ifndef FSDP_SEQUENCE_CACHE_UNIT  // (csrc/sequence_cache_lib.hip compiles this header for its own instantiations alone)
+#if !defined(FSDP_SEQUENCE_CACHE_UNIT) && !defined(FSDP_SORT_HISTORY_UNIT)  // (csrc/sequence_cache_lib.hip and csrc/sort_history_lib.hip compile this header for their own instantiations alone)
 // Up to 255 cones per frame.  Three wavefronts per SIMD (168 registers, 13.0 KB of LDS per frame): the stage is a chain of
 // short dependent sections, and the third resident wavefront fills issue slots the other two leave open (+8 % frames/s over
 // two; 40 bytes of spill).
@@ -1588,7 +1664,7 @@ constexpr int SORT_WAVES_128 = 3;  // (the wide shapes' frame state is 12.4 KB: 
 #else
 constexpr int SORT_WAVES_128 = 4;
 #endif
-#ifndef FSDP_SEQUENCE_CACHE_UNIT
+#if !defined(FSDP_SEQUENCE_CACHE_UNIT) && !defined(FSDP_SORT_HISTORY_UNIT)
 __global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(SORT_WAVES_128)
 sort_kernel_128(int n_frames, const int32_t* __restrict__ cone_offsets, const double* __restrict__ cones_xyt,
                 const double* __restrict__ poses, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm,
@@ -1637,6 +1713,6 @@ __global__ void __launch_bounds__(64) sort_big_kernel_cached(const int32_t* __re
     __syncthreads();
   }
 }
-#endif  // FSDP_SEQUENCE_CACHE_UNIT
+#endif  // FSDP_SEQUENCE_CACHE_UNIT, FSDP_SORT_HISTORY_UNIT
 
 }  // namespace fsdp

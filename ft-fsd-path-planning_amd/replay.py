@@ -5,6 +5,7 @@ loop :103-131).  Same file schema: a list of {"car_position":[x,y], "car_directi
   python -m fsd_path_planning_amd.replay --data-path fsg_19_2_laps.json [--remove-color-info] [--batched] [--output-path out.npz]
                                           [--experimental-performance-improvements]  (per-frame mode only)
                                           [--ranked K]  (per frame: decision margins and deciding cost terms of the sorting stage)
+                                          [--history ROWS]  (per side: where the sorting stage's searches went and what rejected candidates)
 
 Two replay modes:
   per-frame : one PathPlanner, one calculate_path_in_global_frame call per frame, wall-clock per call (what the
@@ -185,6 +186,29 @@ def replay_ranked(mission, positions, directions, observations, top_k: int, devi
     return cat(status, 0, np.int32), cat(counts, (0, 2), np.int32), cat(margins, (0, 2), np.float64), cat(deciding, (0, 2), np.int64)
 
 
+def replay_history(mission, positions, directions, observations, rows_cap: int, device=None, batch_frames: int = 4096):
+    """The recording's frames as independent frames through fsdp_sort_batch_history: where every side's depth-first search went
+    and which predicate turned each neighbour away.  Returns (status (F,), n_rows (F, 2), no_configuration (F, 2) bool — the side
+    was searched and the frame has no configuration for it — and histograms (F, 2, 10): how often each CandVerdict code occurred in
+    the side's stored rows).  A side that visited more than rows_cap rows contributes its first rows_cap to the histogram."""
+    planner = PathPlanner(mission, device=device)
+    ctx = planner._ctx
+    frames = list(zip(observations, positions, directions))
+    # (the calls' arrays are (frames, 2, rows_cap, ...) at 73 bytes a row: batches of at most 2^18 rows a side keep them below 40 MB)
+    step = max(1, min(int(batch_frames), (1 << 18) // max(1, int(rows_cap))))
+    status, n_rows, none_left, hist = [], [], [], []
+    for lo in range(0, len(frames), step):
+        off, cones, poses = pack_frames(frames[lo:lo + step])
+        res, h = ctx.sort_batch_history(off, cones, poses, rows_cap=int(rows_cap))
+        v = h["verdict"].reshape(len(poses), 2, -1)
+        hist.append(np.stack([(v == code).sum(axis=-1) for code in range(10)], axis=-1))
+        status.append(res["status"].copy())
+        n_rows.append(h["n_rows"])
+        none_left.append((h["n_rows"] > 0) & (np.stack([res["n_configs_left"], res["n_configs_right"]], axis=-1) == 0))
+    cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)  # noqa: E731
+    return cat(status, 0, np.int32), cat(n_rows, (0, 2), np.int32), cat(none_left, (0, 2), bool), cat(hist, (0, 2, 10), np.int64)
+
+
 FB_READ_PREVIOUS = 1 | 2 | 4 | 8  # path_fallback bits of the branches that read previous_paths[-1] (include/fsdp.h; the frames fsdp_plan_sequence plans again)
 
 
@@ -303,7 +327,28 @@ def main(argv=None):
     ap.add_argument("--ranked", type=int, default=None, metavar="K",
                     help="instead of a timed replay: rank the K best end configurations of every frame and side and print, per frame, the "
                          "decision margins (left, right) and the deciding cost terms (trackdrive / autocross recordings)")
+    ap.add_argument("--history", type=int, default=None, metavar="ROWS",
+                    help="instead of a timed replay: trace the sorting stage's depth-first search of every frame and side, up to ROWS visited "
+                         "configurations each, and print per side how far the searches went and which predicates turned candidates away; with "
+                         "--output-path the per-frame histograms are written too (trackdrive / autocross recordings)")
     a = ap.parse_args(argv)
+    if a.history is not None:
+        from ._capi import CandVerdict
+
+        mission = select_mission_by_filename(a.data_path.name)
+        positions, directions, observations = load_data_json(a.data_path, a.remove_color_info)
+        status, n_rows, none_left, hist = replay_history(mission, positions, directions, observations, a.history, a.device, a.batch_frames)
+        sides = {}
+        for s, name in enumerate(("left", "right")):
+            sides[name] = {"frames_searched": int((n_rows[:, s] > 0).sum()), "rows_visited": int(n_rows[:, s].sum()),
+                           "most_rows_in_a_frame": int(n_rows[:, s].max()) if len(n_rows) else 0,
+                           "frames_without_a_configuration": int(none_left[:, s].sum()),
+                           "rejections": {CandVerdict(code).name.lower(): int(hist[:, s, code].sum()) for code in range(1, 10)}}
+        if a.output_path:
+            np.savez_compressed(a.output_path, status=status, n_rows=n_rows, no_configuration=none_left, verdict_histogram=hist)
+        print(json.dumps({"file": str(a.data_path), "mission": mission.name, "frames": len(status), "mode": "history", "rows_cap": a.history,
+                          "frames_beyond_rows_cap": int((n_rows > a.history).any(axis=1).sum()), **sides}))
+        return
     if a.ranked is not None:
         from ._capi import COST_TERM_NAMES
 

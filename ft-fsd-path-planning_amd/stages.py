@@ -112,6 +112,30 @@ class ConeSorting:
             out.append(None if m == 0 else (costs[0, s, :m].copy(), configs[0, s, :m].astype(np.int64), terms[0, s, :m].copy()))
         return tuple(out)
 
+    def search_history(self, rows_cap: int = 256):
+        """The search behind run_cone_sorting's candidates for the current input, per side (left, right): None for a side that was
+        not searched, else ``(all_configurations, configuration_is_end, neighbours, verdicts)`` — the reference's own history
+        tuple (calc_scores_and_end_configurations(..., return_history=True), end_configurations.py:411-429: every configuration
+        the depth-first search visited, in visiting order, (R, target_length) indices into the flattened cones, -1 padded, and
+        (R,) bool) plus, per visited row, the popped cone's neighbours (R, max_n_neighbors; -1 padded) and why each was or was not
+        pushed (_capi.CandVerdict codes; 0xFF padded).  The frame's status is not raised: the history is what explains it.
+        Raises ValueError if a side visited more than the `rows_cap` rows a call stores.  Plans the frame afresh: it neither
+        uses nor advances the sorting cache."""
+        xyt = flatten_cones_by_type_array(self.input.slam_cones)
+        pose = np.concatenate([np.asarray(self.input.slam_position, float).reshape(2), np.asarray(self.input.slam_direction, float).reshape(2)])
+        ctx = self._own_ctx or _ctx(self._device, self._params)
+        res, h = ctx.sort_batch_history(np.array([0, len(xyt)], np.int32), xyt, pose[None], rows_cap=int(rows_cap))
+        self.last_result = res[0]
+        out = []
+        for s in range(2):
+            n, t = int(h["n_rows"][0, s]), int(h["target_length"][0, s])
+            if n > int(rows_cap):
+                raise ValueError(f"the {('left', 'right')[s]} side's search visited {n} configurations, more than rows_cap = {int(rows_cap)}: "
+                                 f"call search_history(rows_cap={n})")
+            out.append(None if n == 0 else (h["rows"][0, s, :n, :t].astype(np.int64), h["is_end"][0, s, :n].astype(bool),
+                                            h["cand"][0, s, :n].astype(np.int64), h["verdict"][0, s, :n].copy()))
+        return tuple(out)
+
 
 @dataclass
 class ConeMatchingInput:

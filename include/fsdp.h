@@ -546,6 +546,49 @@ int fsdp_sort_batch(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, co
 int fsdp_sort_batch_ranked(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt,
                            const double* poses, fsdp_frame_result* results, int top_k, int32_t* counts, int32_t* configs,
                            double* costs, double* terms);
+/* The same call with the search history of every side — what calc_scores_and_end_configurations(..., return_history=True)
+ * (find_configs_and_scores.py:41,96; store_all_end_configurations, end_configurations.py:358-361,411-429) returns: every
+ * configuration the depth-first search visited, in visiting order, and whether it was an end configuration — and, beyond the
+ * reference, why each neighbour of the popped cone was or was not pushed.  `results` is filled exactly as fsdp_sort_batch fills it.
+ *   n_rows        (n_frames,2)                      configurations the side's search visited, in full, whether or not it exceeds
+ *                                                   rows_cap; 0 for a side that was not searched (fewer than 3 cones, no start cone)
+ *   target_length (n_frames,2)                      min(reachable cones, max_length) (find_configs_and_scores.py:76), the width of
+ *                                                   the reference's all_configurations; 0 where n_rows is 0
+ *   rows          (n_frames,2,rows_cap,FSDP_MAX_LEN)  the first min(n_rows, rows_cap) visited configurations in visiting order:
+ *                                                   current_attempt after the pop (:369-370,414), -1 padded, indices into the
+ *                                                   frame's cones
+ *   is_end        (n_frames,2,rows_cap)             1 where the row is an end configuration (not has_valid_neighbors, :388,415: the
+ *                                                   row is at target_length - 1, or no neighbour has verdict 0), else 0
+ *   cand, verdict (n_frames,2,rows_cap,FSDP_MAX_NEIGHBORS)  both given or both NULL: the popped cone's neighbours in adjacency
+ *                                                   order (ascending index, -1 padded) and each one's code below — also for a row
+ *                                                   that ends by length (the reference computes the mask before it looks at the length)
+ * Side 0 = left, 1 = right.  Unused entries hold -1 (rows, cand) and 0xFF (is_end, verdict).  A side's rows do not depend on the
+ * other side, on the kernel that plans the frame or on the batch around it, and a side that was searched reports its rows whatever
+ * happens afterwards: the post filters may leave nothing (the reference's NoPathError: the side has no result), the frame may end
+ * with status 101.  A search that stops at a raise (102, :369) reports the rows before the pop that raised; one refused for
+ * capacity (202) a prefix of its rows.  With use_unknown_cones = 0 rows and cand are mapped back to the caller's array like the
+ * indices of `results`.  The call plans every frame afresh: it neither reads nor writes the sorting cache.  Errors, all with
+ * nothing planned: a skidpad context, rows_cap < 1, NULL n_rows / target_length / rows / is_end, exactly one of cand and verdict
+ * NULL, n_frames * 2 * rows_cap beyond 2^31 - 1, outstanding tickets, a device pointer (1); outputs the device has no memory for
+ * (2; the context stays usable). */
+/* why a neighbour of the popped cone was not pushed: the FIRST predicate, in the order the reference evaluates them
+ * (end_configurations.py:108-223), that rejects it */
+enum {
+  FSDP_CAND_ADDED = 0,
+  FSDP_CAND_IN_ATTEMPT = 1,        /* :126  my_in1d                                              */
+  FSDP_CAND_OUTSIDE_ELLIPSE = 2,   /* :129-132, position >= 1                                    */
+  FSDP_CAND_WRONG_SIDE = 3,        /* :134-141, position 0                                       */
+  FSDP_CAND_SKIPS_NEIGHBOUR = 4,   /* :152-160 / :226-257 (a neighbour lies between)             */
+  FSDP_CAND_ABSOLUTE_ANGLE = 5,    /* :184                                                       */
+  FSDP_CAND_DIRECTIONAL_ANGLE = 6, /* :186-189 (beyond the directional threshold AND edge >= 4 m) */
+  FSDP_CAND_ZIGZAG = 7,            /* :194-205, position >= 2                                    */
+  FSDP_CAND_BEHIND_START = 8,      /* :207-211, position 1                                       */
+  FSDP_CAND_CROSSES_CAR = 9        /* :213-221                                                   */
+};
+int fsdp_sort_batch_history(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt,
+                            const double* poses, fsdp_frame_result* results, int rows_cap,
+                            int32_t* n_rows, int32_t* target_length, int32_t* rows, uint8_t* is_end,
+                            int32_t* cand, uint8_t* verdict);
 /* ConeMatching.run_cone_matching — sorted_left/right: (n_frames,FSDP_MAX_LEN,2) padded, counts (n_frames,). */
 int fsdp_match_batch(fsdp_ctx* ctx, int n_frames, const double* sorted_left, const int32_t* n_left,
                      const double* sorted_right, const int32_t* n_right, const double* poses,
