@@ -233,6 +233,8 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     # (ctx, n_frames, cone_capacity, counts, cones, poses, prev_paths, paths, status, next_prev, records, after_stream, ticket)
     lib.fsdp_submit_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.POINTER(ctypes.c_longlong)]
     lib.fsdp_ticket_stream_wait.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
+    # (ctx, n_instances, cone_capacity, counts, cones, poses, reset, paths, status, info, records, after_stream, ticket)
+    lib.fsdp_skidpad_submit_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.POINTER(ctypes.c_longlong)]
     got = (ctypes.c_int32 * 4)()
     lib.fsdp_shapes(got)
     want = [shapes.max_len, shapes.max_neighbors, shapes.max_match, shapes.path_points]
@@ -258,6 +260,7 @@ EXPORTED_SYMBOLS = [
     "fsdp_plan_sequence_cached", "fsdp_plan_sequence_cached_compact", "fsdp_submit_sequence", "fsdp_submit_sequence_compact",
     "fsdp_device_alloc", "fsdp_device_free", "fsdp_device_write", "fsdp_device_read", "fsdp_device_owns", "fsdp_stream_create", "fsdp_stream_destroy",
     "fsdp_stream_wait_stream", "fsdp_submit_device", "fsdp_ticket_stream_wait", "fsdp_sort_batch_history",
+    "fsdp_skidpad_submit_device",
 ]
 
 

@@ -31,6 +31,7 @@
 #include "sequence_launch.h"    // (the chain kernels of fsdp_plan_sequence are a translation unit of their own: sequence_lib.hip)
 #include "host_buffers.h"       // (no kernels: DeviceBuf / PinnedBuf and the stores a slot and a context own)
 #include "device_io_launch.h"   // (the kernels of a device ticket are a translation unit of their own: device_io_lib.hip)
+#include "skid_device_launch.h"  // (the kernels of a skidpad device ticket live in that unit too)
 #include "sort_history_launch.h"  // (the history instantiations of the sorting kernels likewise: sort_history_lib.hip)
 
 using namespace fsdp;
@@ -134,6 +135,9 @@ struct Work {
     int32_t* status = nullptr;
     double* next_prev = nullptr;       // or NULL; may be `prev`
     fsdp_compact_result* records = nullptr;  // or NULL
+    // a skidpad device ticket (fsdp_skidpad_submit_device): its step's records, or NULL
+    fsdp_skidpad_info* skid_info = nullptr;
+    fsdp_path_result* skid_records = nullptr;
   };
   // tickets of fsdp_submit / fsdp_skidpad_submit / fsdp_submit_sequence queued on this slot's stream (id -1: free entry).  A ticket
   // holds the whole description of its pass: enqueue_ticket launches the first pass and fsdp_collect's rerun from it alone.
@@ -161,7 +165,9 @@ struct Work {
     int cache_lo = -1;                     // >= 0: a chunk of a lock-step call that advances the sorting cache (the _cached sorting
                                            // kernels); its frame 0 is this planner
     DevPass dev;                           // a device ticket's pass
-    PinnedBuf<int32_t> h_bad;              // pinned + mapped: the lowest frame of a device ticket whose count was out of range, or -1
+    PinnedBuf<int32_t> h_bad;              // pinned + mapped: the lowest frame of a device ticket whose count was out of range, or -1;
+                                           // [1], a skidpad device ticket: 1 when a planner was not relocalized after the step
+    unsigned reloc_epoch = 0;              // a skidpad step: fsdp_ctx::skid_reloc_epoch when it was submitted
     Event after;                           // a device ticket: recorded on the producer's stream, waited for by the slot's
     Event done;                            // recorded behind the ticket's last command
     // the entry is free again: what the caller owned, and what described his pass, is forgotten
@@ -242,6 +248,8 @@ struct fsdp_ctx {
   uint32_t skid_ticket_base = 0;
   int skid_step_no = 0;              // steps submitted since fsdp_skidpad_reset
   bool skid_all_reloc = false;       // a collected step reported every planner relocalized: cones have no reader any more
+  unsigned skid_reloc_epoch = 0;     // counts the resets (of all planners, or through a device step's mask): a step submitted before
+                                     // one says nothing about the planners after it, whenever it is collected
   int skid_group_env = 0;            // "skid_group": steps per launch when the caller submits ahead (0: chosen from the instance count)
   // fsdp_skidpad_time_groups: HIP events around the packed kernels of every group of steps (select | prep | fit | finish | commit)
   bool skid_time_groups = false;
@@ -1787,6 +1795,18 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
       }
     }
   }
+  if (rc == 0 && n > 0 && t.skid && t.dev.on) {
+    // A skidpad device ticket.  (No skidpad step is ever run again — the block above is not for them: a step has moved its
+    // planners' state on, and a consumer on the GPU has read a device ticket's results.)  The word its out kernel left: no planner
+    // that was not relocalized — unless planners were reset since the step was submitted.
+    if (t.reloc_epoch == c->skid_reloc_epoch && __atomic_load_n(t.h_bad.get() + 1, __ATOMIC_RELAXED) == 0) c->skid_all_reloc = true;
+    if (const int32_t bad = __atomic_load_n(t.h_bad.get(), __ATOMIC_RELAXED); bad >= 0) {
+      c->err = "fsdp_collect: counts[" + std::to_string(bad) + "] of device ticket " + std::to_string(ticket) + " lies outside [0, cone_capacity = " +
+               std::to_string(t.dev.cap) + "] (the lowest such planner; every such planner took the step as having 0 cones: the call's outputs are not to be used, "
+               "and the planners' state has advanced by the step all the same — fsdp_skidpad_reset starts them afresh)";
+      rc = 1;
+    }
+  }
   if (rc == 0 && n > 0) {
     if (t.via_stage && t.sq.on && !t.sq.s.whole()) {  // a planner slice: the ticket's block is dense, the caller's array holds the whole recording
       const SeqSlice& s = t.sq.s;
@@ -1802,7 +1822,7 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
       if (t.sq.n_replanned) *t.sq.n_replanned = __atomic_load_n(&q.h_trailer[&t - q.tk].pad, __ATOMIC_RELAXED);
     }
     if (t.user_info && t.h_info) {
-      if (!c->skid_all_reloc) {
+      if (!c->skid_all_reloc && t.reloc_epoch == c->skid_reloc_epoch) {
         bool all = true;
         for (int i = 0; i < n && all; i++) all = t.h_info[i].relocalized != 0;
         c->skid_all_reloc = all;
@@ -1956,7 +1976,7 @@ int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32
   *ticket = -1;
   const std::string who = "fsdp_submit_device";
   if (c->mission == 2) {
-    c->err = who + ": a skidpad context plans through fsdp_skidpad_submit";
+    c->err = who + ": a skidpad context plans through fsdp_skidpad_submit (device arrays: fsdp_skidpad_submit_device)";
     return 1;
   }
   if (c->n_cache > 0) {
@@ -3156,6 +3176,7 @@ int fsdp_skidpad_reset(fsdp_ctx* c, int n_instances) {
   c->skid_ticket_base = 0;
   c->skid_step_no = 0;
   c->skid_all_reloc = false;
+  c->skid_reloc_epoch++;
   return 0;
 }
 
@@ -3243,6 +3264,22 @@ static int flush_skid(fsdp_ctx* c) {
     Work& q = c->slot[c->skid_pending[k]];
     Work::Ticket& t = q.tk[0];
     t.pending = false;
+    if (t.dev.on) {
+      // a device step: its records to the caller's arrays on the GPU (skid_device_out_kernel)
+      fsdp_skid_dio_out_args o;
+      o.n_inst = n;
+      o.paths = q.buf.d_path;
+      o.info = q.buf.d_skid_info;
+      o.out_paths = t.dev.paths;
+      o.out_status = t.dev.status;
+      o.out_info = (SkidInfo*)t.dev.skid_info;
+      o.out_records = (PathOut*)t.dev.skid_records;
+      o.not_reloc = t.h_bad.device() + 1;
+      fsdp_skid_dio_launch_out(xs, &o);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipEventRecord(t.done, xs));
+      continue;
+    }
     // page-locked results: assemble_kernel writes them into the caller's buffer (over PCIe); the planners' information
     // records ride along into the ticket's pinned block
     // (only a buffer that is page-locked over its WHOLE extent — decided at submit time, `via_stage` otherwise: a view
@@ -3336,6 +3373,7 @@ static int skidpad_submit_impl(fsdp_ctx* c, int n_instances, const int32_t* off,
   t.user_info = info;
   t.via_stage = results && !direct;
   t.compact = compact;
+  t.reloc_epoch = c->skid_reloc_epoch;
   c->skid_pending[c->n_skid_pending++] = si;
   c->last = fsdp_ctx::LastPass{si, n_instances, false, true};
   t.id = c->next_ticket++;
@@ -3355,6 +3393,148 @@ static_assert(sizeof(fsdp_path_result) == sizeof(PathOut) && offsetof(fsdp_path_
 int fsdp_skidpad_submit_compact(fsdp_ctx* c, int n_instances, const int32_t* off, const double* cones, const double* poses,
                                 fsdp_path_result* results, fsdp_skidpad_info* info, long long* ticket) {
   return skidpad_submit_impl(c, n_instances, off, cones, poses, (fsdp_frame_result*)results, info, ticket, true);
+}
+
+// The same step with every array in the memory of the context's GPU (include/fsdp.h).  The way in is a device ticket's (scan +
+// gather into the slot's InputStore), the relocalization attempt and the path kernels are the host route's, on the context's one
+// stream; skid_device_reset_kernel goes in front of the attempt and skid_device_out_kernel behind the path kernels.  The step is
+// never left pending: it joins the steps the host calls left pending, and the group is flushed.
+static_assert(sizeof(fsdp_skidpad_info) == sizeof(SkidInfo) && offsetof(fsdp_skidpad_info, relocalized) == offsetof(SkidInfo, relocalized) &&
+                  offsetof(fsdp_skidpad_info, index_along_path) == offsetof(SkidInfo, index_along_path) &&
+                  offsetof(fsdp_skidpad_info, translation) == offsetof(SkidInfo, translation) && offsetof(fsdp_skidpad_info, rotation) == offsetof(SkidInfo, rotation),
+              "fsdp_skidpad_info is the planners' information record");
+int fsdp_skidpad_submit_device(fsdp_ctx* c, int n_instances, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
+                               const int32_t* reset, double* paths, int32_t* status, fsdp_skidpad_info* info, fsdp_path_result* records,
+                               void* after_stream, long long* ticket) {
+  if (!c || !ticket) return 1;
+  *ticket = -1;
+  const std::string who = "fsdp_skidpad_submit_device";
+  if (c->mission != 2) {
+    c->err = who + ": not a skidpad context (the other missions' device tickets go through fsdp_submit_device)";
+    return 1;
+  }
+  if (!c->have_tables || n_instances < 1 || n_instances != c->n_instances || !c->d_skid) {
+    c->err = who + ": call fsdp_skidpad_set_tables and fsdp_skidpad_reset(n_instances) first";
+    return 1;
+  }
+  if (cone_capacity < 0) {
+    c->err = who + ": cone_capacity must be >= 0";
+    return 1;
+  }
+  if ((long long)n_instances * cone_capacity > 0x7fffffffll) {
+    c->err = who + ": n_instances x cone_capacity = " + std::to_string((long long)n_instances * cone_capacity) + " cone rows exceed the int32 offsets of a step";
+    return 1;
+  }
+  if (!counts || !poses || !paths || !status || (cone_capacity > 0 && !cones)) {
+    c->err = who + ": counts, poses, paths and status are required" + (cone_capacity > 0 ? ", and cones with cone_capacity > 0" : "");
+    return 1;
+  }
+  if (!fsdp_skid_dio_launch_reset || !fsdp_skid_dio_launch_in || !fsdp_skid_dio_launch_out) {
+    c->err = who + ": this library was built without the device ticket kernels (csrc/device_io_lib.hip)";
+    return 2;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = (size_t)n_instances;
+  const struct {
+    const char* name;
+    const void* p;
+    size_t bytes;
+  } arrays[] = {{"counts", counts, sizeof(int32_t) * n},
+                {"cones", cone_capacity > 0 ? cones : nullptr, sizeof(double) * 3 * n * (size_t)cone_capacity},
+                {"poses", poses, sizeof(double) * 4 * n},
+                {"reset", reset, sizeof(int32_t) * n},
+                {"paths", paths, sizeof(double) * PATH_POINTS * 4 * n},
+                {"status", status, sizeof(int32_t) * n},
+                {"info", info, sizeof(fsdp_skidpad_info) * n},
+                {"records", records, sizeof(fsdp_path_result) * n}};
+  for (const auto& x : arrays)
+    if (x.p && !device_owns(c, x.p, x.bytes)) {
+      c->err = who + ": " + x.name + " is not device memory of the context's GPU over its whole extent of " + std::to_string(x.bytes) +
+               " bytes (host memory, page-locked or not, goes through fsdp_skidpad_submit; managed memory, another GPU's memory and memory of "
+               "another HIP runtime are not accepted)";
+      return 1;
+    }
+  // one step per slot, as for fsdp_skidpad_submit
+  int si = (int)(c->next_ticket % c->overlap);
+  for (int k = 0; k < c->overlap && c->slot[si].tk[0].id >= 0; k++) si = (si + 1) % c->overlap;
+  Work& q = c->slot[si];
+  Work::Ticket& t = q.tk[0];
+  if (t.id >= 0) {
+    c->err = who + ": all " + std::to_string(c->overlap) + " slots hold a ticket; collect one first, e.g. ticket " + std::to_string(t.id);
+    return 4;
+  }
+  // everything the step needs room for, before anything is enqueued (the slot's ticket is collected: nothing queued uses its buffers)
+  const bool attempt = reset != nullptr || !c->skid_all_reloc;
+  if (int rc = ensure_work(c, q, n_instances)) return rc;
+  // (rows and max_cones are upper bounds, as for a device ticket: the host never dereferences the batch)
+  const Batch b{n_instances, nullptr, nullptr, nullptr, nullptr, attempt ? n * (size_t)cone_capacity : 0, cone_capacity};
+  if (int rc = take_batch(c, q.in, b)) return rc;
+  HIP_TRY(c, t.h_bad.reserve(2, 16, Pin::MappedCoherent));
+  if (!t.done) HIP_TRY(c, hipEventCreateWithFlags(&t.done.h, hipEventDisableTiming));
+  if (after_stream && !t.after) HIP_TRY(c, hipEventCreateWithFlags(&t.after.h, hipEventDisableTiming));
+  hipStream_t xs = c->stream;
+  if (reset) {
+    // The steps the host calls left pending plan with the planners as they are: their path kernels go in front of the reset.
+    if (int rc = flush_skid(c)) return rc;
+    c->skid_all_reloc = false;  // (the reset planners have to relocalize again: the cones are read again)
+    c->skid_reloc_epoch++;
+  }
+  t.h_bad[0] = -1;
+  t.h_bad[1] = 0;
+  if (after_stream) {
+    HIP_TRY(c, hipEventRecord(t.after, (hipStream_t)after_stream));
+    HIP_TRY(c, hipStreamWaitEvent(xs, t.after, 0));
+  }
+  if (reset) {
+    fsdp_skid_dio_reset_args r;
+    r.n_inst = n_instances;
+    r.reset = reset;
+    r.states = c->d_skid;
+    r.default_path = c->d_default_path;
+    fsdp_skid_dio_launch_reset(xs, &r);
+  }
+  fsdp_dio_in_args a;
+  a.n_frames = n_instances;
+  a.cone_capacity = cone_capacity;
+  a.counts = counts;
+  a.cones = cone_capacity > 0 ? cones : nullptr;
+  a.poses = poses;
+  a.prev = nullptr;
+  a.bad_frame = t.h_bad.device();
+  a.dst_off = q.in.d_off;
+  a.dst_cones = q.in.d_cones;
+  a.dst_poses = q.in.d_poses;
+  a.dst_prev = nullptr;
+  fsdp_skid_dio_launch_in(xs, &a, attempt ? 1 : 0);
+  q.skid_attempted = attempt;
+  if (attempt)
+    hipLaunchKernelGGL(skid_reloc_kernel, dim3((unsigned)n_instances), dim3(WAVE), 0, xs, n_instances, q.in.d_off, q.in.d_cones, q.in.d_poses, c->d_skid,
+                       c->tables, q.buf.d_arena, q.buf.d_skid_status, c->skid_step_no);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) {
+    // (nothing of the step is left running over the caller's arrays, and no ticket goes out)
+    (void)hipStreamSynchronize(xs);
+    c->err = who + ": " + hipGetErrorString(e);
+    return 2;
+  }
+  c->skid_step_no++;
+  q.pass_in = &q.in;
+  q.pass_skid = true;
+  q.unverified = false;
+  t.batch = b;
+  t.skid = true;
+  t.pending = true;
+  t.user_results = nullptr;
+  t.user_info = nullptr;
+  t.via_stage = false;
+  t.compact = true;
+  t.reloc_epoch = c->skid_reloc_epoch;
+  t.dev = Work::DevPass{true, cone_capacity, counts, a.cones, poses, nullptr, paths, status, nullptr, nullptr, info, records};
+  c->skid_pending[c->n_skid_pending++] = si;
+  c->last = fsdp_ctx::LastPass{si, n_instances, false, true};
+  t.id = c->next_ticket++;
+  c->outstanding++;
+  *ticket = t.id;
+  return flush_skid(c);
 }
 
 int fsdp_skidpad_step(fsdp_ctx* c, int n_instances, const int32_t* off, const double* cones, const double* poses,

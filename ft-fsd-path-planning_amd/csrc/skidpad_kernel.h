@@ -16,6 +16,7 @@
 // reference centres are constant inputs uploaded once (fsdp_skidpad_set_tables).
 #pragma once
 #include "path_kernel.h"
+#include "skid_state.h"
 
 namespace fsdp {
 
@@ -24,18 +25,7 @@ constexpr int SKID_NEAR = 20;
 constexpr int ST_OVERFLOW_CLUSTERS = 205;
 constexpr int ST_SYNC_LOST = 206;  // internal: a step's wavefront never saw its predecessor's state published
 
-constexpr int SKID_HIST = 32;  // > SKID_GROUP_MAX
-
-struct SkidState {
-  int32_t has_original, relocalized, index_along_path;
-  int32_t reloc_step;             // the step (since the reset) whose relocalization attempt latched the transform
-  int32_t index_hist[SKID_HIST];  // index_along_path after step g at [g % SKID_HIST]
-  double orig[4];          // pose latched at the first relocalization attempt
-  double translation[2];
-  double right_calc[2];
-  double rotation;
-  double prev[PATH_POINTS][4];  // previous_paths[-1] (map frame once relocalized)
-};
+// (SKID_HIST, SkidState, SkidInfo: skid_state.h)
 
 struct SkidTables {
   const double* path;    // known global path = BASE_SKIDPAD_PATH[::2], (n_path, 2)
@@ -45,12 +35,6 @@ struct SkidTables {
   double ref_right[2], ref_left[2];  // calculate_reference_centers_for_skidpad_path
   double mean_distance;              // mean of the first 9 segment lengths of the known path (NumPy mean)
   const Params* prm;                 // the context's configuration constants
-};
-
-struct SkidInfo {  // what RelocalizationInformation / the planner state expose (relocalization_information.py:12-35)
-  int32_t relocalized, index_along_path;
-  double translation[2];
-  double rotation;
 };
 
 struct SkidShared {

@@ -6,7 +6,8 @@ of its own (the torch wheels do) hands out pointers the runtime of this library 
 cleanly (FsdpError), see INTEGRATION.md.
 
 DeviceFleet is n stateful planners stepped in lock-step, their previous paths kept on the device: one device ticket per tick,
-nothing crosses PCIe, and the host waits for nothing between ticks.
+nothing crosses PCIe, and the host waits for nothing between ticks.  SkidpadDeviceFleet is the same for the skidpad mission, whose
+planners keep their state in the context (fsdp_skidpad_submit_device).
 """
 from __future__ import annotations
 
@@ -79,8 +80,10 @@ def as_device_ptr(obj, shape, dtype, writable: bool = False) -> int:
     shape, dtype = tuple(int(x) for x in shape), np.dtype(dtype)
     if tuple(cai["shape"]) != shape:
         raise ValueError(f"device array of shape {tuple(cai['shape'])}, expected {shape}")
-    if np.dtype(cai["typestr"]) != dtype:
-        raise ValueError(f"device array of dtype {np.dtype(cai['typestr'])}, expected {dtype}")
+    got = np.dtype(cai["typestr"])
+    # (an array of records — the interface's typestr knows them only as opaque items, '|V32' — matches by its item size)
+    if got != dtype and not (dtype.fields is not None and got.kind == "V" and got.itemsize == dtype.itemsize):
+        raise ValueError(f"device array of dtype {got}, expected {dtype}")
     strides = cai.get("strides")
     if strides is not None:
         want, acc = [], dtype.itemsize
@@ -178,6 +181,72 @@ class DeviceFleet:
             if self._own_ctx:
                 self.ctx.close()
             self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SkidpadDeviceFleet:
+    """n_planners skidpad planners stepped in a closed loop on the GPU (SkidpadBatch.submit_device): one device ticket per tick.
+
+    The planners' state — latch, transform, window index, previous path — lives in the context, and all skidpad work runs on the
+    context's one stream in submit order, so consecutive steps need no ordering from the fleet.  step() returns at once: (paths,
+    status, ticket), the first two device arrays that are final once the ticket is done (``ctx.stream_wait(ticket,
+    consumer_stream)``, or fleet.wait()).  At most ``depth`` steps are outstanding: a further step first collects the oldest one.
+    A ``reset`` mask (n) int32 on the device restarts single planners in front of a step; reset() restarts all of them."""
+
+    def __init__(self, n_planners: int, cone_capacity: int, device: int | None = None, params: dict | None = None, depth: int = 4,
+                 table=None):
+        from .skidpad import SkidpadBatch
+
+        self.n, self.cap = int(n_planners), int(cone_capacity)
+        if self.n < 1 or self.cap < 0:
+            raise ValueError("SkidpadDeviceFleet: n_planners >= 1 and cone_capacity >= 0")
+        self.batch = SkidpadBatch(self.n, device=device, table=table, params=params)
+        self.ctx = self.batch._ctx
+        self.batch.set_overlap(int(depth))
+        self._tickets: list = []
+
+    def step(self, counts, cones, poses, reset=None, after_stream=None, paths=None, status=None, info=None):
+        """One tick: counts (n) int32, cones (n, cone_capacity, 3) or None when cone_capacity = 0, poses (n, 4), reset (n) int32 or
+        None — device arrays.  after_stream: the stream that produces them (a hipStream_t as an int), or None when they are
+        complete.  info: True or a device array of INFO_DTYPE records (ticket.out["info"])."""
+        while len(self._tickets) >= self.ctx.ticket_capacity:
+            self.batch.collect(self._tickets.pop(0))
+        t = self.batch.submit_device(counts, cones, poses, reset=reset, paths=paths, status=status, info=info, after_stream=after_stream,
+                                     cone_capacity=self.cap)
+        self._tickets.append(t)
+        return t.out["paths"], t.out["status"], t
+
+    def wait(self):
+        """Collect every outstanding step (raises FsdpError for a step with a count out of range)."""
+        err = None
+        while self._tickets:
+            try:
+                self.batch.collect(self._tickets.pop(0))
+            except _capi.FsdpError as e:
+                err = err or e
+        if err is not None:
+            raise err
+
+    def reset(self):
+        """Fresh planners, all of them (fsdp_skidpad_reset: the host call, which waits for every outstanding step)."""
+        try:
+            self.wait()
+        finally:
+            self.batch.reset()
+
+    def close(self):
+        if getattr(self, "batch", None) is None:
+            return
+        try:
+            self.wait()
+        finally:
+            self.batch.close()
+            self.batch = self.ctx = None
 
     def __del__(self):
         try:

@@ -124,9 +124,48 @@ class SkidpadBatch:
                             out.ctypes.data, info.ctypes.data, ctypes.byref(t)), "fsdp_skidpad_submit")
         return _capi.Ticket(int(t.value), out, info, (off, cones, poses))
 
+    def submit_device(self, counts, cones, poses, *, reset=None, paths=None, status=None, info=None, records=None, after_stream=None,
+                      cone_capacity: int | None = None):
+        """One step whose arrays are device memory of this context's GPU (fsdp_skidpad_submit_device) — DeviceArrays or any objects
+        with ``__cuda_array_interface__``: counts (n) int32, cones (n, cone_capacity, 3) float64 (None with cone_capacity = 0), poses
+        (n, 4); reset (n) int32 or None: planners with a non-zero entry are fresh planners before this step.  paths (n, path_points,
+        4) and status (n) int32 are allocated as DeviceArrays when not given; info / records: True, or device arrays of n INFO_DTYPE
+        / path_result_dtype records.  after_stream: the producer's hipStream_t (int) or None.  Returns a DeviceTicket whose ``out``
+        holds the device arrays; they are final when the ticket is done (collect, or Context.stream_wait for a consumer on the GPU).
+        Every array must stay alive until collect (the ticket holds them)."""
+        from .device import DeviceArray, DeviceTicket, as_device_ptr
+
+        if isinstance(counts, np.ndarray) or not hasattr(counts, "__cuda_array_interface__"):
+            raise TypeError("submit_device takes device arrays (DeviceArray / __cuda_array_interface__); host arrays go through submit")
+        ctx = self._ctx
+        n = int(counts.__cuda_array_interface__["shape"][0])
+        if cone_capacity is None:
+            cone_capacity = 0 if cones is None else int(cones.__cuda_array_interface__["shape"][1])
+        cap, rows = int(cone_capacity), ctx.shapes.path_points
+        if paths is None:
+            paths = DeviceArray(ctx, (n, rows, 4))
+        if status is None:
+            status = DeviceArray(ctx, (n,), np.int32)
+        if info is True:
+            info = DeviceArray(ctx, (n,), INFO_DTYPE)
+        if records is True:
+            records = DeviceArray(ctx, (n,), ctx.path_result_dtype)
+        ptr = lambda a, shape, dt, writable=False: None if a is None else as_device_ptr(a, shape, dt, writable=writable)
+        t = ctypes.c_longlong(-1)
+        ctx._check(ctx._lib.fsdp_skidpad_submit_device(
+            ctx._h, n, cap, ptr(counts, (n,), np.int32), ptr(cones if cap > 0 else None, (n, cap, 3), np.float64), ptr(poses, (n, 4), np.float64),
+            ptr(reset, (n,), np.int32), ptr(paths, (n, rows, 4), np.float64, True), ptr(status, (n,), np.int32, True),
+            ptr(info, (n,), INFO_DTYPE, True), ptr(records, (n,), ctx.path_result_dtype, True), after_stream, ctypes.byref(t)), "fsdp_skidpad_submit_device")
+        out = {"paths": paths, "status": status, "info": info, "records": records}
+        return DeviceTicket(int(t.value), out, None, (counts, cones, poses, reset))
+
     def collect(self, ticket):
+        """Wait for this ticket only -> (results, info); for a device ticket the dict of its output device arrays (FsdpError when a
+        count was outside [0, cone_capacity])."""
         self._ctx._check(self._ctx._lib.fsdp_collect(self._ctx._h, ctypes.c_longlong(ticket.id)), "fsdp_collect")
         ticket._keep = None
+        if ticket.info is None and isinstance(ticket.out, dict):
+            return ticket.out
         return ticket.out, ticket.info
 
     def set_overlap(self, depth: int):

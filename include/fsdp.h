@@ -428,8 +428,8 @@ int fsdp_stream_wait_stream(fsdp_ctx* ctx, void* stream, void* after);
  * Returns an error, nothing enqueued: a pointer outside the rule above; NULL counts, poses, paths or status; a skidpad context;
  * a context whose sorting cache is on; n_frames < 1; cone_capacity < 0; n_frames x cone_capacity beyond 2^31 - 1 rows; every
  * ticket entry taken (4: collect one first); memory the device does not have (2; the context stays usable).
- * Not offered: device forms of the sequence, cached, ranked, stage-level and skidpad calls, CSR input with
- * device offsets, peer-GPU memory. */
+ * Not offered: device forms of the sequence, cached, ranked and stage-level calls, CSR input with
+ * device offsets, peer-GPU memory.  (A skidpad context's device tickets: fsdp_skidpad_submit_device.) */
 int fsdp_submit_device(fsdp_ctx* ctx, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
                        const double* prev_paths, double* paths, int32_t* status, double* next_prev, fsdp_compact_result* records,
                        void* after_stream, long long* ticket);
@@ -671,6 +671,41 @@ typedef struct {
 } fsdp_path_result;
 int fsdp_skidpad_submit_compact(fsdp_ctx* ctx, int n_instances, const int32_t* cone_offsets, const double* cones_xyt,
                                 const double* poses, fsdp_path_result* results, fsdp_skidpad_info* info, long long* ticket);
+/* The same step as a DEVICE ticket: every array in the memory of the context's GPU, for a simulator whose cones live there — a
+ * closed loop of stateful skidpad planners in which nothing crosses PCIe and the host waits for nothing between ticks.  One call
+ * is one calculate_path_in_global_frame of every planner; results, planner information and the planners' state afterwards are
+ * those of fsdp_skidpad_submit with the same cones and poses, byte for byte.
+ * Inputs as for fsdp_submit_device, under its pointer rule (host memory is refused with 1 and a message that points to
+ * fsdp_skidpad_submit): counts (n_instances), cones (n_instances, cone_capacity, 3) — planner i's cones are its first counts[i]
+ * rows, the rows behind them are never read; cone_capacity = 0 with cones == NULL: every planner sees no cones —, poses
+ * (n_instances, 4).
+ *   reset    (n_instances) int32 or NULL: planner i with reset[i] != 0 is a fresh planner before this step (PathPlanner.__init__):
+ *            its state is what fsdp_skidpad_reset writes for every planner, written by a kernel on the context's stream in front
+ *            of the step's relocalization attempt.  Steps the host calls left pending are planned before it.  A non-NULL mask
+ *            makes the library read the cones again until a collected step shows every planner relocalized.
+ * Outputs, device memory:
+ *   paths    (n_instances, FSDP_PATH_POINTS, 4), required: the path field fsdp_skidpad_step returns (the caller's frame)
+ *   status   (n_instances), required
+ *   info     (n_instances) fsdp_skidpad_info, or NULL
+ *   records  (n_instances) fsdp_path_result, or NULL
+ * Ordering.  All skidpad work runs on the context's one stream in submit order: consecutive device steps need no ordering from
+ * the caller for the planners' state; the output arrays are the caller's to keep apart between ticks.  after_stream as for
+ * fsdp_submit_device (an event recorded on it, the context's stream waits for it); fsdp_ticket_stream_wait takes these tickets.
+ * Finality.  A device step is never left pending: the call flushes it, together with the steps submitted ahead through the host
+ * calls that were still pending (in order; grouped steps equal single steps).  No skidpad step is ever run again, so the outputs
+ * are final when the ticket's event fires.
+ * Once a collected device step has left every planner relocalized — one word its out kernel leaves in page-locked memory; the
+ * host reads no info for it — later steps gather the poses alone and skip the relocalization attempt, as fsdp_skidpad_submit does.
+ * fsdp_collect returns 1 when a count was outside [0, cone_capacity] and names the lowest such planner; such a planner took the
+ * step with 0 cones, nothing was read outside the caller's rows, and THE PLANNERS' STATE HAS ADVANCED BY THAT STEP all the same
+ * (fsdp_skidpad_reset, or a reset mask, starts planners afresh).
+ * Returns an error, nothing enqueued, the context stays usable: a context that is not a skidpad context; tables or
+ * fsdp_skidpad_reset missing, or n_instances different from the reset's; a pointer outside the rule; NULL counts, poses, paths or
+ * status; cone_capacity < 0; n_instances x cone_capacity beyond 2^31 - 1 rows; every slot holding a ticket (4: collect one
+ * first); memory the device does not have (2).  The mirror: the Python binding of fsdp_skidpad_submit* refuses device arrays. */
+int fsdp_skidpad_submit_device(fsdp_ctx* ctx, int n_instances, int cone_capacity, const int32_t* counts, const double* cones,
+                               const double* poses, const int32_t* reset, double* paths, int32_t* status, fsdp_skidpad_info* info,
+                               fsdp_path_result* records, void* after_stream, long long* ticket);
 /* time `iters` repetitions of the one-wavefront-per-planner path kernel on the last step's inputs with HIP events (the
  * states are restored afterwards) */
 int fsdp_skidpad_time_path(fsdp_ctx* ctx, int iters, float* ms_total);
