@@ -433,6 +433,11 @@ class Context:
         self.n_cache = 0
         self.shapes, self.result_dtype, self.path_result_dtype = shapes, shapes.result_dtype, shapes.path_result_dtype
         self.compact_dtype = shapes.compact_dtype
+        # the library reads no environment: the hardware queues the runtime grants this process arrive as an option (a replay
+        # deeper than the queues is issued as ganged passes: include/fsdp.h "Pass overlap")
+        queues = os.environ.get("GPU_MAX_HW_QUEUES", "")
+        if queues.isdigit() and int(queues) > 0:
+            self.set_option("hw_queues", int(queues))
         for k, v in {**DEFAULT_OPTIONS, **(options or {})}.items():
             self.set_option(k, v)
 
@@ -825,6 +830,15 @@ class Context:
             return
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
         self._check(self._lib.fsdp_set_global_path(self._h, _dp(xy), ctypes.c_int(len(xy))), "fsdp_set_global_path")
+
+    def set_previous_paths(self, prev_paths):
+        """fsdp_set_previous_paths: (n,horizon,4) previous paths of the resident batch's frames (None = fresh planners again)."""
+        if prev_paths is None:
+            self._check(self._lib.fsdp_set_previous_paths(self._h, None), "fsdp_set_previous_paths")
+            return
+        prev = self.pad_paths(prev_paths)
+        assert len(prev) == self.n_frames
+        self._check(self._lib.fsdp_set_previous_paths(self._h, _dp(prev)), "fsdp_set_previous_paths")
 
     def set_overlap(self, depth: int):
         """depth d (1..32): consecutive run() passes rotate through d HIP streams / buffer sets and overlap (a replay is a

@@ -103,6 +103,7 @@ struct Work {
   // the most recent pass launched on the slot (verify_pass re-runs it with the route kernels when they were needed)
   const InputStore<>* pass_in = nullptr;
   bool ran_big = false, ran_retry = false, unverified = false, pass_skid = false;
+  int gang_members = 0, gang_first = 0, gang_n = 0;  // ... was a ganged pass of so many members; its last member's first frame and frames
   // A sequence pass (fsdp_plan_sequence*, fsdp_submit_sequence*) as its ticket describes it: the ticket's pass — and the rerun
   // fsdp_collect issues when the pass lacked a route — resolves the planners' previous-path chains between the path stage and the
   // assembly.  enqueue_ticket hands it to the launches inside the pass's description (Pass::sq): nothing about the pass in progress
@@ -191,6 +192,7 @@ struct fsdp_ctx {
   std::string err;
   Work slot[FSDP_MAX_OVERLAP];
   InputStore<> res;       // the resident batch of fsdp_upload (every slot's fsdp_run pass reads it)
+  size_t res_rows = 0;    // ... and its cone rows
   bool resident = false;  // res describes a batch fsdp_run may plan
   bool res_checked = false;  // a verified pass over the resident batch has set expect_big / expect_retry exactly
   // The most recent pass (launch_pass, a skidpad step), what fsdp_download, fsdp_resident_frames and fsdp_debug_* read: they
@@ -200,6 +202,7 @@ struct fsdp_ctx {
     int n = 0;               // its frames
     bool in_result = false;  // its results are in the slot's result block (an fsdp_run / fsdp_time_runs pass)
     bool whole = false;      // it covered the whole call (not a chunk of a blocking call)
+    int offset = 0;          // a ganged pass: the last member's first frame in the slot's blocks (n = that member's frames)
   } last;
   DeviceBuf<double> d_default_path;  // (40,4)
   Params params;                     // configuration constants (fsdp_params) ...
@@ -215,6 +218,10 @@ struct fsdp_ctx {
   std::string stage_names;    // kernels of the most recent pass, comma-separated
   bool profile_sort = false;  // profiling build: which kernel fsdp_profile_path runs
   int overlap = 1;
+  int hw_queues = 4;          // "hw_queues": hardware queues the runtime grants this process (HIP's default; the library reads no environment)
+  int gang = 0;               // "gang": members per ganged pass of fsdp_time_runs: 0 = by overlap and hw_queues; 1 = never; k > 1 = k
+  size_t gang_grown_from = 0;  // frames slot 0 held before it first grew for ganged passes: fsdp_set_overlap sizes new slots by this
+                               // or by the resident batch, whichever is more, instead of by the grown slot 0
   unsigned turn = 0;
   long long next_ticket = 0;
   int last_ticket_slot = -1;  // slot of the most recent ticket
@@ -235,7 +242,9 @@ struct fsdp_ctx {
   bool time_main_only = false;            // fsdp_time_detail: events only around the path stage's main kernel
   bool time_kernel_clock = false;         // fsdp_time_detail bit 1: the refit kernel's launches note their own start / end clock
   std::vector<unsigned> tev_recorded;     // per pass of the most recent fsdp_time_runs: which of its events were recorded
+  std::vector<int> tev_members;           // ... and how many passes its launches cover: a gang's members at its first pass, 0 at the others
   DeviceBuf<unsigned long long> d_kclock;  // [2 * iters]: first-wavefront-start | last-wavefront-end of the refit kernel, per timed pass
+  int gang_primed[FSDP_MAX_OVERLAP] = {};  // slot i has executed a ganged pass of so many members since `primed` was last cleared
   bool primed[FSDP_MAX_OVERLAP] = {};     // slot i has executed a pass of the current packing (its stream / hardware queue is set up)
   // skidpad mission
   DeviceBuf<double> d_table, d_noise;
@@ -492,9 +501,16 @@ struct SortVariant {
 
 // Both launches append the name of the kernel they took to `names` (fsdp_stage_names).
 // st: the batch's stage-in (src_off != NULL: the kernel brings it onto the device itself; the ranked kernels have none)
-static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& st, std::string& names, const SortVariant& var) {
+// gang (plain variant only): the pass is a ganged one, its twin kernels stage the members' frames (sort_kernel.h StageGang)
+static void launch_sort(fsdp_ctx* c, Work& q, const Inputs& in, const StageIn& st, std::string& names, const SortVariant& var,
+                        const StageGang* gang = nullptr) {
   const bool small = sort128(c, in);
   const dim3 grid(in.n_frames), block(WAVE);
+  if (gang) {
+    hipLaunchKernelGGL((small ? sort_kernel_128_gang : sort_kernel_gang), grid, block, 0, q.stream, *gang, q.buf.d_sort, q.buf.d_big, c->d_params);
+    names += small ? "sort_kernel_128_gang" : "sort_kernel_gang";
+    return;
+  }
   if (var.kind == SortVariant::RANKED)
     hipLaunchKernelGGL((small ? sort_kernel_128_ranked : sort_kernel_ranked), grid, block, 0, q.stream, in.n_frames, in.d_off, in.d_cones,
                        in.d_poses, q.buf.d_sort, q.buf.d_big, c->d_params, *var.rank);
@@ -675,7 +691,19 @@ static void launch_path_retry(fsdp_ctx* c, Work& q, const Inputs& in, bool sized
 // The description of one pass, beyond its slot and its inputs: what it writes where, where its sorting kernel finds the batch, which
 // kernels it is made of and what it is planned for.  The default is a pass over the resident batch; a ticket's pass is built from
 // the ticket (enqueue_ticket).  The launches read nothing else about the pass: the context holds no per-call state.
+// one member of a ganged pass: a batch on the device or in page-locked host memory (device views), as StageMember takes it
+struct GangMember {
+  const int32_t* off = nullptr;
+  const double* cones = nullptr;  // the array's row 0 (the member's rows start at off[0] = base)
+  const double* poses = nullptr;
+  const double* prev = nullptr;
+  int n = 0;
+  int32_t base = 0;
+  size_t rows = 0;
+};
 struct Pass {
+  std::vector<GangMember> members;    // not empty: a ganged pass over the members' frames, one behind the other; the slot's own input
+                                      // store (launch_pass's `in_`: reserved and described for the sum) receives the copies
   fsdp_frame_result* host = nullptr;  // NULL: results into the slot's result block; else the device view of a page-locked host buffer
                                       // that assemble_kernel writes straight over PCIe (a ticket: no copy command at all)
   bool compact = false;               // ... as fsdp_compact_result records (fsdp_submit_compact)
@@ -789,8 +817,40 @@ static int launch_pass(fsdp_ctx* c, Work& q, const InputStore<>& in_, const Pass
     seqc = seqc_args(c, q, in, pass.sq->s);
     var.seqc = &seqc;
   }
+  StageGang gang;
+  int last_first = 0, last_n = in.n_frames;
+  if (!pass.members.empty()) {
+    if (pass.members.size() > (size_t)GANG_MAX || var.kind != SortVariant::PLAIN || !c->params.use_unknown_cones) {
+      c->err = "internal: a ganged pass takes at most " + std::to_string(GANG_MAX) + " members, the plain sorting kernels and unfiltered inputs";
+      return 2;
+    }
+    int frames = 0;
+    size_t rows = 0;
+    for (const GangMember& gm : pass.members) {
+      StageMember& sm = gang.m[gang.n_members++];
+      sm.src_off = gm.off;
+      sm.src_cones = gm.cones + 3 * (size_t)gm.base;
+      sm.src_poses = gm.poses;
+      sm.src_prev = in.use_prev ? gm.prev : nullptr;
+      sm.base = gm.base;
+      sm.first_frame = last_first = frames;
+      sm.first_row = (int32_t)rows;
+      last_n = gm.n;
+      frames += gm.n;
+      rows += gm.rows;
+    }
+    if (frames != in.n_frames || !in_.fits((size_t)frames, rows, in.use_prev)) {
+      c->err = "internal: slot " + std::to_string(q.index) + "'s input store does not hold the ganged pass's " + std::to_string(frames) + " frames";
+      return 2;
+    }
+    gang.dst_off = in.d_off;
+    gang.dst_cones = in.d_cones;
+    gang.dst_poses = in.d_poses;
+    gang.dst_prev = in.use_prev ? in.d_prev : nullptr;
+    gang.n_frames = frames;
+  }
   mark(q, t);
-  launch_sort(c, q, in, pass.stage, names, var);
+  launch_sort(c, q, in, pass.stage, names, var, pass.members.empty() ? nullptr : &gang);
   names += ',';
   if (with_big) {
     mark(q, t);
@@ -826,7 +886,11 @@ static int launch_pass(fsdp_ctx* c, Work& q, const InputStore<>& in_, const Pass
   q.ran_retry = with_retry;
   q.unverified = pass.trailer == SLOT_QUEUE;  // (a ticket's pass is settled by fsdp_collect, through the ticket's own trailer)
   q.pass_skid = false;
-  c->last = fsdp_ctx::LastPass{q.index, in.n_frames, pass.host == nullptr && !pass.device, true};
+  q.gang_members = (int)pass.members.size();
+  q.gang_first = last_first;
+  q.gang_n = last_n;
+  if (q.gang_members > 0) c->gang_primed[q.index] = std::max(c->gang_primed[q.index], q.gang_members);
+  c->last = fsdp_ctx::LastPass{q.index, last_n, pass.host == nullptr && !pass.device, true, last_first};
   return 0;
 }
 
@@ -843,7 +907,8 @@ static PassTrailer read_trailer(const Work& q, int idx) {
 // A pass's trailer against the routes it ran: keeps the expectations and the retry hint up to date — for a pass over the
 // resident batch exactly what that batch needs from now on, else with decay — and says whether the pass lacked a route
 // kernel it needed and must run again (with both).
-static bool settle_routes(fsdp_ctx* c, const PassTrailer& tr, bool ran_big, bool ran_retry, bool resident) {
+// members: the pass was a gang of so many batches — the retry hint sizes a single pass's grid, so it takes the list length per member.
+static bool settle_routes(fsdp_ctx* c, const PassTrailer& tr, bool ran_big, bool ran_retry, bool resident, int members = 1) {
   auto track = [](bool needed, bool& expect, int& clean) {
     if (needed) {
       expect = true;
@@ -853,7 +918,8 @@ static bool settle_routes(fsdp_ctx* c, const PassTrailer& tr, bool ran_big, bool
       clean = 0;
     }
   };
-  c->retry_hint = std::max(tr.n_retry, c->retry_hint - (c->retry_hint + 7) / 8);
+  const int per_pass = members > 1 ? (tr.n_retry + members - 1) / members : tr.n_retry;
+  c->retry_hint = std::max(per_pass, c->retry_hint - (c->retry_hint + 7) / 8);
   if (resident) {
     c->expect_big = tr.n_big > 0;
     c->expect_retry = tr.n_retry > 0;
@@ -881,10 +947,19 @@ static int verify_pass(fsdp_ctx* c, Work& q) {
     c->err = "internal: pass trailer out of date (slot " + std::to_string(q.index) + ")";
     return 2;
   }
-  if (settle_routes(c, tr, q.ran_big, q.ran_retry, q.pass_in == &c->res)) {
+  if (settle_routes(c, tr, q.ran_big, q.ran_retry, q.pass_in == &c->res, q.gang_members)) {
+    // (a ganged pass left its members' copies in the slot's own input store: it runs again as the plain pass over that store which
+    // every kernel behind the sorting kernel has seen anyway; what the readers hand out stays the last member's block, whichever
+    // slot the context's most recent pass was on)
+    const int members = q.gang_members, first = q.gang_first, n = q.gang_n;
     Pass again;
     again.force_routes = true;
     if (int rc = launch_pass(c, q, *q.pass_in, again)) return rc;
+    if (members > 0) {
+      q.gang_members = members, q.gang_first = first, q.gang_n = n;
+      c->last.n = n;
+      c->last.offset = first;
+    }
     HIP_TRY(c, hipStreamSynchronize(q.stream));
     HIP_TRY(c, hipGetLastError());
     q.unverified = false;
@@ -1272,6 +1347,7 @@ int fsdp_upload(fsdp_ctx* c, int n_frames, const int32_t* off, const double* con
   c->resident = false;  // (until the new batch stands: a failed upload leaves no batch to plan)
   if (int rc = ensure_slots(c, n_frames > 0 ? n_frames : 1)) return rc;
   if (int rc = upload_inputs(c, c->res, c->stream, b)) return rc;
+  c->res_rows = b.total;
   c->resident = true;
   c->res_checked = false;
   c->last = fsdp_ctx::LastPass();  // (no pass has planned this batch yet)
@@ -1297,7 +1373,10 @@ int fsdp_set_overlap(fsdp_ctx* c, int depth) {
   if (c->last.slot >= depth) c->last = fsdp_ctx::LastPass();  // (released above)
   c->last_ticket_slot = -1;
   for (bool& p : c->primed) p = false;  // the kernels of a pass depend on the frames in flight (launch_path)
-  return ensure_slots(c, std::max(1, (int)c->slot[0].buf.frames()));
+  for (int& p : c->gang_primed) p = 0;
+  // (slot 0 may have grown for ganged passes: the other slots keep the size of a plain pass)
+  const size_t plain = c->gang_grown_from ? std::max(c->gang_grown_from, c->resident ? (size_t)c->res.n_frames : (size_t)0) : c->slot[0].buf.frames();
+  return ensure_slots(c, std::max(1, (int)plain));
 }
 
 int fsdp_run(fsdp_ctx* c) {
@@ -1343,7 +1422,7 @@ int fsdp_download(fsdp_ctx* c, fsdp_frame_result* results) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (int rc = sync_all(c)) return rc;
   Work& q = c->slot[c->last.slot];  // the most recent pass
-  HIP_TRY(c, hipMemcpyAsync(results, q.buf.d_result, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
+  HIP_TRY(c, hipMemcpyAsync(results, q.buf.d_result + c->last.offset, sizeof(fsdp_frame_result) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   return 0;
 }
@@ -2432,6 +2511,12 @@ int fsdp_set_option(fsdp_ctx* c, const char* name, long long v) {
     if (v < 0 || v > 0x7fffffff) return bad();
     c->params.retry_pack_min = v == 0 ? 512 : (int)v;
     HIP_TRY(c, copy_sync(c, c->d_params, &c->params, sizeof(Params), hipMemcpyHostToDevice));
+  } else if (k == "hw_queues") {
+    if (v < 1 || v > 0x7fffffff) return bad();
+    c->hw_queues = (int)v;
+  } else if (k == "gang") {
+    if (v < 0 || v > FSDP_MAX_OVERLAP) return bad();
+    c->gang = (int)v;
   } else if (k == "poison") {
     c->poison = v != 0;
   } else if (k == "plan_chunks") {
@@ -2447,6 +2532,7 @@ int fsdp_set_option(fsdp_ctx* c, const char* name, long long v) {
     return bad();
   }
   for (bool& p : c->primed) p = false;  // (the kernels of a pass may have changed: fsdp_time_reserve warms the slots again)
+  for (int& p : c->gang_primed) p = 0;
   c->res_checked = false;
   return 0;
 }
@@ -2508,6 +2594,61 @@ static int reserve_timing(fsdp_ctx* c, int iters) {
   return 0;
 }
 
+// ---- ganged replay -------------------------------------------------------------------------------------------------------
+// Streams that share a hardware queue run one after the other.  A replay whose overlap depth exceeds the queues the runtime grants
+// (option "hw_queues") therefore keeps only hw_queues launches of n frames on the chip, however many streams it spreads its passes
+// over (depth 20 on 4 queues: 4 x 256 wavefronts of fit_kernel<4> on a chip that holds 2048).  fsdp_time_runs then issues the same
+// passes as gangs: g = ceil(overlap / S) passes become one pass over g x n frames (launch_pass, Pass::members) on one of S slots'
+// streams, round robin, S = min(GANG_STREAMS, hw_queues) — streams beyond the queues would wait for each other again.  Frames in
+// flight stay overlap x n; results are those of the single passes.
+// GANG_STREAMS: measured among 1..4 at depth 20 under four queues (profiles/gang_replay.md: 5.8 / 6.3 / 6.5 / 6.4 M frames/s in a
+// 20-pass region, 5.9 / 6.5 / 6.8 / 6.9 M in a 100-pass one).
+constexpr int GANG_STREAMS = 4;
+// members per ganged pass of fsdp_time_runs (1: the passes stay single)
+static int gang_size(const fsdp_ctx* c) {
+  if (!c->params.use_unknown_cones || c->gang == 1) return 1;  // (the filter kernels read a pass's inputs in front of the sorting kernel)
+  if (c->gang > 1) return std::min(c->gang, c->overlap);  // (no gang is larger than the passes in flight)
+  if (c->overlap <= c->hw_queues) return 1;
+  const int streams = std::min(GANG_STREAMS, c->hw_queues);
+  return (c->overlap + streams - 1) / streams;
+}
+static int gang_slots(const fsdp_ctx* c, int g) { return std::max(1, std::min(c->overlap, (c->overlap + g - 1) / g)); }
+// the first `slots` slots hold room for passes of g resident batches (their stores only grow; nothing is in flight)
+static int ensure_gang(fsdp_ctx* c, int g, int slots) {
+  const size_t n = (size_t)c->res.n_frames * (size_t)g, rows = c->res_rows * (size_t)g;
+  if (n > 0x7fffffffull || rows > 0x7fffffffull) {
+    c->err = "fsdp_time_runs: a ganged pass of " + std::to_string(g) + " batches exceeds the 32-bit frame / cone offsets";
+    return 1;
+  }
+  for (int i = 0; i < slots; i++) {
+    Work& q = c->slot[i];
+    if (i == 0 && c->gang_grown_from == 0 && n > q.buf.frames()) c->gang_grown_from = std::max<size_t>(1, q.buf.frames());
+    if (int rc = ensure_work(c, q, (int)n)) return rc;
+    if (!q.in.fits(n, rows, c->res.use_prev)) {
+      HIP_TRY(c, hipStreamSynchronize(q.stream));
+      HIP_TRY(c, q.in.reserve(n, rows, c->res.use_prev));
+    }
+  }
+  return 0;
+}
+// a ganged pass of `members` resident batches on slot q
+static int launch_gang(fsdp_ctx* c, Work& q, int members, Pass& pass) {
+  GangMember gm;
+  gm.off = c->res.d_off;
+  gm.cones = c->res.d_cones;
+  gm.poses = c->res.d_poses;
+  gm.prev = c->res.use_prev ? c->res.d_prev.get() : nullptr;
+  gm.n = c->res.n_frames;
+  gm.base = 0;  // (fsdp_upload rebases a slice's offsets)
+  gm.rows = c->res_rows;
+  pass.members.assign((size_t)members, gm);
+  q.in.n_frames = c->res.n_frames * members;
+  q.in.max_cones = c->res.max_cones;
+  q.in.use_prev = c->res.use_prev;
+  pass.in_flight = frames_in_flight(c, c->res.n_frames, false);  // (overlap x n, as for the single passes: the same packing)
+  return launch_pass(c, q, q.in, pass);
+}
+
 // one verified pass over the resident batch: afterwards the route expectations are exactly what this batch needs
 static int check_resident(fsdp_ctx* c) {
   if (c->res_checked || !c->resident || c->res.n_frames == 0) return 0;
@@ -2531,6 +2672,17 @@ int fsdp_time_reserve(fsdp_ctx* c, int iters) {
     for (int i = 0; i < c->overlap; i++)
       if (!c->primed[i])
         if ((rc = launch_pass(c, c->slot[i], c->res, Pass()))) return rc;
+    // a ganged region's slots get their room and run one gang each here, outside the region
+    if (const int g = gang_size(c); g > 1) {
+      const int slots = gang_slots(c, g);
+      if ((rc = sync_all(c))) return rc;
+      if ((rc = ensure_gang(c, g, slots))) return rc;
+      for (int i = 0; i < slots; i++) {
+        if (c->gang_primed[i] >= g) continue;
+        Pass warm;
+        if ((rc = launch_gang(c, c->slot[i], g, warm))) return rc;
+      }
+    }
     rc = sync_all(c);
     if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
@@ -2582,6 +2734,10 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
   rc = reserve_timing(c, iters);
   if (rc) return rc;
   hipEvent_t ev_begin = c->tev[need - 2], ev_end = c->tev[need - 1];
+  // (a ganged region's slots get their room in front of the region: fsdp_time_reserve has done it for a caller who reserves)
+  const int g = gang_size(c), slots = gang_slots(c, g);
+  if (g > 1)
+    if ((rc = ensure_gang(c, g, slots))) return rc;
   // the refit kernel's own clock readings: atomicMin over "all ones", atomicMax over zero (set before the region begins)
   const size_t kcap = c->d_kclock.capacity() / 2;  // (passes the block has room for: first readings, then last readings)
   HIP_TRY(c, hipMemsetAsync(c->d_kclock, 0xff, sizeof(unsigned long long) * kcap, c->stream));
@@ -2595,8 +2751,12 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
   }
   int n_stages = 0;
   c->tev_recorded.assign((size_t)iters, 0u);
-  for (int it = 0; it < iters; it++) {
-    const int si = (c->overlap > 1) ? (int)(c->turn++ % (unsigned)c->overlap) : 0;
+  c->tev_members.assign((size_t)iters, 0);
+  // Ganged (gang_size): passes it .. it + m - 1 are one launch chain on one of `slots` streams.  Its events and clock readings are
+  // those of pass `it`; the gang's other passes record none (tev_recorded = 0), so fsdp_time_results sums every launch once.
+  for (int it = 0; it < iters; it += g) {
+    const int m = std::min(g, iters - it);
+    const int si = g > 1 ? (int)(c->turn++ % (unsigned)slots) : (c->overlap > 1) ? (int)(c->turn++ % (unsigned)c->overlap) : 0;
     Work& q = c->slot[si];
     if (!started[si] && si != 0) HIP_TRY(c, hipStreamWaitEvent(q.stream, ev_begin, 0));
     started[si] = true;
@@ -2609,9 +2769,10 @@ int fsdp_time_runs(fsdp_ctx* c, int iters, float* ms_total, float* ms_stage) {
     t.clock_last = c->time_kernel_clock ? c->d_kclock + kcap + it : nullptr;
     Pass timed;
     timed.events = &t;
-    if ((rc = launch_pass(c, q, c->res, timed))) return rc;
+    if ((rc = g > 1 ? launch_gang(c, q, m, timed) : launch_pass(c, q, c->res, timed))) return rc;
     n_stages = t.n - 1;
     c->tev_recorded[it] = t.recorded;
+    c->tev_members[it] = m;
     last_of_slot[si] = it;
   }
   // the end event follows the last pass of every slot
@@ -2649,7 +2810,7 @@ int fsdp_time_kernel_clock(fsdp_ctx* c, double* ms_sum, int* launches) {
     const unsigned long long a = h[(size_t)it], b = h[kcap + (size_t)it];
     if (a == ~0ull || b == 0ull || b < a) continue;  // (a pass whose path stage was not the three-kernel form)
     *ms_sum += (double)(b - a) / (double)khz;
-    (*launches)++;
+    *launches += c->tev_members[(size_t)it];  // (the passes the reading covers: a gang's launch is one reading for all its members)
   }
   return 0;
 }
@@ -3627,9 +3788,9 @@ extern "C" int fsdp_debug_refit(fsdp_ctx* c, int32_t* n_knots, double* knots34, 
   std::vector<FitRec> recs((size_t)n);
   std::vector<PathMid> mids((size_t)n);
   const size_t fit_off = (size_t)ARENA_FIT * sizeof(double);  // frame_arena(): A.fit
-  HIP_TRY(c, hipMemcpy2DAsync(recs.data(), sizeof(FitRec), (const char*)q.buf.d_arena.get() + fit_off, sizeof(double) * ARENA_DOUBLES,
+  HIP_TRY(c, hipMemcpy2DAsync(recs.data(), sizeof(FitRec), (const char*)(q.buf.d_arena.get() + (size_t)c->last.offset * ARENA_DOUBLES) + fit_off, sizeof(double) * ARENA_DOUBLES,
                               sizeof(FitRec), (size_t)n, hipMemcpyDeviceToHost, q.stream));
-  HIP_TRY(c, hipMemcpyAsync(mids.data(), q.buf.d_mid, sizeof(PathMid) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
+  HIP_TRY(c, hipMemcpyAsync(mids.data(), q.buf.d_mid + c->last.offset, sizeof(PathMid) * (size_t)n, hipMemcpyDeviceToHost, q.stream));
   HIP_TRY(c, hipStreamSynchronize(q.stream));
   for (int i = 0; i < n; i++) {
     // only frames that went prep -> fit -> finish hold a record (the others took the exact route or ended earlier)
@@ -3648,7 +3809,7 @@ extern "C" int fsdp_debug_arena(fsdp_ctx* c, int frame, int offset, int count, d
   if (int rc = sync_all(c)) return rc;
   Work* q = debug_slot(c, "fsdp_debug_arena");
   if (!q || frame >= c->last.n) return 1;
-  HIP_TRY(c, copy_sync(c, out, q->buf.d_arena + (size_t)frame * ARENA_DOUBLES + offset, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
+  HIP_TRY(c, copy_sync(c, out, q->buf.d_arena + ((size_t)c->last.offset + (size_t)frame) * ARENA_DOUBLES + offset, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -1343,6 +1343,54 @@ struct StageIn {
   int32_t base = 0;                   // src_off[0]: src_cones points at row `base` of the caller's array, the device copies start at 0
 };
 
+// A ganged pass (fsdp_lib.hip fsdp_time_runs): one pass over the frames of up to GANG_MAX batches ("members"), whose inputs lie
+// in as many places (device memory or page-locked host memory).  The sorting kernel's gang twins stage every member's frames into
+// the slot's device copies one behind the other — gang frame first_frame + f is member frame f, its cones start at row
+// first_row + (src_off[f] - base) — so every kernel behind them sees one batch of n_frames frames and knows nothing of members.
+constexpr int GANG_MAX = 32;  // (= FSDP_MAX_OVERLAP)
+struct StageMember {
+  const int32_t* src_off = nullptr;
+  const double* src_cones = nullptr;  // row `base` of the member's cone array
+  const double* src_poses = nullptr;
+  const double* src_prev = nullptr;   // optional previous paths (member frames,40,4): all members have them or none
+  int32_t base = 0;                   // src_off[0]
+  int32_t first_frame = 0;            // the member's first frame in the gang
+  int32_t first_row = 0;              // the member's first cone row in the gang's copy
+  int32_t pad = 0;
+};
+struct StageGang {
+  StageMember m[GANG_MAX];
+  int32_t* dst_off = nullptr;
+  double* dst_cones = nullptr;
+  double* dst_poses = nullptr;
+  double* dst_prev = nullptr;
+  int n_members = 0;
+  int n_frames = 0;  // of all members
+};
+// the wavefront's view of its frame's member as a StageIn (scalar search: `frame` is the workgroup's index); *local: the frame's
+// index in the member's arrays.  dst_* are advanced to the member's first gang frame, so that StageIn's one index serves both
+// sides; the cone copy stays whole (base takes the member's first row into the rebased offset).  sort_frame itself is unchanged:
+// the gang twins hand it the member's view, the local frame and the SortOut block from the member's first frame on.
+__device__ inline StageIn gang_member(const StageGang& g, int frame, int* local) {
+  int k = 0;
+  for (int i = 1; i < g.n_members; i++)
+    if (frame >= g.m[i].first_frame) k = i;
+  const StageMember& mb = g.m[k];
+  StageIn st;
+  st.src_off = mb.src_off;
+  st.src_cones = mb.src_cones - 3 * (ptrdiff_t)mb.first_row;  // (read only at rows >= first_row: one rebased offset serves source and copy)
+  st.src_poses = mb.src_poses;
+  st.src_prev = mb.src_prev;
+  st.dst_off = g.dst_off + mb.first_frame;
+  st.dst_cones = g.dst_cones;
+  st.dst_poses = g.dst_poses + 4 * (size_t)mb.first_frame;
+  st.dst_prev = g.dst_prev + (size_t)(PATH_POINTS * 4) * (size_t)mb.first_frame;
+  st.n_frames = g.n_frames - mb.first_frame;  // (the gang's last frame writes the closing offset)
+  st.base = mb.base - mb.first_row;
+  *local = frame - mb.first_frame;
+  return st;
+}
+
 // The cache entry a frame leaves for its planner's next call (rule of core_trace_sorter.py:189-195), and the frame's hit codes.
 // A frame the reference raises on (101 / 102: sort_left_right never reaches the assignment) keeps the previous entry; a
 // capacity refusal drops it (the next call misses); a frame beyond the LDS capacities is left to sort_big_kernel, which reads
@@ -1712,6 +1760,38 @@ __global__ void __launch_bounds__(64) sort_big_kernel_cached(const int32_t* __re
     sort_frame<SortSharedBig, true>(S, *prm, big[1 + i], cone_offsets, cones_xyt, poses, out, StageIn(), &cache);
     __syncthreads();
   }
+}
+
+// ---- the gang twins of the two plain kernels (StageGang above): the same frame code behind a prologue that finds the frame's
+// member; out / big are the gang's, indexed by gang frame.  The twins' frame state is a type of its own, so that every template of
+// the stage is instantiated for them apart: the plain kernels stay the only callers of their instantiations and compile to the
+// code they had without the twins (a second caller changes what the compiler inlines into the first).  This rests on the
+// compiler's behaviour, not on the language: whoever touches the twins or updates the compiler repeats the per-symbol disassembly
+// comparison of profiles/gang_replay.md section 6 (recipe there) against the commit before. ----
+struct SortSharedGang : SortShared {};
+struct SortShared128Gang : SortShared128 {};
+template <class SH>
+__device__ __forceinline__ void sort_kernel_gang_body(SH& S, const StageGang& gang, SortOut* __restrict__ out, int* __restrict__ big,
+                                                      const Params* __restrict__ prm) {
+  const int frame = blockIdx.x;
+  if (frame >= gang.n_frames) return;
+  PROF_INIT();
+  int local;
+  const StageIn st = gang_member(gang, frame, &local);
+  sort_frame<SH>(S, *prm, local, st.dst_off, st.dst_cones, st.dst_poses, out + (frame - local), st);
+  if (big != nullptr && lane_id() == 0 && (out[frame].status == ST_OVERFLOW_CONES || out[frame].status == ST_OVERFLOW_ENDS))
+    big[1 + atomicAdd(&big[0], 1)] = frame;
+  PROF_FLUSH();
+}
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3)))
+sort_kernel_gang(StageGang gang, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm) {
+  __shared__ SortSharedGang S;
+  sort_kernel_gang_body(S, gang, out, big, prm);
+}
+__global__ void __launch_bounds__(64) FSDP_WAVES_PER_EU(SORT_WAVES_128)
+sort_kernel_128_gang(StageGang gang, SortOut* __restrict__ out, int* __restrict__ big, const Params* __restrict__ prm) {
+  __shared__ SortShared128Gang S;
+  sort_kernel_gang_body(S, gang, out, big, prm);
 }
 #endif  // FSDP_SEQUENCE_CACHE_UNIT, FSDP_SORT_HISTORY_UNIT
 

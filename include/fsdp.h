@@ -452,10 +452,21 @@ int fsdp_download(fsdp_ctx* ctx, fsdp_frame_result* results);
  * fsdp_sync waits for all passes in flight, fsdp_download returns the most recent one.  depth 1 (default) = strictly one
  * pass after the other.  Every stream takes one of the HIP runtime's hardware queues (environment variable
  * GPU_MAX_HW_QUEUES, default 4): with more streams than queues two passes share a queue and serialize — raise
- * GPU_MAX_HW_QUEUES above the depth (bench.py sets 16 for its depth of 10; a skidpad context uses one stream whatever
- * the depth: its slots only hold the steps' buffers).  Every extra depth costs one more set of
+ * GPU_MAX_HW_QUEUES above the depth where the process may (bench.py asks for 22 for its depth of 20; a skidpad context uses one
+ * stream whatever the depth: its slots only hold the steps' buffers).  Every extra depth costs one more set of
  * buffers (~0.1 MB per frame).  Measured at 4096 frames x 128 cones: the steady rate saturates at depth 8; a run of 20
- * passes is fastest with 10 in flight (two full rounds instead of 8 + 8 + 4). */
+ * passes is fastest with 10 in flight (two full rounds instead of 8 + 8 + 4).
+ * Fewer queues than streams (option "hw_queues" says how many the runtime grants; the library reads no environment, the Python
+ * binding passes GPU_MAX_HW_QUEUES on): the replay of the resident batch by fsdp_time_runs does not depend on the variable.  With
+ * depth > hw_queues it issues its passes as *gangs*: g = ceil(depth / S) passes (S = min(4, hw_queues) streams) become one pass
+ * over g x n frames on one of the first S slots' streams — the sorting kernel's gang twins stage every member's frames into the
+ * slot's own input store, every kernel behind them runs unchanged on the larger batch — so a few chip-filling launch chains
+ * replace many small ones that would queue up behind each other (depth 20 under 4 queues: 4.1 -> 6.3 M frames/s).  Results are
+ * those of the single passes, bit for bit; frames in flight, and with them the packing, stay depth x n.  The first S slots hold
+ * room for g x n frames each on top of the per-slot buffers (device memory at most doubles: 20 x 4096 frames, ~7 GB -> ~13 GB).
+ * fsdp_run, tickets, blocking calls, sequence passes and skidpad keep their launches, and so do contexts with
+ * use_unknown_cones off (their filter kernels read a pass's inputs in front of the sorting kernel).  depth <= hw_queues: exactly
+ * the launches of single passes. */
 #define FSDP_MAX_OVERLAP 32
 int fsdp_set_overlap(fsdp_ctx* ctx, int depth);
 
@@ -477,6 +488,11 @@ int fsdp_route_stats(fsdp_ctx* ctx, int* expect_big, int* expect_retry, long lon
  *   "no_sort128"      1: the sorting kernel's 255-cone state also for frames of up to 128 cones
  *   "retry_pack_min"  retry lists longer than this run four frames per wavefront in path_retry_kernel (default 512)
  *   "plan_chunks"     k > 1: every blocking call is cut into up to k chunks of >= 512 frames; 1: never (default: four from 16 384 frames)
+ *   "hw_queues"       hardware queues the HIP runtime grants the process (default 4, HIP's own default; _capi.Context passes the
+ *                     environment's GPU_MAX_HW_QUEUES): decides whether fsdp_time_runs gangs its passes (fsdp_set_overlap above)
+ *   "gang"            0: gangs by overlap depth and hw_queues (default); 1: never; k > 1: gangs of min(k, depth) passes on
+ *                     ceil(depth / k) streams (measurements; the memory bound stated at fsdp_set_overlap holds for the default
+ *                     policy — a forced size may take up to three times the per-slot buffers)
  *   "poison"          1: every pass first fills its intermediates and scratch with 0xFF bytes (tests: no result depends on what a
  *                     buffer held before — tests/test_streaming_gpu.py)
  *   "skid_group"      steps per launch of a skidpad replay that submits ahead (default: from the instance count)
@@ -488,7 +504,11 @@ int fsdp_set_option(fsdp_ctx* ctx, const char* name, long long value);
  * synchronisation in between) and time them with HIP events recorded on the streams the kernels run on.
  * ms_total: whole region; ms_stage[FSDP_MAX_STAGES]: summed durations of every kernel of a pass, in launch order (events
  * around each launch; with overlap these include the time a launch shares the chip with the other slots' kernels);
- * unused entries are 0 and fsdp_stage_names names the used ones.  Either pointer may be NULL. */
+ * unused entries are 0 and fsdp_stage_names names the used ones.  Either pointer may be NULL.
+ * A ganged region (fsdp_set_overlap above) records the events of a gang once, in the event slots of the gang's first pass; the
+ * gang's other passes record none.  ms_stage therefore sums the duration of every launch exactly once — a launch now covers g
+ * passes — and dividing it by `iters` still gives the time per pass.  The refit kernel's own clock readings
+ * (fsdp_time_kernel_clock) follow the same rule: one reading per gang, which counts for all its passes. */
 #define FSDP_MAX_STAGES 8
 int fsdp_time_runs(fsdp_ctx* ctx, int iters, float* ms_total, float* ms_stage);
 /* The same in three steps, for a caller that puts its own wall clock around the passes: fsdp_time_reserve creates the
@@ -510,7 +530,8 @@ int fsdp_time_results(fsdp_ctx* ctx, float* ms_total, float* ms_stage);
  * region notes when its first wavefront started and its last one ended (the device's constant-rate counter, s_memrealtime),
  * i.e. the duration a kernel trace reports — without the time the launch waited in its hardware queue, which an event bracket
  * on the stream includes when twenty streams share the command processor.  *ms_sum = summed duration, *launches = how many
- * launches it covers (0 when the region ran the one-kernel path stage, or was timed without bit 1 of fsdp_time_detail).
+ * passes' launches it covers (a ganged launch is one reading that covers its g passes, so ms_sum / launches stays the time
+ * per pass; 0 when the region ran the one-kernel path stage, or was timed without bit 1 of fsdp_time_detail).
  * No counterpart in the reference (measurement only). */
 int fsdp_time_kernel_clock(fsdp_ctx* ctx, double* ms_sum, int* launches);
 /* What the link between this GPU and the host carries for page-locked buffers of `bytes` bytes, hipMemcpyAsync x iters: host ->
