@@ -12,4 +12,4 @@ from .skidpad import SkidpadBatch  # noqa: F401
 from .acceleration import AccelerationBatch  # noqa: F401
 from .multi import MultiPlanner, MultiSkidpadBatch  # noqa: F401
 from .device import DeviceArray, DeviceFleet, SkidpadDeviceFleet, as_device_ptr, device_array  # noqa: F401
-from ._capi import COMPACT_DTYPE, STANDARD, WIDE, Context, FsdpError, PATH_RESULT_DTYPE, RESULT_DTYPE, decision_margin, pinned_copy, pinned_empty  # noqa: F401
+from ._capi import COMPACT_DTYPE, STANDARD, WIDE, Context, FsdpError, PATH_RESULT_DTYPE, RESULT_DTYPE, decision_margin, pack_path_table, pinned_copy, pinned_empty  # noqa: F401

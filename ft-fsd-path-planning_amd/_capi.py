@@ -233,6 +233,11 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     # (ctx, n_frames, cone_capacity, counts, cones, poses, prev_paths, paths, status, next_prev, records, after_stream, ticket)
     lib.fsdp_submit_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.POINTER(ctypes.c_longlong)]
     lib.fsdp_ticket_stream_wait.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
+    # per-frame global paths: (ctx, xy, path_offsets, n_paths); fsdp_submit / fsdp_submit_device with path_ids behind prev_paths
+    lib.fsdp_set_global_path_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    lib.fsdp_submit_paths.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.POINTER(ctypes.c_longlong)]
+    lib.fsdp_submit_paths_compact.argtypes = lib.fsdp_submit_paths.argtypes
+    lib.fsdp_submit_device_paths.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.POINTER(ctypes.c_longlong)]
     # (ctx, n_instances, cone_capacity, counts, cones, poses, reset, paths, status, info, records, after_stream, ticket)
     lib.fsdp_skidpad_submit_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.POINTER(ctypes.c_longlong)]
     got = (ctypes.c_int32 * 4)()
@@ -261,7 +266,18 @@ EXPORTED_SYMBOLS = [
     "fsdp_device_alloc", "fsdp_device_free", "fsdp_device_write", "fsdp_device_read", "fsdp_device_owns", "fsdp_stream_create", "fsdp_stream_destroy",
     "fsdp_stream_wait_stream", "fsdp_submit_device", "fsdp_ticket_stream_wait", "fsdp_sort_batch_history",
     "fsdp_skidpad_submit_device",
+    "fsdp_set_global_path_table", "fsdp_submit_paths", "fsdp_submit_paths_compact", "fsdp_submit_device_paths",
 ]
+
+
+def pack_path_table(paths):
+    """A list of (k_i, 2) polylines as fsdp_set_global_path_table takes it -> (xy (sum k_i, 2) float64, offsets (n + 1) int32); a
+    polyline may be empty."""
+    rows = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 2) for p in paths]
+    off = np.zeros(len(rows) + 1, np.int32)
+    off[1:] = np.cumsum([len(r) for r in rows])
+    xy = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, 2))
+    return xy, off
 
 
 class CandVerdict(enum.IntEnum):
@@ -672,11 +688,13 @@ class Context:
         return results, [centers[i, : counts[i]].copy() for i in range(n)]
 
     # streams of batches: several different batches in flight (fsdp_submit / fsdp_collect)
-    def submit(self, offsets, cones, poses, prev_paths=None, out=None, compact: bool = False) -> Ticket:
+    def submit(self, offsets, cones, poses, prev_paths=None, out=None, compact: bool = False, path_ids=None) -> Ticket:
         """Enqueue one batch (H2D, the kernels of a pass, D2H) on the next pass slot and return at once.  Arrays made by
         ``pinned_empty`` / ``pinned_copy`` are transferred asynchronously; others are accepted but staged.  ``out``: the
         self.result_dtype (compact: self.compact_dtype) array the results go to (default: a new pinned array).  Raises when
-        every slot holds a ticket.  The arrays must stay untouched until collect()."""
+        every slot holds a ticket.  The arrays must stay untouched until collect().
+        path_ids (fsdp_submit_paths): (n) int32, one entry of the context's path table (set_global_path_table) per frame — the frame
+        is planned along that path — or -1 for a frame that plans from its cones; an id that names nothing raises FsdpError."""
         offsets, cones, poses, n = self._prep(offsets, cones, poses)
         prev = None if prev_paths is None else self.pad_paths(prev_paths)
         dt = self.compact_dtype if compact else self.result_dtype
@@ -684,10 +702,18 @@ class Context:
             out = pinned_empty(n, dt)
         assert out.dtype == dt and len(out) == n and out.flags.c_contiguous
         t = ctypes.c_longlong(-1)
-        fn = self._lib.fsdp_submit_compact if compact else self._lib.fsdp_submit
-        self._check(fn(self._h, n, offsets.ctypes.data, cones.ctypes.data if len(cones) else None, poses.ctypes.data,
-                       None if prev is None else prev.ctypes.data, out.ctypes.data, ctypes.byref(t)), "fsdp_submit")
-        return Ticket(int(t.value), out, None, (offsets, cones, poses, prev))
+        cp, pp = cones.ctypes.data if len(cones) else None, None if prev is None else prev.ctypes.data
+        if path_ids is None:
+            fn = self._lib.fsdp_submit_compact if compact else self._lib.fsdp_submit
+            self._check(fn(self._h, n, offsets.ctypes.data, cp, poses.ctypes.data, pp, out.ctypes.data, ctypes.byref(t)), "fsdp_submit")
+            return Ticket(int(t.value), out, None, (offsets, cones, poses, prev))
+        self._host_arrays(path_ids)
+        ids = np.ascontiguousarray(path_ids, dtype=np.int32)
+        if ids.shape != (n,):
+            raise ValueError(f"path_ids: {ids.shape} for {n} frames")
+        fn = self._lib.fsdp_submit_paths_compact if compact else self._lib.fsdp_submit_paths
+        self._check(fn(self._h, n, offsets.ctypes.data, cp, poses.ctypes.data, pp, ids.ctypes.data, out.ctypes.data, ctypes.byref(t)), "fsdp_submit_paths")
+        return Ticket(int(t.value), out, None, (offsets, cones, poses, prev, ids))
 
     def submit_slice(self, lo: int, hi: int, offsets, cones, poses, prev, out, compact: bool = False) -> Ticket:
         """Frames [lo, hi) of a batch that is already in the ABI's layout (int32 offsets of the WHOLE batch, (N, 3) cones,
@@ -739,14 +765,17 @@ class Context:
 
     # device tickets: batches and results in the caller's GPU memory (fsdp_submit_device; device.py)
     def submit_device(self, counts, cones, poses, prev=None, paths=None, status=None, next_prev=None, records=False, after_stream=None,
-                      cone_capacity: int | None = None) -> Ticket:
+                      cone_capacity: int | None = None, path_ids=None) -> Ticket:
         """fsdp_submit_device: one batch whose arrays are device memory of this context's GPU — DeviceArrays or any objects with
         ``__cuda_array_interface__``: counts (n) int32, cones (n, cone_capacity, 3) float64 (None with cone_capacity = 0), poses (n, 4),
         prev (n, path_points, 4) or None.  Missing outputs are allocated as DeviceArrays: paths (n, path_points, 4), status (n) int32;
         next_prev only when given (it may be ``prev``); records: True, or a device array of n compact records (uint8 (n, itemsize)).
         after_stream: the producer's hipStream_t (int) or None — the ONLY ordering against the arrays' producer: the `stream` entry of an
         array's ``__cuda_array_interface__`` is not read (with None the inputs must be complete when the call is made).  collect() returns the dict of the output arrays.  Every array must
-        stay alive until collect (the ticket holds them)."""
+        stay alive until collect (the ticket holds them).
+        path_ids (fsdp_submit_device_paths): a device (n) int32 array, one entry of the context's path table (set_global_path_table) per
+        frame, or -1 for a frame that plans from its cones.  The host cannot read it: an id that names nothing is planned as -1, and
+        collect() raises FsdpError naming the lowest such frame."""
         from .device import DeviceArray, DeviceTicket, as_device_ptr
 
         if isinstance(counts, np.ndarray) or not hasattr(counts, "__cuda_array_interface__"):
@@ -765,12 +794,18 @@ class Context:
             records = None
         ptr = lambda a, shape, dt, writable=False: None if a is None else as_device_ptr(a, shape, dt, writable=writable)
         t = ctypes.c_longlong(-1)
-        self._check(self._lib.fsdp_submit_device(
-            self._h, n, cap, ptr(counts, (n,), np.int32), ptr(cones if cap > 0 else None, (n, cap, 3), np.float64), ptr(poses, (n, 4), np.float64),
-            ptr(prev, (n, rows, 4), np.float64), ptr(paths, (n, rows, 4), np.float64, True), ptr(status, (n,), np.int32, True),
-            ptr(next_prev, (n, rows, 4), np.float64, True), ptr(records, (n, rec), np.uint8, True), after_stream, ctypes.byref(t)), "fsdp_submit_device")
+        ins = [ptr(counts, (n,), np.int32), ptr(cones if cap > 0 else None, (n, cap, 3), np.float64), ptr(poses, (n, 4), np.float64),
+               ptr(prev, (n, rows, 4), np.float64)]
+        outs = [ptr(paths, (n, rows, 4), np.float64, True), ptr(status, (n,), np.int32, True), ptr(next_prev, (n, rows, 4), np.float64, True),
+                ptr(records, (n, rec), np.uint8, True), after_stream, ctypes.byref(t)]
+        if path_ids is None:
+            self._check(self._lib.fsdp_submit_device(self._h, n, cap, *ins, *outs), "fsdp_submit_device")
+        else:
+            if isinstance(path_ids, np.ndarray) or not hasattr(path_ids, "__cuda_array_interface__"):
+                raise TypeError("submit_device takes path_ids as a device array (host ids go through submit)")
+            self._check(self._lib.fsdp_submit_device_paths(self._h, n, cap, *ins, ptr(path_ids, (n,), np.int32), *outs), "fsdp_submit_device_paths")
         out = {"paths": paths, "status": status, "next_prev": next_prev, "records": records}
-        return DeviceTicket(int(t.value), out, None, (counts, cones, poses, prev))
+        return DeviceTicket(int(t.value), out, None, (counts, cones, poses, prev, path_ids))
 
     def stream_wait(self, ticket: Ticket, stream):
         """fsdp_ticket_stream_wait: whatever is enqueued on ``stream`` (a hipStream_t as an int) afterwards runs behind the ticket."""
@@ -830,6 +865,16 @@ class Context:
             return
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
         self._check(self._lib.fsdp_set_global_path(self._h, _dp(xy), ctypes.c_int(len(xy))), "fsdp_set_global_path")
+
+    def set_global_path_table(self, paths):
+        """fsdp_set_global_path_table: a list of (k_i, 2) polylines (k_i = 0 allowed) that the frames of submit(path_ids=) /
+        submit_device(path_ids=) name by index; None or an empty list clears the table."""
+        if paths is None or len(paths) == 0:
+            self._check(self._lib.fsdp_set_global_path_table(self._h, None, None, 0), "fsdp_set_global_path_table")
+            return
+        self._host_arrays(*paths)
+        xy, off = pack_path_table(paths)
+        self._check(self._lib.fsdp_set_global_path_table(self._h, xy.ctypes.data if len(xy) else None, off.ctypes.data, len(off) - 1), "fsdp_set_global_path_table")
 
     def set_previous_paths(self, prev_paths):
         """fsdp_set_previous_paths: (n,horizon,4) previous paths of the resident batch's frames (None = fresh planners again)."""

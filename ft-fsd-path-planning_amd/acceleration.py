@@ -138,8 +138,9 @@ class AccelerationBatch:
     What runs where: the relocalization (acceleration_relocalization.py:120-170) is a one-off line fit per planner and stays the
     per-planner host code above (`AccelerationRelocalizer.attempt`, only for planners that are not relocalized yet); everything a
     step does for every planner every time — the pose into the known frame, the path stage along the known path, the path back
-    into the caller's frame (full_pipeline.py:118-136,178-194) — is one vectorised transform, ONE batched launch sequence on the
-    GPU (fsdp_plan_batch_sequential: a planner's previous path travels with it) and one vectorised transform back."""
+    into the caller's frame (full_pipeline.py:118-136,178-194) — is one vectorised transform, ONE pass on the GPU for the planners
+    before and after relocalization alike (fsdp_submit_paths: the known path is entry 0 of the context's path table, a planner
+    that is not relocalized yet carries id -1; a planner's previous path travels with it) and one vectorised transform back."""
 
     def __init__(self, n_planners: int, mission=None, seeds=None, device: int | None = None, params: dict | None = None):
         from . import _capi
@@ -153,13 +154,13 @@ class AccelerationBatch:
         if len(seeds) != self.n:
             raise ValueError("one relocalization seed per planner")
         self.relocalizers = [AccelerationRelocalizer(s) for s in seeds]
-        # two contexts: planners that are relocalized plan along the known path, the others from (no) cones and their previous path
-        self._known = _capi.Context(device=device, mission=int(self.mission), params=params)
-        self._known.set_global_path(known_path())
-        self._blind = None
-        self._device, self._params = device, params
-        self.horizon = self._known.horizon
-        self._prev = np.repeat(self._known.default_path()[None, : self.horizon], self.n, axis=0)  # previous_paths[-1] of a fresh planner
+        # one context whose path table holds the known path: planners that are relocalized plan along entry 0, the others (id -1)
+        # from (no) cones and their previous path — in the same pass (fsdp_submit_paths)
+        self._ctx = _capi.Context(device=device, mission=int(self.mission), params=params)
+        self._ctx.set_global_path_table([known_path()])
+        self.horizon = self._ctx.horizon
+        self._prev = np.repeat(self._ctx.default_path()[None, : self.horizon], self.n, axis=0)  # previous_paths[-1] of a fresh planner
+        self._no_cones = (np.zeros(self.n + 1, np.int32), np.zeros((0, 3)))
         self._orig = np.zeros((self.n, 2))
         self._angle = np.zeros(self.n)
         self._reloc = np.zeros(self.n, dtype=bool)
@@ -196,20 +197,11 @@ class AccelerationBatch:
             pose_k[k, 0], pose_k[k, 1] = rotate_single_points(d[:, 0], d[:, 1], -self._angle[k])
             yaw_k = yaw - self._angle[k]
             pose_k[k, 2], pose_k[k, 3] = np.cos(yaw_k), np.sin(yaw_k)
-        res_path = np.full((n, self.horizon, 4), np.nan)
-        status = np.zeros(n, dtype=np.int32)
-        empty_off = np.zeros(1, np.int32)
-        for sel, ctx in ((k, self._known), (~k, None)):
-            if not sel.any():
-                continue
-            if ctx is None:
-                if self._blind is None:
-                    self._blind = _capi.Context(device=self._device, mission=int(self.mission), params=self._params)
-                ctx = self._blind
-            m = int(sel.sum())
-            r = ctx.plan_batch_sequential(np.zeros(m + 1, np.int32), np.zeros((0, 3)), pose_k[sel], self._prev[sel])
-            status[sel] = r["status"]
-            res_path[sel] = r["path"][:, : self.horizon]
+        # one pass for all planners: the known path for the relocalized ones, no global path for the others
+        ids = np.where(k, 0, -1).astype(np.int32)
+        r = self._ctx.collect(self._ctx.submit(*self._no_cones, pose_k, prev_paths=self._prev, compact=True, path_ids=ids))
+        status = r["status"].astype(np.int32)
+        res_path = r["path"][:, : self.horizon].copy()
         ok = status == 0
         self._prev[ok] = res_path[ok]  # the path stage keeps its history in the frame it computed in
         res_path[~ok] = np.nan
@@ -222,6 +214,4 @@ class AccelerationBatch:
         return res_path, status
 
     def close(self):
-        self._known.close()
-        if self._blind is not None:
-            self._blind.close()
+        self._ctx.close()

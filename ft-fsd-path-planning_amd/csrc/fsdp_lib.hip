@@ -33,6 +33,7 @@
 #include "device_io_launch.h"   // (the kernels of a device ticket are a translation unit of their own: device_io_lib.hip)
 #include "skid_device_launch.h"  // (the kernels of a skidpad device ticket live in that unit too)
 #include "sort_history_launch.h"  // (the history instantiations of the sorting kernels likewise: sort_history_lib.hip)
+#include "gpath_table_launch.h"   // (the path wrappers of a pass with per-frame global paths likewise: gpath_table_lib.hip)
 
 using namespace fsdp;
 
@@ -139,6 +140,7 @@ struct Work {
     // a skidpad device ticket (fsdp_skidpad_submit_device): its step's records, or NULL
     fsdp_skidpad_info* skid_info = nullptr;
     fsdp_path_result* skid_records = nullptr;
+    const int32_t* path_ids = nullptr;  // fsdp_submit_device_paths: the frames' path ids (n), or NULL
   };
   // tickets of fsdp_submit / fsdp_skidpad_submit / fsdp_submit_sequence queued on this slot's stream (id -1: free entry).  A ticket
   // holds the whole description of its pass: enqueue_ticket launches the first pass and fsdp_collect's rerun from it alone.
@@ -166,8 +168,12 @@ struct Work {
     int cache_lo = -1;                     // >= 0: a chunk of a lock-step call that advances the sorting cache (the _cached sorting
                                            // kernels); its frame 0 is this planner
     DevPass dev;                           // a device ticket's pass
+    const int32_t* path_ids = nullptr;     // fsdp_submit_paths: the caller's path ids (n), checked against the table by the submit; a
+                                           // repeated pass reads them again like the batch itself
+    PinnedBuf<int32_t> h_ids;              // pinned + mapped: pageable path ids are staged here and read by the path kernels themselves
     PinnedBuf<int32_t> h_bad;              // pinned + mapped: the lowest frame of a device ticket whose count was out of range, or -1;
-                                           // [1], a skidpad device ticket: 1 when a planner was not relocalized after the step
+                                           // [1], a skidpad device ticket: 1 when a planner was not relocalized after the step;
+                                           // [2], fsdp_submit_device_paths: the lowest frame whose path id was out of range, or -1
     unsigned reloc_epoch = 0;              // a skidpad step: fsdp_ctx::skid_reloc_epoch when it was submitted
     Event after;                           // a device ticket: recorded on the producer's stream, waited for by the slot's
     Event done;                            // recorded behind the ticket's last command
@@ -180,6 +186,7 @@ struct Work {
       sq = SeqPass();
       dev = DevPass();
       cache_lo = -1;
+      path_ids = nullptr;
     }
   } tk[SLOT_QUEUE];
 };
@@ -210,6 +217,11 @@ struct fsdp_ctx {
   DeviceBuf<double> d_chord;         // (40,2) almost-straight chord (trivial path of the skidpad mission)
   DeviceBuf<double> d_gpath;         // PathPlanner.global_path (n_gpath,2), or NULL
   int n_gpath = 0;
+  // fsdp_set_global_path_table: n_gpt polylines one behind the other, path k the points [off[k], off[k + 1]); read only by a pass
+  // that carries path ids (fsdp_submit_paths, fsdp_submit_device_paths)
+  DeviceBuf<double> d_gpt_xy;        // (off[n_gpt], 2); at least one point's room, so that an empty entry still has an address
+  DeviceBuf<int32_t> d_gpt_off;      // (n_gpt + 1)
+  int n_gpt = 0;
   // fsdp_set_option (include/fsdp.h): what a test or a measurement may pin; 0 = the library's own choice
   int force_path_mode = 0;    // "path_mode": 0 = by batch size; 1 = one kernel (64 lanes per frame); 2 = three kernels
   int fit_g = 4;              // "fit_g": lanes per frame of fit_kernel when frames are packed: 4 = exactly the Givens quad, sixteen
@@ -617,8 +629,32 @@ static long long frames_in_flight(const fsdp_ctx* c, int n, bool ticket) {
   return sum;
 }
 
+// one launch of a pass with per-frame global paths (gpath_table_launch.h); ids: the pass's path ids as the GPU addresses them
+static void launch_gpt(fsdp_ctx* c, Work& q, const Inputs& in, const int32_t* ids, int form, unsigned blocks = 0) {
+  fsdp_gpt_launch_args a;
+  a.form = form;
+  a.n_frames = in.n_frames;
+  a.blocks = blocks;
+  a.poses = in.d_poses;
+  a.matched = q.buf.d_match;
+  a.default_path = c->d_default_path;
+  a.prev_paths = in.use_prev ? in.d_prev : nullptr;
+  a.table_xy = c->d_gpt_xy;
+  a.table_off = c->d_gpt_off;
+  a.n_paths = c->n_gpt;
+  a.ids = ids;
+  a.arena = q.buf.d_arena;
+  a.out = q.buf.d_path;
+  a.mid = q.buf.d_mid;
+  a.retry = q.buf.d_retry;
+  a.prm = c->d_params;
+  fsdp_gpt_launch(q.stream, &a);
+}
+
 // the path stage's fast kernels (no route, no assembly); returns whether it was the three-kernel form
-static bool launch_path(fsdp_ctx* c, Work& q, const Inputs& in, StageEvents* t, std::string& names, long long in_flight) {
+// ids: not NULL for a pass with per-frame global paths — the TABLE twins of the wrappers that read a global path, and of the three-kernel
+// forms the one a context-wide path takes (32 knots per fit, 8 lanes per frame), for all of its frames: those with id -1 ride along
+static bool launch_path(fsdp_ctx* c, Work& q, const Inputs& in, StageEvents* t, std::string& names, long long in_flight, const int32_t* ids = nullptr) {
   const double* prev = in.use_prev ? in.d_prev : nullptr;
   const int n = in.n_frames;
   // (the packed kernels hold degree-3 fits only: a context with max_deg < 3 plans every batch with the one-kernel stage)
@@ -631,6 +667,11 @@ static bool launch_path(fsdp_ctx* c, Work& q, const Inputs& in, StageEvents* t, 
     // degrees, 32 knots per fit, the scaling-free divisions; what that form cannot hold goes to the exact kernel like any other
     // frame the packed kernels hand on) instead of one frame per wavefront.
     const bool mono16 = c->force_path_mode != 1 && c->params.max_deg != 3 && in_flight > PATH_SMALL_BATCH;
+    if (ids) {
+      launch_gpt(c, q, in, ids, mono16 ? PATH_G_LATENCY : PATH_G_SMALL);
+      names += mono16 ? "path_table_kernel<16>," : "path_table_kernel<64>,";
+      return split;
+    }
     if (mono16)
       hipLaunchKernelGGL(path_kernel<PATH_G_LATENCY>, dim3((n + WAVE / PATH_G_LATENCY - 1) / (WAVE / PATH_G_LATENCY)), dim3(WAVE), 0, q.stream, n, in.d_poses,
                          q.buf.d_match, c->d_default_path, prev, c->d_gpath, c->n_gpath, q.buf.d_arena, q.buf.d_path, q.buf.d_retry, c->d_params);
@@ -645,13 +686,19 @@ static bool launch_path(fsdp_ctx* c, Work& q, const Inputs& in, StageEvents* t, 
   // polylines that need 17-32 knots (87 % of such frames; never more than 32 on the reference's tables): the WIDE instantiations
   // of the three kernels — 32 knots per fit in the frame's LDS workspace, eight lanes per frame — keep them on the packed kernels
   // instead of sending every frame to the exact one.
-  if (c->n_gpath > 0) {
-    launch_prep<8, WIDE_KNOTS>(c, q, in, prev);
+  // (a pass with ids: the same three, the first one as its TABLE twin — one sequence of launches for both, so that the kernels
+  // of this translation unit keep their order in the code object)
+  if (ids || c->n_gpath > 0) {
+    if (ids)
+      launch_gpt(c, q, in, ids, PATH_G_SPLIT);
+    else
+      launch_prep<8, WIDE_KNOTS>(c, q, in, prev);
     mark(q, t, MARK_MAIN);
     launch_fit<8, WIDE_KNOTS>(c, q, n, t);
     mark(q, t, MARK_MAIN);
     launch_finish<8, WIDE_KNOTS>(c, q, n);
-    names += "path_prep_kernel<8,32>,fit_kernel<8,32>,path_finish_kernel<8,32>,";
+    names += ids ? "path_table_prep_kernel<8,32>," : "path_prep_kernel<8,32>,";
+    names += "fit_kernel<8,32>,path_finish_kernel<8,32>,";
     return split;
   }
   const bool packed = c->force_pack ? c->force_pack == 2 : in_flight >= PACK_FRAMES;
@@ -681,10 +728,14 @@ static bool launch_path(fsdp_ctx* c, Work& q, const Inputs& in, StageEvents* t, 
 // nothing to compute, but on a chip full of other passes' wavefronts the last of them was dispatched ~1.7 ms later, and the pass's
 // assembly waits for it (the stream of different batches: 355 such launches, 12 % of the summed kernel time of the trace).  The kernel
 // walks its list grid-stride: any grid plans any list.
-static void launch_path_retry(fsdp_ctx* c, Work& q, const Inputs& in, bool sized = false) {
+static void launch_path_retry(fsdp_ctx* c, Work& q, const Inputs& in, bool sized = false, const int32_t* ids = nullptr) {
   const double* prev = in.use_prev ? in.d_prev : nullptr;
   int rb = in.n_frames < 1024 ? in.n_frames : 1024;  // one wavefront per SIMD at most; blocks beyond the list's length return at once
   if (sized) rb = std::max(1, std::min(rb, 16 + 2 * c->retry_hint));
+  if (ids) {  // (a pass with per-frame global paths: the same lookup)
+    launch_gpt(c, q, in, ids, 0, (unsigned)rb);
+    return;
+  }
   hipLaunchKernelGGL(path_retry_kernel, dim3(rb), dim3(WAVE), 0, q.stream, in.d_poses, q.buf.d_match, c->d_default_path, prev, c->d_gpath,
                      c->n_gpath, q.buf.d_arena, q.buf.d_path, q.buf.d_retry, c->d_params);
 }
@@ -719,6 +770,8 @@ struct Pass {
   const Work::SeqPass* sq = nullptr;  // a sequence pass: the chain kernels between the path stage and the assembly
   bool device = false;                // a device ticket's pass: `host` (or NULL: the slot's block) is device memory, the results are handed
                                       // out by device_out_kernel, and path_retry_kernel's grid is always sized from the retry hint
+  const int32_t* path_ids = nullptr;  // a pass with per-frame global paths: the frames' ids into the context's path table, as the GPU
+                                      // addresses them (device memory, or the device view of page-locked host memory)
 };
 
 // skid: a skidpad step's records (path stage only, on the context's stream)
@@ -864,13 +917,13 @@ static int launch_pass(fsdp_ctx* c, Work& q, const InputStore<>& in_, const Pass
   mark(q, t);
   launch_match(c, q, in);
   names += "match_kernel<" + std::to_string(MATCH_G) + ">,";
-  const bool split = launch_path(c, q, in, t, names, pass.in_flight >= 0 ? pass.in_flight : frames_in_flight(c, in.n_frames, false));
+  const bool split = launch_path(c, q, in, t, names, pass.in_flight >= 0 ? pass.in_flight : frames_in_flight(c, in.n_frames, false), pass.path_ids);
   MarkKind after_path = split ? MARK_PLAIN : MARK_MAIN;  // (the one-kernel path stage is the main kernel: close its bracket)
   if (with_retry) {
     mark(q, t, after_path);
     after_path = MARK_PLAIN;
-    launch_path_retry(c, q, in, !pass.force_routes || c->retry_hint > 0 || pass.device);
-    names += "path_retry_kernel,";
+    launch_path_retry(c, q, in, !pass.force_routes || c->retry_hint > 0 || pass.device, pass.path_ids);
+    names += pass.path_ids ? "path_table_retry_kernel," : "path_retry_kernel,";
   }
   if (pass.sq) {  // (fsdp_plan_sequence: never timed)
     launch_sequence(c, q, in, pass);
@@ -1462,6 +1515,48 @@ int fsdp_set_global_path(fsdp_ctx* c, const double* xy, int n) {
   return 0;
 }
 
+int fsdp_set_global_path_table(fsdp_ctx* c, const double* xy, const int32_t* path_offsets, int n_paths) {
+  if (!c) return 1;
+  const std::string who = "fsdp_set_global_path_table";
+  if (c->outstanding) return busy_error(c, who.c_str());
+  if (c->mission == 2) {
+    c->err = who + ": a skidpad context plans along its own path table (fsdp_skidpad_set_tables)";
+    return 1;
+  }
+  if (n_paths < 0 || (n_paths > 0 && !path_offsets)) {
+    c->err = who + ": n_paths must be >= 0, and path_offsets given with n_paths > 0";
+    return 1;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = refuse_device_pointers(c, who.c_str(), {{"xy", xy}, {"path_offsets", path_offsets}})) return rc;
+  if (n_paths > 0 && path_offsets[0] != 0) {
+    c->err = who + ": path_offsets[0] must be 0";
+    return 1;
+  }
+  for (int k = 0; k < n_paths; k++)
+    if (path_offsets[k + 1] < path_offsets[k]) {
+      c->err = who + ": path_offsets must be non-decreasing (path_offsets[" + std::to_string(k + 1) + "] = " + std::to_string(path_offsets[k + 1]) + " < " +
+               std::to_string(path_offsets[k]) + ")";
+      return 1;
+    }
+  const size_t points = n_paths > 0 ? (size_t)path_offsets[n_paths] : 0;
+  if (points > 0 && !xy) {
+    c->err = who + ": xy is NULL";
+    return 1;
+  }
+  if (int rc = sync_all(c)) return rc;
+  c->d_gpt_xy.reset();
+  c->d_gpt_off.reset();
+  c->n_gpt = 0;
+  if (n_paths == 0) return 0;
+  HIP_TRY(c, c->d_gpt_xy.reserve(std::max<size_t>(2 * points, 2)));
+  HIP_TRY(c, c->d_gpt_off.reserve((size_t)n_paths + 1));
+  if (points > 0) HIP_TRY(c, copy_sync(c, c->d_gpt_xy, xy, sizeof(double) * 2 * points, hipMemcpyHostToDevice));
+  HIP_TRY(c, copy_sync(c, c->d_gpt_off, path_offsets, sizeof(int32_t) * ((size_t)n_paths + 1), hipMemcpyHostToDevice));
+  c->n_gpt = n_paths;
+  return 0;
+}
+
 // ---- streams of batches: submit / collect ------------------------------------------------------------------------------
 // One batch per ticket.  Ticket t goes to slot t % depth and is queued on that slot's stream behind the slot's previous
 // ticket (up to SLOT_QUEUE per slot): host -> device of the batch, the kernels of its pass and device -> host of its results
@@ -1647,6 +1742,21 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
   } else if (int rc = upload_inputs(c, q.in, q.stream, b)) {
     return rc;
   }
+  if (t.path_ids && n > 0) {
+    // The pass's path ids (fsdp_submit_paths), read by the path kernels themselves: the caller's array where it is page-locked, else
+    // the ticket's own block (an int per frame; a repeated pass stages them again from the caller's array, like the batch)
+    const int32_t* ids = t.path_ids;
+    if (!is_pinned(ids, sizeof(int32_t) * (size_t)n)) {
+      HIP_TRY(c, t.h_ids.reserve((size_t)n, 1024, Pin::Mapped));
+      memcpy(t.h_ids.get(), ids, sizeof(int32_t) * (size_t)n);
+      ids = t.h_ids;
+    }
+    pass.path_ids = (const int32_t*)device_view(ids);
+    if (!pass.path_ids) {
+      c->err = "internal: path_ids is not mapped into the device's address space";
+      return 2;
+    }
+  }
   // (the initial_prev rows of a sequence pass: adjacent also for a slice; seq_slice_in_kernel brought a page-locked slice's along)
   if (sq && sq->init && !slice_in) HIP_TRY(c, hipMemcpyAsync(q.seq_buf.d_seq_init, sq->init, init_bytes, hipMemcpyHostToDevice, q.stream));
   t.via_stage = false;
@@ -1749,6 +1859,7 @@ struct TicketSpec {
   bool compact = false;
   int cache_lo = -1;                     // >= 0: a chunk of a call that advances the sorting cache, its frame 0 is this planner
   Work::SeqPass sq;                      // on: a sequence pass
+  const int32_t* path_ids = nullptr;     // a pass with per-frame global paths: the caller's ids (checked by the submit)
 };
 
 // The one way a pass becomes a ticket (fsdp_submit*, the chunks of a blocking call, the sequence calls): entry t of slot q gets its
@@ -1765,6 +1876,7 @@ static int issue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, const TicketSpec&
   t.compact = spec.compact;
   t.sq = spec.sq;
   t.cache_lo = spec.cache_lo;
+  t.path_ids = spec.path_ids;
   if (int rc = enqueue_ticket(c, q, t, false)) {
     (void)hipStreamSynchronize(q.stream);
     (void)hipGetLastError();
@@ -1776,34 +1888,82 @@ static int issue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, const TicketSpec&
   return 0;
 }
 
+// What the calls that carry path ids refuse alike (fsdp_submit_paths*, fsdp_submit_device_paths): a context where an id has no
+// single meaning, or nothing to name
+static int refuse_paths_call(fsdp_ctx* c, const std::string& who) {
+  if (c->d_gpath) {
+    c->err = who + ": the context also has a context-wide global path (fsdp_set_global_path), and a context's frames follow either that one or "
+                   "the table entries their ids name — fsdp_set_global_path(ctx, NULL, 0) clears it";
+    return 1;
+  }
+  if (c->n_cache > 0) {
+    c->err = who + ": the sorting cache is on (it stays a lock-step feature of the calls without path ids: fsdp_sort_cache_reset(ctx, 0) turns it off)";
+    return 1;
+  }
+  if (c->n_gpt == 0) {
+    c->err = who + ": the context has no path table (fsdp_set_global_path_table)";
+    return 1;
+  }
+  if (!fsdp_gpt_launch || !fsdp_gpt_launch_ids_scan) {
+    c->err = who + ": this library was built without the path table kernels (csrc/gpath_table_lib.hip)";
+    return 2;
+  }
+  return 0;
+}
+
+// with_ids: fsdp_submit_paths* (path_ids required with n_frames > 0)
 static int submit_impl(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev_paths,
-                       fsdp_frame_result* results, long long* ticket, bool compact) {
+                       fsdp_frame_result* results, long long* ticket, bool compact, bool with_ids = false, const int32_t* path_ids = nullptr) {
   if (!c || !ticket) return 1;
   *ticket = -1;
+  const char* who = with_ids ? "fsdp_submit_paths" : "fsdp_submit";
   if (c->mission == 2) {
-    c->err = "fsdp_submit: a skidpad context plans through fsdp_skidpad_submit";
+    c->err = std::string(who) + ": a skidpad context plans through fsdp_skidpad_submit";
     return 1;
   }
   if (n_frames > 0 && !results) {
-    c->err = "fsdp_submit: results is NULL";
+    c->err = std::string(who) + ": results is NULL";
     return 1;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = refuse_device_pointers(c, "fsdp_submit", {{"cone_offsets", off}, {"cones_xyt", cones}, {"poses", poses}, {"prev_paths", prev_paths}, {"results", results}}))
+  if (int rc = refuse_device_pointers(c, who, {{"cone_offsets", off}, {"cones_xyt", cones}, {"poses", poses}, {"prev_paths", prev_paths}, {"results", results}, {"path_ids", path_ids}}))
     return rc;
+  if (with_ids) {
+    if (int rc = refuse_paths_call(c, who)) return rc;
+    if (n_frames > 0 && !path_ids) {
+      c->err = std::string(who) + ": path_ids is NULL";
+      return 1;
+    }
+    // (the host can read these ids: an id that names nothing is refused before anything is enqueued)
+    for (int i = 0; i < n_frames; i++)
+      if (path_ids[i] < -1 || path_ids[i] >= c->n_gpt) {
+        c->err = std::string(who) + ": path_ids[" + std::to_string(i) + "] = " + std::to_string(path_ids[i]) + " lies outside [-1, n_paths = " +
+                 std::to_string(c->n_gpt) + ") (-1: the frame plans from its cones)";
+        return 1;
+      }
+  }
   Batch b;
   if (int rc = check_batch(c, n_frames, off, cones, poses, prev_paths, &b)) return rc;
   Work* qp = nullptr;
   Work::Ticket* t = nullptr;
-  if (int rc = free_ticket(c, "fsdp_submit", n_frames, &qp, &t)) return rc;
+  if (int rc = free_ticket(c, who, n_frames, &qp, &t)) return rc;
   TicketSpec spec;
   spec.batch = b;
   spec.in_flight = frames_in_flight(c, n_frames, true);
   spec.results = results;
   spec.compact = compact;
+  spec.path_ids = with_ids ? path_ids : nullptr;
   if (int rc = issue_ticket(c, *qp, *t, spec)) return rc;
   *ticket = t->id;
   return 0;
+}
+int fsdp_submit_paths(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev_paths,
+                      const int32_t* path_ids, fsdp_frame_result* results, long long* ticket) {
+  return submit_impl(c, n_frames, off, cones, poses, prev_paths, results, ticket, false, true, path_ids);
+}
+int fsdp_submit_paths_compact(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev_paths,
+                              const int32_t* path_ids, fsdp_compact_result* results, long long* ticket) {
+  return submit_impl(c, n_frames, off, cones, poses, prev_paths, (fsdp_frame_result*)results, ticket, true, true, path_ids);
 }
 int fsdp_submit(fsdp_ctx* c, int n_frames, const int32_t* off, const double* cones, const double* poses, const double* prev_paths,
                 fsdp_frame_result* results, long long* ticket) {
@@ -1861,6 +2021,10 @@ int fsdp_collect(fsdp_ctx* c, long long ticket) {
       } else if (const int32_t bad = __atomic_load_n(t.h_bad.get(), __ATOMIC_RELAXED); bad >= 0) {
         c->err = "fsdp_collect: counts[" + std::to_string(bad) + "] of device ticket " + std::to_string(ticket) + " lies outside [0, cone_capacity = " +
                  std::to_string(t.dev.cap) + "] (the lowest such frame; every such frame was planned as having 0 cones: the call's outputs are not to be used)";
+        rc = 1;
+      } else if (const int32_t bad_id = t.dev.path_ids ? __atomic_load_n(t.h_bad.get() + 2, __ATOMIC_RELAXED) : -1; bad_id >= 0) {
+        c->err = "fsdp_collect: path_ids[" + std::to_string(bad_id) + "] of device ticket " + std::to_string(ticket) + " lies outside [-1, n_paths = " +
+                 std::to_string(c->n_gpt) + ") (the lowest such frame; every such frame was planned from its cones, as with -1: the call's outputs are not to be used)";
         rc = 1;
       }
     } else if (settle_routes(c, tr, t.ran_big, t.ran_retry, false)) {
@@ -1999,13 +2163,15 @@ static int enqueue_device_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, hipStrea
   if (int rc = ensure_work(c, q, n)) return rc;
   // (rows and max_cones are upper bounds: n * cone_capacity, cone_capacity; batch.prev says whether the store holds previous paths)
   if (int rc = take_batch(c, q.in, t.batch)) return rc;
-  HIP_TRY(c, t.h_bad.reserve(1, 16, Pin::MappedCoherent));
+  HIP_TRY(c, t.h_bad.reserve(3, 16, Pin::MappedCoherent));
   t.h_bad[0] = -1;
+  t.h_bad[2] = -1;
   if (after_stream) {
     if (!t.after) HIP_TRY(c, hipEventCreateWithFlags(&t.after.h, hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(t.after, after_stream));
     HIP_TRY(c, hipStreamWaitEvent(q.stream, t.after, 0));
   }
+  if (d.path_ids) fsdp_gpt_launch_ids_scan(q.stream, n, c->n_gpt, d.path_ids, t.h_bad.device() + 2);
   fsdp_dio_in_args a;
   a.n_frames = n;
   a.cone_capacity = d.cap;
@@ -2026,6 +2192,7 @@ static int enqueue_device_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, hipStrea
   pass.trailer = (int)(&t - q.tk);
   pass.force_routes = true;
   pass.in_flight = t.in_flight;
+  pass.path_ids = d.path_ids;
   if (int rc = launch_pass(c, q, q.in, pass)) return rc;
   t.seq = q.seq;
   t.ran_big = q.ran_big;
@@ -2048,12 +2215,13 @@ static int enqueue_device_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, hipStrea
   return 0;
 }
 
-int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
-                       const double* prev_paths, double* paths, int32_t* status, double* next_prev, fsdp_compact_result* records,
-                       void* after_stream, long long* ticket) {
+// with_ids: fsdp_submit_device_paths (path_ids required)
+static int submit_device_impl(fsdp_ctx* c, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
+                              const double* prev_paths, const int32_t* path_ids, bool with_ids, double* paths, int32_t* status, double* next_prev,
+                              fsdp_compact_result* records, void* after_stream, long long* ticket) {
   if (!c || !ticket) return 1;
   *ticket = -1;
-  const std::string who = "fsdp_submit_device";
+  const std::string who = with_ids ? "fsdp_submit_device_paths" : "fsdp_submit_device";
   if (c->mission == 2) {
     c->err = who + ": a skidpad context plans through fsdp_skidpad_submit (device arrays: fsdp_skidpad_submit_device)";
     return 1;
@@ -2078,6 +2246,13 @@ int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32
     c->err = who + ": this library was built without the device ticket kernels (csrc/device_io_lib.hip)";
     return 2;
   }
+  if (with_ids) {
+    if (int rc = refuse_paths_call(c, who)) return rc;
+    if (!path_ids) {
+      c->err = who + ": path_ids is NULL";
+      return 1;
+    }
+  }
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = (size_t)n_frames, row = sizeof(double) * PATH_POINTS * 4;
   const struct {
@@ -2088,6 +2263,7 @@ int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32
                 {"cones", cone_capacity > 0 ? cones : nullptr, sizeof(double) * 3 * n * (size_t)cone_capacity},
                 {"poses", poses, sizeof(double) * 4 * n},
                 {"prev_paths", prev_paths, row * n},
+                {"path_ids", with_ids ? path_ids : nullptr, sizeof(int32_t) * n},
                 {"paths", paths, row * n},
                 {"status", status, sizeof(int32_t) * n},
                 {"next_prev", next_prev, row * n},
@@ -2101,7 +2277,7 @@ int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32
     }
   Work* qp = nullptr;
   Work::Ticket* t = nullptr;
-  if (int rc = free_ticket(c, "fsdp_submit_device", n_frames, &qp, &t)) return rc;
+  if (int rc = free_ticket(c, who.c_str(), n_frames, &qp, &t)) return rc;
   // (the batch as the slot's stores size it: counts only, and prev as the flag take_batch reads — the host never dereferences a device ticket's batch)
   t->batch = Batch{n_frames, nullptr, nullptr, nullptr, prev_paths, n * (size_t)cone_capacity, cone_capacity};
   t->skid = false;
@@ -2112,6 +2288,8 @@ int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32
   t->sq = Work::SeqPass();
   t->cache_lo = -1;
   t->dev = Work::DevPass{true, cone_capacity, counts, cone_capacity > 0 ? cones : nullptr, poses, prev_paths, paths, status, next_prev, records};
+  t->dev.path_ids = with_ids ? path_ids : nullptr;
+  t->path_ids = nullptr;
   if (int rc = enqueue_device_ticket(c, *qp, *t, (hipStream_t)after_stream)) {
     (void)hipStreamSynchronize(qp->stream);
     (void)hipGetLastError();
@@ -2122,6 +2300,16 @@ int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32
   c->outstanding++;
   *ticket = t->id;
   return 0;
+}
+int fsdp_submit_device(fsdp_ctx* c, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
+                       const double* prev_paths, double* paths, int32_t* status, double* next_prev, fsdp_compact_result* records,
+                       void* after_stream, long long* ticket) {
+  return submit_device_impl(c, n_frames, cone_capacity, counts, cones, poses, prev_paths, nullptr, false, paths, status, next_prev, records, after_stream, ticket);
+}
+int fsdp_submit_device_paths(fsdp_ctx* c, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
+                             const double* prev_paths, const int32_t* path_ids, double* paths, int32_t* status, double* next_prev,
+                             fsdp_compact_result* records, void* after_stream, long long* ticket) {
+  return submit_device_impl(c, n_frames, cone_capacity, counts, cones, poses, prev_paths, path_ids, true, paths, status, next_prev, records, after_stream, ticket);
 }
 
 int fsdp_ticket_stream_wait(fsdp_ctx* c, long long ticket, void* stream) {

@@ -137,9 +137,11 @@ class DeviceFleet:
         rows = np.broadcast_to(self.ctx.default_path(), self._prev.shape) if initial_prev is None else self.ctx.pad_paths(initial_prev)
         self._prev.copy_from(rows)
 
-    def step(self, counts, cones, poses, after_stream=None, paths=None, status=None):
+    def step(self, counts, cones, poses, after_stream=None, paths=None, status=None, path_ids=None):
         """One tick: counts (n) int32, cones (n, cone_capacity, 3) or None when cone_capacity = 0, poses (n, 4) — device arrays.
-        after_stream: the stream that produces them (a hipStream_t as an int), or None when they are complete."""
+        after_stream: the stream that produces them (a hipStream_t as an int), or None when they are complete.
+        path_ids: a device (n) int32 array — planner i follows entry path_ids[i] of the context's path table
+        (Context.set_global_path_table) in this tick, or plans from its cones with -1; its previous path travels across a switch."""
         ctx = self.ctx
         while len(self._tickets) >= ctx.ticket_capacity:
             ctx.collect(self._tickets.pop(0))
@@ -148,7 +150,7 @@ class DeviceFleet:
         if after_stream is not None:
             ctx.stream_wait_stream(self._stream, after_stream)
         t = ctx.submit_device(counts, cones, poses, prev=self._prev, paths=paths, status=status, next_prev=self._prev, after_stream=self._stream,
-                              cone_capacity=self.cap)
+                              cone_capacity=self.cap, path_ids=path_ids)
         self._tickets.append(t)
         return t.out["paths"], t.out["status"], t
 

@@ -435,6 +435,43 @@ int fsdp_submit_device(fsdp_ctx* ctx, int n_frames, int cone_capacity, const int
                        void* after_stream, long long* ticket);
 int fsdp_ticket_stream_wait(fsdp_ctx* ctx, long long ticket, void* stream);
 
+/* ---- per-frame global paths: a path table, one path id per frame ----------------------------------------------------------
+ * PathPlanner.set_global_path belongs to ONE planner object; fsdp_set_global_path gives every frame of a context the same path.
+ * For n planners in lock-step that follow different paths — cars on different tracks, cars of which some have mapped their
+ * track and some have not, acceleration planners before and after relocalization — the context holds a TABLE of paths and a
+ * pass carries one id per frame:
+ *   fsdp_set_global_path_table  n_paths polylines one behind the other in xy, shape (path_offsets[n_paths], 2); path k is the points
+ *                               [path_offsets[k], path_offsets[k + 1]).  Copied once into device memory, offsets included; n_paths = 0
+ *                               clears the table.  A path of length 0 is allowed (a frame that names it gets status 103, the
+ *                               reference's argmin of an empty array).  Refused: while tickets are outstanding, on a skidpad context,
+ *                               offsets that do not start at 0 or that decrease, device pointers.
+ *   fsdp_submit_paths[_compact] fsdp_submit[_compact] plus path_ids (n_frames) int32, host memory (page-locked: read in place by
+ *                               the path kernels; pageable: staged into the ticket's own block).  path_ids[i] >= 0 plans frame i
+ *                               along that table entry — its matches are ignored, exactly as with fsdp_set_global_path of that
+ *                               polyline; -1 plans frame i from its cones, exactly as a context without a global path does.  An
+ *                               id outside [-1, n_paths) is refused (1) before anything is enqueued; the message names the frame.
+ *   fsdp_submit_device_paths    fsdp_submit_device plus path_ids in the memory of the context's GPU (the pointer rule of counts).
+ *                               The host cannot read these ids: an id outside [-1, n_paths) is planned as -1, and fsdp_collect
+ *                               returns 1 and names the lowest such frame (the rule of counts; the outputs are then not to be used).
+ * The ids are part of the ticket: the context keeps nothing per call, and the rerun fsdp_collect issues for a pass that lacked a
+ * route kernel reads the ticket's own ids again.  The three calls are refused, with a message that names the reason, when the
+ * context also has a context-wide path (one meaning per context: fsdp_set_global_path(ctx, NULL, 0) clears it), when its sorting
+ * cache is on, or when it has no table.  The other entry points do not read the table: a context with a table plans through them as
+ * it did before.
+ * Routing: a pass with ids runs the path stage's one-kernel form under the rules of any pass (small batches, max_deg < 3), and
+ * otherwise the three kernels in the form a context-wide path takes (32 knots per fit, 8 lanes per frame) for ALL of its frames,
+ * those with id -1 included; results do not depend on the route.
+ * Not offered: path ids for the sequence, cached, ranked, history, stage-level and skidpad calls and for the blocking
+ * fsdp_plan_batch* calls. */
+int fsdp_set_global_path_table(fsdp_ctx* ctx, const double* xy, const int32_t* path_offsets, int n_paths);
+int fsdp_submit_paths(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt, const double* poses,
+                      const double* prev_paths, const int32_t* path_ids, fsdp_frame_result* results, long long* ticket);
+int fsdp_submit_paths_compact(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt, const double* poses,
+                              const double* prev_paths, const int32_t* path_ids, fsdp_compact_result* results, long long* ticket);
+int fsdp_submit_device_paths(fsdp_ctx* ctx, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
+                             const double* prev_paths, const int32_t* path_ids, double* paths, int32_t* status, double* next_prev,
+                             fsdp_compact_result* records, void* after_stream, long long* ticket);
+
 /* The resident form: one batch stays in HBM and is planned again and again (the benchmark's step; a caller that plans the
  * same frames under several global paths / previous paths). */
 int fsdp_upload(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt, const double* poses);
