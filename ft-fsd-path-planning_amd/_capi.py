@@ -238,6 +238,11 @@ def load(shapes: Shapes = STANDARD) -> ctypes.CDLL:
     lib.fsdp_submit_paths.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.POINTER(ctypes.c_longlong)]
     lib.fsdp_submit_paths_compact.argtypes = lib.fsdp_submit_paths.argtypes
     lib.fsdp_submit_device_paths.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.POINTER(ctypes.c_longlong)]
+    # the sequence calls with path_ids behind initial_prev
+    lib.fsdp_plan_sequence_paths.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.POINTER(ctypes.c_longlong)]
+    lib.fsdp_plan_sequence_paths_compact.argtypes = lib.fsdp_plan_sequence_paths.argtypes
+    lib.fsdp_submit_sequence_paths.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 7 + [ctypes.POINTER(ctypes.c_longlong)] * 2
+    lib.fsdp_submit_sequence_paths_compact.argtypes = lib.fsdp_submit_sequence_paths.argtypes
     # (ctx, n_instances, cone_capacity, counts, cones, poses, reset, paths, status, info, records, after_stream, ticket)
     lib.fsdp_skidpad_submit_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.POINTER(ctypes.c_longlong)]
     got = (ctypes.c_int32 * 4)()
@@ -267,6 +272,7 @@ EXPORTED_SYMBOLS = [
     "fsdp_stream_wait_stream", "fsdp_submit_device", "fsdp_ticket_stream_wait", "fsdp_sort_batch_history",
     "fsdp_skidpad_submit_device",
     "fsdp_set_global_path_table", "fsdp_submit_paths", "fsdp_submit_paths_compact", "fsdp_submit_device_paths",
+    "fsdp_plan_sequence_paths", "fsdp_plan_sequence_paths_compact", "fsdp_submit_sequence_paths", "fsdp_submit_sequence_paths_compact",
 ]
 
 
@@ -553,13 +559,16 @@ class Context:
         cache on (sort_cache_reset) frame i is planner i, and prev_paths may be None (fresh path-stage history)."""
         return self.plan_batch(offsets, cones, poses, prev_paths=prev_paths, _sequential=self.n_cache > 0)
 
-    def plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False):
+    def plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False, path_ids=None):
         """fsdp_plan_sequence: n_planners planners x T consecutive steps in one call, frame = step * n_planners + planner (T =
         frames / n_planners) — the bytes of T plan_batch_sequential calls whose prev_paths rows are the planners' most recent
         successful paths.  initial_prev: (n_planners, <= path_points, 4) or None, a row starting with NaN = none (the fresh
         planner's initial path).  -> (results, final_prev (n_planners, path_points, 4) with NaN rows for planners that have no
-        path yet, n_replanned = frames planned a second time on the device)."""
-        return self._plan_sequence(cone_offsets, cones_xyt, poses, int(n_planners), initial_prev, compact, cached=False)[:3]
+        path yet, n_replanned = frames planned a second time on the device).
+        path_ids (fsdp_plan_sequence_paths): (frames) int32, step-major like the frames — an entry of the context's path table
+        (set_global_path_table) per frame, or -1 for a frame that plans from its cones; a planner's id may change from step to step.
+        The bytes are then those of T submit(prev_paths=, path_ids=) calls chained the same way."""
+        return self._plan_sequence(cone_offsets, cones_xyt, poses, int(n_planners), initial_prev, compact, cached=False, path_ids=path_ids)[:3]
 
     def plan_sequence_cached(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False):
         """fsdp_plan_sequence_cached: plan_sequence on a context whose sorting cache is on for exactly n_planners planners
@@ -572,9 +581,17 @@ class Context:
                                f"{n_planners} (sort_cache_reset(n_planners) turns it on)")
         return self._plan_sequence(cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact, cached=True)
 
-    def _plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact, cached):
+    def _sequence_ids(self, who, path_ids, n):
+        """path_ids of a sequence call as the ABI takes them: contiguous int32, one per frame of the recording"""
+        self._host_arrays(path_ids)
+        ids = np.ascontiguousarray(path_ids, dtype=np.int32)
+        if ids.shape != (n,):
+            raise ValueError(f"{who}: path_ids {ids.shape} for {n} frames")
+        return ids
+
+    def _plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact, cached, path_ids=None):
         """fsdp_plan_sequence[_cached][_compact] -> (results, final_prev, n_replanned, hits, n_resorted), the last two of a cached call"""
-        who = "plan_sequence_cached" if cached else "plan_sequence"
+        who = "plan_sequence_cached" if cached else ("plan_sequence" if path_ids is None else "plan_sequence_paths")
         offsets, cones, poses, n = self._prep_any_base(cone_offsets, cones_xyt, poses)
         if n_planners < 1 or n < 1 or n % n_planners:
             raise ValueError(f"{who}: {n} frames are not a whole number (>= 1) of steps of {n_planners} planners")
@@ -588,7 +605,8 @@ class Context:
         again, resorted = ctypes.c_longlong(0), ctypes.c_longlong(0)
         fn = getattr(self._lib, f"fsdp_{who}_compact" if compact else f"fsdp_{who}")
         self._check(fn(self._h, n_planners, n // n_planners, offsets.ctypes.data, cones.ctypes.data if len(cones) else None, poses.ctypes.data,
-                       None if init is None else init.ctypes.data, out.ctypes.data, final.ctypes.data, ctypes.byref(again),
+                       None if init is None else init.ctypes.data, *(() if path_ids is None else (self._sequence_ids(who, path_ids, n).ctypes.data,)),
+                       out.ctypes.data, final.ctypes.data, ctypes.byref(again),
                        *((hits.ctypes.data, ctypes.byref(resorted)) if cached else ())), f"fsdp_{who}")
         self.n_frames = n
         return out, final, int(again.value), hits, int(resorted.value)
@@ -728,14 +746,16 @@ class Context:
         return Ticket(int(t.value), out, None, (offsets, cones, poses, prev))
 
     def submit_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False, planner_lo: int = 0,
-                        planners_total: int | None = None, out=None, final_prev_out=None) -> SequenceTicket:
+                        planners_total: int | None = None, out=None, final_prev_out=None, path_ids=None) -> SequenceTicket:
         """fsdp_submit_sequence: plan_sequence as a ticket, for the planners [planner_lo, planner_lo + n_planners) of a recording.
         The arrays describe the WHOLE recording of planners_total (default: n_planners) planners x T steps, step-major: offsets of
         T * planners_total frames (any base), their cones and poses, initial_prev (planners_total, <= path_points, 4) or None.
         out / final_prev_out: the recording's result array (T * planners_total records) and (planners_total, path_points, 4) block
         the call writes ITS rows of (default: new page-locked arrays) — the planner slices of one recording share them.  Page-locked
         arrays (pinned_empty / pinned_copy) are read and written in place by the GPU; others are staged.  Everything must stay
-        untouched until collect(), which returns (out, final_prev_out, n_replanned)."""
+        untouched until collect(), which returns (out, final_prev_out, n_replanned).
+        path_ids (fsdp_submit_sequence_paths): (T * planners_total) int32 of the WHOLE recording, step-major: the path table entry
+        of each frame or -1 (plan_sequence); a slice reads its own planners' entries."""
         n_planners, planner_lo = int(n_planners), int(planner_lo)
         total = n_planners if planners_total is None else int(planners_total)
         offsets, cones, poses, n = self._prep_any_base(cone_offsets, cones_xyt, poses)
@@ -757,11 +777,13 @@ class Context:
         if final_prev_out.dtype != np.float64 or final_prev_out.shape != (total, rows, 4) or not final_prev_out.flags.c_contiguous:
             raise ValueError(f"submit_sequence: final_prev_out must be a contiguous float64 array of shape {(total, rows, 4)}")
         again, t = ctypes.c_longlong(0), ctypes.c_longlong(-1)
-        fn = self._lib.fsdp_submit_sequence_compact if compact else self._lib.fsdp_submit_sequence
+        who = "fsdp_submit_sequence" if path_ids is None else "fsdp_submit_sequence_paths"
+        ids = None if path_ids is None else self._sequence_ids("submit_sequence", path_ids, n)
+        fn = getattr(self._lib, who + "_compact" if compact else who)
         self._check(fn(self._h, n_planners, n // total, planner_lo, total, offsets.ctypes.data, cones.ctypes.data if len(cones) else None,
-                       poses.ctypes.data, None if init is None else init.ctypes.data, out.ctypes.data, final_prev_out.ctypes.data,
-                       ctypes.byref(again), ctypes.byref(t)), "fsdp_submit_sequence")
-        return SequenceTicket(int(t.value), out, final_prev_out, again, (offsets, cones, poses, init))
+                       poses.ctypes.data, None if init is None else init.ctypes.data, *(() if ids is None else (ids.ctypes.data,)), out.ctypes.data,
+                       final_prev_out.ctypes.data, ctypes.byref(again), ctypes.byref(t)), who)
+        return SequenceTicket(int(t.value), out, final_prev_out, again, (offsets, cones, poses, init, ids))
 
     # device tickets: batches and results in the caller's GPU memory (fsdp_submit_device; device.py)
     def submit_device(self, counts, cones, poses, prev=None, paths=None, status=None, next_prev=None, records=False, after_stream=None,

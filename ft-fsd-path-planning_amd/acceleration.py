@@ -130,6 +130,53 @@ def rotate_point_rows(x, y, theta):
     return fma(y, -s, x * c), fma(y, c, x * s)
 
 
+def plan_sequence_on(relocalizers, reloc, angle, orig, prev, off, cones, poses, path_stage):
+    """The host part of AccelerationBatch.plan_sequence, with the path stage as an argument (the GPU's sequence call there, the CPU
+    oracle in tests/test_sequence_paths_cpu.py).  n = len(relocalizers) planners x T steps, step-major; reloc / angle / orig / prev
+    are the batch's per-planner state arrays (relocalized, angle_to_fix, original position, previous path) and are advanced in
+    place, exactly as T `step` calls advance them.
+    path_stage(poses (T * n, 4), ids (T * n) int32: 0 = along the known path, -1 = none, initial_prev (n, horizon, 4))
+      -> (paths (T * n, horizon, 4), status (T * n), final_prev (n, horizon, 4)): every planner's steps chained through the path of
+      its most recent step with status 0.
+    -> (paths (T, n, horizon, 4) in the callers' frames, NaN rows where status != 0; status (T, n))"""
+    n = len(relocalizers)
+    T = len(poses) // n
+    position, direction = poses[:, :2], poses[:, 2:]
+    # each waiting planner's attempts over its steps, in step order, until one succeeds: every attempt draws from the planner's own
+    # RandomState, so a planner sees the draws T `step` calls would give it, whatever the other planners do
+    first = np.where(reloc, 0, T)  # the step from which the planner plans along the known path (T: not within this log)
+    for i in np.nonzero(~reloc)[0]:
+        r = relocalizers[i]
+        for t in range(T):
+            f = t * n + i
+            r.attempt([cones[off[f] : off[f + 1], :2]], position[f], direction[f])
+            if r.is_relocalized:
+                reloc[i], angle[i], orig[i], first[i] = True, r.angle_to_fix, r.original_position, t
+                break
+    k = (np.arange(T)[:, None] >= first[None, :]).reshape(-1)  # (frames): behind the planner's relocalization step
+    who = np.tile(np.arange(n), T)[k]  # ... and their planners
+    pose_k = poses.copy()
+    if k.any():
+        yaw = np.arctan2(direction[k, 1], direction[k, 0])
+        d = position[k] - orig[who]
+        pose_k[k, 0], pose_k[k, 1] = rotate_single_points(d[:, 0], d[:, 1], -angle[who])
+        yaw_k = yaw - angle[who]
+        pose_k[k, 2], pose_k[k, 3] = np.cos(yaw_k), np.sin(yaw_k)
+    ids = np.where(k, 0, -1).astype(np.int32)
+    path, status, final = path_stage(pose_k, ids, prev.copy())
+    prev[:] = final  # (the path of every planner's last successful step, else the row it came with)
+    res_path = np.array(path, dtype=np.float64)
+    ok = status == 0
+    res_path[~ok] = np.nan
+    back = ok & k
+    if back.any():
+        w = np.tile(np.arange(n), T)[back]
+        x, y = rotate_point_rows(res_path[back, :, 1], res_path[back, :, 2], angle[w][:, None])
+        res_path[back, :, 1] = x + orig[w, 0][:, None]
+        res_path[back, :, 2] = y + orig[w, 1][:, None]
+    return res_path.reshape(T, n, *res_path.shape[1:]), status.reshape(T, n)
+
+
 class AccelerationBatch:
     """n acceleration / ebs_test planners advanced in lock-step (the counterpart of SkidpadBatch for these missions): one
     `step(cone_offsets, cones_xyt, poses)` = one `calculate_path_in_global_frame` call of every planner, with the results of
@@ -140,7 +187,8 @@ class AccelerationBatch:
     step does for every planner every time — the pose into the known frame, the path stage along the known path, the path back
     into the caller's frame (full_pipeline.py:118-136,178-194) — is one vectorised transform, ONE pass on the GPU for the planners
     before and after relocalization alike (fsdp_submit_paths: the known path is entry 0 of the context's path table, a planner
-    that is not relocalized yet carries id -1; a planner's previous path travels with it) and one vectorised transform back."""
+    that is not relocalized yet carries id -1; a planner's previous path travels with it) and one vectorised transform back.
+    `plan_sequence` plans a whole log of T steps the same way in ONE pass (fsdp_plan_sequence_paths): the bytes of T `step` calls."""
 
     def __init__(self, n_planners: int, mission=None, seeds=None, device: int | None = None, params: dict | None = None):
         from . import _capi
@@ -212,6 +260,27 @@ class AccelerationBatch:
             res_path[back, :, 1] = x + self._orig[back, 0][:, None]
             res_path[back, :, 2] = y + self._orig[back, 1][:, None]
         return res_path, status
+
+    def plan_sequence(self, cone_offsets, cones_xyt, poses):
+        """T consecutive `step` calls as ONE pass: the frames are step-major, frame = step * n + planner (T = frames / n).  Returns
+        (paths (T, n, horizon, 4), status (T, n)) — the bytes of T `step` calls on this batch as it stands, fresh or continued — and
+        leaves the batch as those calls would: a following `step` or `plan_sequence` continues the log.
+
+        The relocalization depends on cones and poses only, never on a planned path, so the host runs it for the whole log up
+        front; the rest is one fsdp_plan_sequence_paths call whose ids are -1 before a planner's relocalization step and 0 from it
+        on, with the planners' previous-path chains resolved on the device (`plan_sequence_on`)."""
+        from . import _capi
+
+        off, cones, poses, frames = _capi.Context._prep(cone_offsets, cones_xyt, poses)
+        if frames < 1 or frames % self.n:
+            raise ValueError(f"{frames} frames are not a whole number (>= 1) of steps of {self.n} planners")
+        no_cones = np.zeros(frames + 1, np.int32)
+
+        def path_stage(pose_k, ids, prev):
+            r, final, _ = self._ctx.plan_sequence(no_cones, self._no_cones[1], pose_k, self.n, initial_prev=prev, compact=True, path_ids=ids)
+            return r["path"][:, : self.horizon], r["status"].astype(np.int32), final[:, : self.horizon]
+
+        return plan_sequence_on(self.relocalizers, self._reloc, self._angle, self._orig, self._prev, off, cones, poses, path_stage)
 
     def close(self):
         self._ctx.close()

@@ -34,6 +34,7 @@
 #include "skid_device_launch.h"  // (the kernels of a skidpad device ticket live in that unit too)
 #include "sort_history_launch.h"  // (the history instantiations of the sorting kernels likewise: sort_history_lib.hip)
 #include "gpath_table_launch.h"   // (the path wrappers of a pass with per-frame global paths likewise: gpath_table_lib.hip)
+#include "sequence_table_launch.h"  // (the chain kernel of a sequence pass with per-frame global paths likewise: sequence_table_lib.hip)
 
 using namespace fsdp;
 
@@ -120,6 +121,7 @@ struct Work {
     const double* init = nullptr;   // the slice's first initial_prev row, or NULL
     double* final_prev = nullptr;   // the slice's first final_prev row, or NULL
     long long* n_replanned = nullptr;
+    const int32_t* path_ids = nullptr;  // fsdp_*_sequence_paths: the whole recording's path ids (n_steps * total, step-major), or NULL
     // set by enqueue_ticket
     double* final_dev = nullptr;    // where seq_final_kernel writes: page-locked host memory (the caller's rows or the ticket's h_fin), or the slot's d_seq_final
     bool fin_staged = false;        // final_prev goes through h_fin (fsdp_collect copies it out)
@@ -817,6 +819,12 @@ static void launch_sequence(fsdp_ctx* c, Work& q, const Inputs& in, const Pass& 
   a.final_prev = sq.final_dev;
   a.replanned_out = &(q.h_trailer.device() + pass.trailer)->pad;
   a.prm = c->d_params;
+  if (pass.path_ids) {  // (per-frame global paths: the TABLE twin of the chain kernel between the two kernels that read no global path)
+    fsdp_seq_launch_mark(q.stream, &a);
+    fsdp_seqt_launch_chain(q.stream, &a, c->d_gpt_xy, c->d_gpt_off, c->n_gpt, pass.path_ids);
+    fsdp_seq_launch_final(q.stream, &a);
+    return;
+  }
   fsdp_seq_launch(q.stream, &a);
 }
 
@@ -927,7 +935,7 @@ static int launch_pass(fsdp_ctx* c, Work& q, const InputStore<>& in_, const Pass
   }
   if (pass.sq) {  // (fsdp_plan_sequence: never timed)
     launch_sequence(c, q, in, pass);
-    names += "seq_mark_kernel,seq_chain_kernel,seq_final_kernel,";
+    names += pass.path_ids ? "seq_mark_kernel,seq_chain_table_kernel,seq_final_kernel," : "seq_mark_kernel,seq_chain_kernel,seq_final_kernel,";
   }
   mark(q, t, after_path);
   launch_assemble(c, q, in.n_frames, pass, false);
@@ -1641,6 +1649,29 @@ static int pack_slice(fsdp_ctx* c, Work::Ticket& t, Batch* b) {
   return 0;
 }
 
+// The path ids of a sequence ticket's frames (fsdp_*_sequence_paths), dense in the call's frame order, gathered from the
+// recording's array into the ticket's page-locked block, where the path kernels and the chain kernel read them: 4 bytes per frame,
+// in the loop that checks them against the table.  Nothing is enqueued before it; a repeated pass gathers, and checks, them again.
+static int gather_sequence_ids(fsdp_ctx* c, Work::Ticket& t) {
+  const Work::SeqPass& sq = t.sq;
+  const SeqSlice& s = sq.s;
+  HIP_TRY(c, t.h_ids.reserve((size_t)s.frames(), 1024, Pin::Mapped));
+  int32_t* dst = t.h_ids.get();
+  for (int step = 0; step < s.n_steps; step++) {
+    const size_t r = (size_t)seq_rec_frame(s, step, 0);
+    for (int p = 0; p < s.n; p++) {
+      const int32_t id = sq.path_ids[r + (size_t)p];
+      if (id < -1 || id >= c->n_gpt) {
+        c->err = std::string(sq.who) + ": path_ids[" + std::to_string(r + (size_t)p) + "] = " + std::to_string(id) + " lies outside [-1, n_paths = " +
+                 std::to_string(c->n_gpt) + ") (-1: the frame plans from its cones)";
+        return 1;
+      }
+      *dst++ = id;
+    }
+  }
+  return 0;
+}
+
 // enqueue ticket t's batch on slot q: inputs, the pass with its results' way back, the ticket's event.  The pass is described by
 // the ticket alone (its Pass is built here from the ticket's fields, nothing is read from the call in progress): fsdp_collect's
 // rerun, with force_routes, is this function of the same data.
@@ -1661,6 +1692,8 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
   } else if (sq && sq->cached) {
     pass.sort.kind = SortVariant::SPEC;
   }
+  if (sq && sq->path_ids)
+    if (int rc = gather_sequence_ids(c, t)) return rc;
   // a bigger batch than the slot has seen: its buffers are replaced — not under the feet of the passes queued on the stream
   if ((size_t)n > q.buf.frames() || !q.in.fits((size_t)n, b.total, b.prev != nullptr) || (sq && !q.seq_buf.fits((size_t)n, (size_t)sq->s.n)))
     HIP_TRY(c, hipStreamSynchronize(q.stream));
@@ -1752,6 +1785,12 @@ static int enqueue_ticket(fsdp_ctx* c, Work& q, Work::Ticket& t, bool force_rout
       ids = t.h_ids;
     }
     pass.path_ids = (const int32_t*)device_view(ids);
+    if (!pass.path_ids) {
+      c->err = "internal: path_ids is not mapped into the device's address space";
+      return 2;
+    }
+  } else if (sq && sq->path_ids && n > 0) {  // (a sequence ticket's ids: gathered into the ticket's block above)
+    pass.path_ids = (const int32_t*)device_view(t.h_ids.get());
     if (!pass.path_ids) {
       c->err = "internal: path_ids is not mapped into the device's address space";
       return 2;
@@ -2434,6 +2473,8 @@ struct SeqCall {
   double* final_prev;
   long long* n_replanned;
   bool cached;
+  bool with_ids = false;              // fsdp_*_sequence_paths: per-frame global paths
+  const int32_t* path_ids = nullptr;  // ... the recording's ids (n_steps * planners_total, step-major)
 };
 
 // what every sequence entry point refuses, in one order (blocking: the call needs the context to itself)
@@ -2453,6 +2494,13 @@ static int seq_refusals(fsdp_ctx* c, const std::string& who, const SeqCall& k, b
   if (k.cached && !fsdp_seqc_launch_sort) {
     c->err = who + ": this library was built without csrc/sequence_cache_lib.hip";
     return 1;
+  }
+  if (k.with_ids) {
+    if (int rc = refuse_paths_call(c, who)) return rc;
+    if (!fsdp_seqt_launch_chain || !fsdp_seq_launch_mark || !fsdp_seq_launch_final) {
+      c->err = who + ": this library was built without csrc/sequence_table_lib.hip";
+      return 2;
+    }
   }
   if (blocking && c->outstanding) return busy_error(c, who.c_str());
   if (k.n_planners < 1 || k.n_steps < 1) {
@@ -2483,8 +2531,14 @@ static int seq_refusals(fsdp_ctx* c, const std::string& who, const SeqCall& k, b
     c->err = who + ": results is NULL";
     return 1;
   }
+  if (k.with_ids && !k.path_ids) {
+    c->err = who + ": path_ids is NULL";
+    return 1;
+  }
+  // (the ids themselves are checked against the table where they are gathered, in front of everything the ticket enqueues:
+  // gather_sequence_ids)
   return refuse_device_pointers(c, who.c_str(), {{"cone_offsets", k.off}, {"cones_xyt", k.cones}, {"poses", k.poses}, {"initial_prev", k.initial_prev},
-                                                  {"results", k.results}, {"final_prev", k.final_prev}});
+                                                  {"results", k.results}, {"final_prev", k.final_prev}, {"path_ids", k.path_ids}});
 }
 
 // the call's frames as a Batch: the whole call through check_batch (its arrays are the batch); a planner slice's segments
@@ -2530,17 +2584,19 @@ static TicketSpec seq_spec(const Batch& b, const SeqCall& k, const char* who, lo
   sq.init = k.initial_prev ? k.initial_prev + SEQ_PREV_DOUBLES * (size_t)k.planner_lo : nullptr;
   sq.final_prev = k.final_prev ? k.final_prev + SEQ_PREV_DOUBLES * (size_t)k.planner_lo : nullptr;
   sq.n_replanned = k.n_replanned;
+  sq.path_ids = k.with_ids ? k.path_ids : nullptr;
   return spec;
 }
 
 static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
                          const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev, long long* n_replanned,
-                         bool cached = false, int8_t* hits = nullptr, long long* n_resorted = nullptr) {
+                         bool cached = false, int8_t* hits = nullptr, long long* n_resorted = nullptr, bool with_ids = false,
+                         const int32_t* path_ids = nullptr) {
   if (!c) return 1;
-  const char* who = cached ? "fsdp_plan_sequence_cached" : "fsdp_plan_sequence";
+  const char* who = with_ids ? "fsdp_plan_sequence_paths" : (cached ? "fsdp_plan_sequence_cached" : "fsdp_plan_sequence");
   if (n_replanned) *n_replanned = 0;
   if (n_resorted) *n_resorted = 0;
-  const SeqCall k{n_planners, n_steps, 0, n_planners, off, cones, poses, initial_prev, results, compact, final_prev, n_replanned, cached};
+  const SeqCall k{n_planners, n_steps, 0, n_planners, off, cones, poses, initial_prev, results, compact, final_prev, n_replanned, cached, with_ids, path_ids};
   if (int rc = seq_refusals(c, who, k, true)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   const int n = n_planners * n_steps;
@@ -2579,12 +2635,12 @@ static int plan_sequence(fsdp_ctx* c, int n_planners, int n_steps, const int32_t
 // The ticket form (include/fsdp.h): planners [planner_lo, planner_lo + n_planners) of a recording of planners_total, cache off.
 static int submit_sequence(fsdp_ctx* c, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* off, const double* cones,
                            const double* poses, const double* initial_prev, fsdp_frame_result* results, bool compact, double* final_prev,
-                           long long* n_replanned, long long* ticket) {
+                           long long* n_replanned, long long* ticket, bool with_ids = false, const int32_t* path_ids = nullptr) {
   if (!c) return 1;
-  const char* who = "fsdp_submit_sequence";
+  const char* who = with_ids ? "fsdp_submit_sequence_paths" : "fsdp_submit_sequence";
   if (ticket) *ticket = -1;
   if (n_replanned) *n_replanned = 0;
-  const SeqCall k{n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, results, compact, final_prev, n_replanned, false};
+  const SeqCall k{n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, results, compact, final_prev, n_replanned, false, with_ids, path_ids};
   if (int rc = seq_refusals(c, who, k, false)) return rc;
   if (!ticket) {
     c->err = std::string(who) + ": ticket is NULL";
@@ -2636,6 +2692,35 @@ int fsdp_submit_sequence_compact(fsdp_ctx* c, int n_planners, int n_steps, int p
                                  double* final_prev, long long* n_replanned, long long* ticket) {
   return submit_sequence(c, n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true,
                          final_prev, n_replanned, ticket);
+}
+
+// The sequence calls with per-frame global paths (include/fsdp.h): path_ids covers the whole recording, step-major.
+int fsdp_plan_sequence_paths(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                             const double* initial_prev, const int32_t* path_ids, fsdp_frame_result* results, double* final_prev,
+                             long long* n_replanned) {
+  return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, results, false, final_prev, n_replanned, false, nullptr, nullptr, true,
+                       path_ids);
+}
+
+int fsdp_plan_sequence_paths_compact(fsdp_ctx* c, int n_planners, int n_steps, const int32_t* off, const double* cones, const double* poses,
+                                     const double* initial_prev, const int32_t* path_ids, fsdp_compact_result* results, double* final_prev,
+                                     long long* n_replanned) {
+  return plan_sequence(c, n_planners, n_steps, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true, final_prev, n_replanned, false,
+                       nullptr, nullptr, true, path_ids);
+}
+
+int fsdp_submit_sequence_paths(fsdp_ctx* c, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* off,
+                               const double* cones, const double* poses, const double* initial_prev, const int32_t* path_ids,
+                               fsdp_frame_result* results, double* final_prev, long long* n_replanned, long long* ticket) {
+  return submit_sequence(c, n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, results, false, final_prev, n_replanned,
+                         ticket, true, path_ids);
+}
+
+int fsdp_submit_sequence_paths_compact(fsdp_ctx* c, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* off,
+                                       const double* cones, const double* poses, const double* initial_prev, const int32_t* path_ids,
+                                       fsdp_compact_result* results, double* final_prev, long long* n_replanned, long long* ticket) {
+  return submit_sequence(c, n_planners, n_steps, planner_lo, planners_total, off, cones, poses, initial_prev, (fsdp_frame_result*)results, true,
+                         final_prev, n_replanned, ticket, true, path_ids);
 }
 
 int fsdp_sort_cache_reset(fsdp_ctx* c, int n_planners) {

@@ -102,6 +102,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) pa
   }
 }
 
+// (FSDP_SEQ_TABLE_UNIT: csrc/sequence_table_lib.hip compiles this header for table_lookup alone — the kernels below, which are no
+// templates, belong to gpath_table_lib.hip)
+#ifndef FSDP_SEQ_TABLE_UNIT
 // path_retry_kernel: four frames per wavefront with 16 lanes each, and the whole wavefront for what that form hands on (or, a list
 // of up to retry_pack_min frames, for every frame).  The lookup follows the frame: a group's own in the first level, the wavefront's
 // in the second.
@@ -172,5 +175,7 @@ __global__ void __launch_bounds__(1024) path_ids_scan_kernel(int n_frames, int n
     __hip_atomic_store(bad_out, bad == 0x7fffffff ? -1 : bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+
+#endif  // FSDP_SEQ_TABLE_UNIT
 
 }  // namespace fsdp

@@ -63,6 +63,9 @@ __device__ __forceinline__ int seq_walk_back(const PathOut* out, int n_planners,
   return SEQ_TRANSPARENT;
 }
 
+// (FSDP_SEQ_TABLE_UNIT: csrc/sequence_table_lib.hip compiles this header for the chain rule's helpers above alone — the kernels
+// below belong to sequence_lib.hip)
+#ifndef FSDP_SEQ_TABLE_UNIT
 // grid = ceil(n_frames / 64).  A flagged frame is a run head when the walk back from it stops at a settled frame or runs off
 // the start; not when it stops at a flagged frame, whose result is not final yet.
 __global__ void __launch_bounds__(64) seq_mark_kernel(int n_planners, int n_steps, const PathOut* __restrict__ out, int* __restrict__ seq) {
@@ -234,5 +237,6 @@ __global__ void __launch_bounds__(256) seq_slice_out_kernel(fsdp_seq_slice_out_a
   }
 }
 #endif  // FSDP_EMU
+#endif  // FSDP_SEQ_TABLE_UNIT
 
 }  // namespace fsdp

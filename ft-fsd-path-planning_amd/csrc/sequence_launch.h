@@ -38,6 +38,10 @@ struct fsdp_seq_launch_args {
 // header memset -> seq_mark_kernel -> seq_chain_kernel -> seq_final_kernel on `stream`.  Weak: a library built from fsdp_lib.hip
 // alone (the variant builds of tools/) has no sequence kernels, and fsdp_plan_sequence says so.
 extern "C" __attribute__((weak)) void fsdp_seq_launch(hipStream_t stream, const fsdp_seq_launch_args* a);
+// Its first step (header memset -> seq_mark_kernel) and its last (seq_final_kernel) alone: a sequence pass with per-frame global
+// paths puts seq_chain_table_kernel between them (sequence_table_launch.h); gpath / n_gpath are not read.
+extern "C" __attribute__((weak)) void fsdp_seq_launch_mark(hipStream_t stream, const fsdp_seq_launch_args* a);
+extern "C" __attribute__((weak)) void fsdp_seq_launch_final(hipStream_t stream, const fsdp_seq_launch_args* a);
 
 // A planner slice of a recording (fsdp_submit_sequence with page-locked arrays): seq_slice_in_kernel in front of the pass,
 // seq_slice_out_kernel behind its assembly.  Every src of the first and every dst of the second is the device view of a

@@ -22,6 +22,21 @@ extern "C" void fsdp_seq_launch(hipStream_t stream, const fsdp_seq_launch_args* 
                      a->initial_prev, a->final_prev, (const int*)a->seq, a->replanned_out);
 }
 
+// The first and the last step of fsdp_seq_launch on their own, for a pass whose chain kernel lives in another code object
+// (sequence_table_lib.hip: a sequence with per-frame global paths).  Host code only: the kernels are the ones above.
+extern "C" void fsdp_seq_launch_mark(hipStream_t stream, const fsdp_seq_launch_args* a) {
+  using namespace fsdp;
+  const long long n = (long long)a->n_planners * a->n_steps;
+  (void)hipMemsetAsync(a->seq, 0, sizeof(int) * SEQ_LIST, stream);
+  hipLaunchKernelGGL(seq_mark_kernel, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, a->n_planners, a->n_steps,
+                     (const PathOut*)a->out, a->seq);
+}
+extern "C" void fsdp_seq_launch_final(hipStream_t stream, const fsdp_seq_launch_args* a) {
+  using namespace fsdp;
+  hipLaunchKernelGGL(seq_final_kernel, dim3((unsigned)a->n_planners), dim3(WAVE), 0, stream, a->n_planners, a->n_steps, (const PathOut*)a->out,
+                     a->initial_prev, a->final_prev, (const int*)a->seq, a->replanned_out);
+}
+
 // The staging kernels of a planner slice.  In: the grid of stage_in_kernel (256 workgroups keep ~1 MB of loads on the wire).
 // Out: stores towards host memory leave at the link's pace — the cap launch_assemble applies (128 workgroups).
 extern "C" void fsdp_seq_launch_slice_in(hipStream_t stream, const fsdp_seq_slice_in_args* a) {

@@ -141,6 +141,11 @@ class MultiPlanner:
         for c in self.ctx:
             c.set_global_path(xy)
 
+    def set_global_path_table(self, paths):
+        """Context.set_global_path_table on every context: the table submit_sequence(path_ids=) names entries of."""
+        for c in self.ctx:
+            c.set_global_path_table(paths)
+
     def reset_host_time(self):
         self.host_seconds, self.host_frames = 0.0, 0
 
@@ -252,13 +257,15 @@ class MultiPlanner:
 
     # ---- whole stateful sequences, sharded by planner ----------------------------------------------------------------
     def submit_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False,
-                        out: np.ndarray | None = None) -> MultiSequenceTicket:
+                        out: np.ndarray | None = None, path_ids=None) -> MultiSequenceTicket:
         """Context.plan_sequence's recording (n_planners planners x T steps, step-major) cut by PLANNER over the contexts
         (planner_slices) and enqueued as one sequence ticket each (fsdp_submit_sequence); contexts that get no planner are
         skipped.  Page-locked arrays are sharded zero-copy — every context reads its planners' segments of the caller's arrays in
         place; a pageable recording is staged ONCE into page-locked buffers that all contexts read.  Results and final_prev rows
         are written by the GPUs into one page-locked array each (``out``: the recording's records; default: blocks of the planner's
-        pool).  The arrays must stay untouched until ``collect``, which returns (results, final_prev, n_replanned)."""
+        pool).  The arrays must stay untouched until ``collect``, which returns (results, final_prev, n_replanned).
+        path_ids: (frames) int32, step-major — each frame's entry of the path table (set_global_path_table) or -1; every context
+        reads its planners' entries of the one array (fsdp_submit_sequence_paths)."""
         import time
 
         t0 = time.perf_counter()
@@ -282,6 +289,7 @@ class MultiPlanner:
             offsets, cones, poses, _ = st.load(offsets, cones[offsets[0] : offsets[-1]], poses, None)
         if init is not None and not _capi.is_pinned(init):
             init = _capi.pinned_copy(init)
+        ids = None if path_ids is None else c0._sequence_ids("submit_sequence", path_ids, n)
         dt = c0.compact_dtype if compact else c0.result_dtype
         if out is None:
             out = self._pool.get(n, dt)
@@ -293,7 +301,7 @@ class MultiPlanner:
             for g, (lo, hi) in enumerate(planner_slices(n_planners, len(self.ctx))):
                 if hi > lo:
                     parts.append((g, self.ctx[g].submit_sequence(offsets, cones, poses, hi - lo, initial_prev=init, compact=compact, planner_lo=lo,
-                                                                 planners_total=n_planners, out=out, final_prev_out=final)))
+                                                                 planners_total=n_planners, out=out, final_prev_out=final, path_ids=ids)))
         except BaseException:
             self._drain(parts)  # (slices already on their GPUs read the arrays and write the blocks)
             raise
@@ -302,9 +310,9 @@ class MultiPlanner:
         self.host_frames += n
         return MultiSequenceTicket(parts, out, final, el)
 
-    def plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False):
+    def plan_sequence(self, cone_offsets, cones_xyt, poses, n_planners: int, initial_prev=None, compact: bool = False, path_ids=None):
         """The bytes of ``Context.plan_sequence`` — (results, final_prev, n_replanned) — with the planners sharded over the contexts."""
-        return self.collect(self.submit_sequence(cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact))
+        return self.collect(self.submit_sequence(cone_offsets, cones_xyt, poses, n_planners, initial_prev, compact, path_ids=path_ids))
 
     # ---- a stream of batches ----------------------------------------------------------------------------------------
     def plan_stream(self, batches, depth: int | None = None, compact: bool = False):

@@ -212,11 +212,12 @@ def replay_history(mission, positions, directions, observations, rows_cap: int, 
 FB_READ_PREVIOUS = 1 | 2 | 4 | 8  # path_fallback bits of the branches that read previous_paths[-1] (include/fsdp.h; the frames fsdp_plan_sequence plans again)
 
 
-def _replay_recordings_in_flight(ctxs, chunked):
+def _replay_recordings_in_flight(ctxs, chunked, chunked_ids=None):
     """Recordings (each a list of consecutive chunks (offsets, cones, poses) of one planner) as sequence tickets
     (fsdp_submit_sequence) over the contexts `ctxs`: as many chunks in flight as the contexts' ticket capacities allow, a
     recording's next chunk submitted — to the context that planned the previous one — as soon as that one is collected, with the
-    path it left (final_prev -> initial_prev).  -> (per recording the list of its chunks' results, frames planned again)"""
+    path it left (final_prev -> initial_prev).  chunked_ids: per recording the chunks' path ids (fsdp_submit_sequence_paths), or
+    None.  -> (per recording the list of its chunks' results, frames planned again)"""
     from ._capi import pinned_empty
 
     results = [[None] * len(chunks) for chunks in chunked]
@@ -227,7 +228,8 @@ def _replay_recordings_in_flight(ctxs, chunked):
     inflight, again = [], 0
 
     def start(r, k, g, prev):
-        inflight.append((g, r, k, ctxs[g].submit_sequence(*chunked[r][k], 1, initial_prev=prev, final_prev_out=finals[r][k % len(finals[r])])))
+        inflight.append((g, r, k, ctxs[g].submit_sequence(*chunked[r][k], 1, initial_prev=prev, final_prev_out=finals[r][k % len(finals[r])],
+                                                          path_ids=None if chunked_ids is None else chunked_ids[r][k])))
         room[g] -= 1
 
     while waiting or inflight:
@@ -244,7 +246,7 @@ def _replay_recordings_in_flight(ctxs, chunked):
 
 
 def replay_stateful_batched(mission, positions, directions, observations, device=None, batch_frames: int = 4096, depth: int = 4,
-                            cache: bool = False, multi=None, recordings=None):
+                            cache: bool = False, multi=None, recordings=None, path_ids=None, path_table=None):
     """The recording as ONE planner sees it — consecutive frames chain through previous_paths[-1] (core_calculate_path.py:
     572-573), which the reference reads in its fallbacks only (:202-203, 218-221, 235-236, 531-536, 564-570) — at the speed
     of a batched replay: the recording cut into consecutive calls of `batch_frames` steps of fsdp_plan_sequence (one planner),
@@ -259,7 +261,21 @@ def replay_stateful_batched(mission, positions, directions, observations, device
     recording its own fresh planner, their chunks kept in flight as sequence tickets up to the ticket capacity (a blocking call
     per chunk leaves the GPU idle between calls); returns a list of result arrays.  multi: a MultiPlanner whose contexts share
     the recordings (several contexts or GPUs; also for one recording, whose chunks then simply run as tickets on the first
-    context).  Neither goes with cache: the cache-on sequence call has no ticket form."""
+    context).  Neither goes with cache: the cache-on sequence call has no ticket form.
+    path_ids: one int32 id per frame of the recording (with recordings: a list of such arrays) — the entry of the path table the
+    frame follows, or -1 for a frame that plans from its cones (fsdp_plan_sequence_paths: a car that maps its track part-way through
+    the log).  path_table: the list of (k, 2) polylines the ids name, set on the contexts the replay creates; a MultiPlanner's
+    contexts keep the table its caller set (MultiPlanner.set_global_path_table) unless one is given here.  Not with cache."""
+    if path_ids is not None and cache:
+        raise ValueError("replay_stateful_batched: path ids do not go with the sorting cache (fsdp_plan_sequence_cached takes none)")
+    ids_of = None
+    if path_ids is not None:
+        per_rec = list(path_ids) if recordings is not None else [path_ids]
+        lens = [len(r[0]) for r in recordings] if recordings is not None else [len(positions)]
+        per_rec = [np.ascontiguousarray(i, dtype=np.int32) for i in per_rec]
+        if [i.shape for i in per_rec] != [(m,) for m in lens]:
+            raise ValueError("replay_stateful_batched: path_ids holds one id per frame of every recording")
+        ids_of = [[i[lo:lo + batch_frames] for lo in range(0, len(i), batch_frames)] for i in per_rec]
     if multi is not None or recordings is not None:
         if cache:
             raise ValueError("replay_stateful_batched: the sorting cache has no ticket form (cache=True goes with one recording and no MultiPlanner)")
@@ -268,6 +284,9 @@ def replay_stateful_batched(mission, positions, directions, observations, device
         many = recordings if recordings is not None else [(positions, directions, observations)]
         own = None if multi is not None else PathPlanner(mission, False, device=device)
         ctxs = multi.ctx if multi is not None else [own._ctx]
+        if path_table is not None:
+            for c in ctxs:
+                c.set_global_path_table(path_table)
         chunked = []
         for pos, dirs, obs in many:
             frames = list(zip(obs, pos, dirs))
@@ -275,14 +294,16 @@ def replay_stateful_batched(mission, positions, directions, observations, device
             chunked.append([(pinned_copy(o, np.int32), pinned_copy(c), pinned_copy(p)) for o, c, p in packed])  # (page-locked: read in place)
         if chunked and chunked[0]:
             for c in ctxs:
-                c.plan_sequence(*chunked[0][0], 1)  # warm-up, like replay_batched's
+                c.plan_sequence(*chunked[0][0], 1, path_ids=None if ids_of is None else ids_of[0][0])  # warm-up, like replay_batched's
         t0 = time.perf_counter()
-        parts, again = _replay_recordings_in_flight(ctxs, chunked)
+        parts, again = _replay_recordings_in_flight(ctxs, chunked, ids_of)
         sec = time.perf_counter() - t0
         res = [np.concatenate(p) if p else np.zeros(0, ctxs[0].result_dtype) for p in parts]
         return (res if recordings is not None else res[0]), sec, again
     planner = PathPlanner(mission, cache, device=device)
     ctx = planner._ctx
+    if path_table is not None:
+        ctx.set_global_path_table(path_table)
     frames = list(zip(observations, positions, directions))
     chunks = [pack_frames(frames[lo:lo + batch_frames]) for lo in range(0, len(frames), batch_frames)]
 
@@ -290,17 +311,20 @@ def replay_stateful_batched(mission, positions, directions, observations, device
         parts, prev, again = [], None, 0
         if cache:
             ctx.sort_cache_reset(1)  # (a fresh planner: the warm-up left an entry)
-        for off, cones, poses in chunks:
+        for j, (off, cones, poses) in enumerate(chunks):
             if cache:
                 res, prev, k = ctx.plan_sequence_cached(off, cones, poses, 1, initial_prev=prev)[:3]
             else:
-                res, prev, k = ctx.plan_sequence(off, cones, poses, 1, initial_prev=prev)
+                res, prev, k = ctx.plan_sequence(off, cones, poses, 1, initial_prev=prev, path_ids=None if ids_of is None else ids_of[0][j])
             parts.append(res)
             again += k
         return parts, again
 
     if chunks:
-        (ctx.plan_sequence_cached if cache else ctx.plan_sequence)(*chunks[0], 1)  # warm-up, like replay_batched's
+        if cache:  # warm-up, like replay_batched's
+            ctx.plan_sequence_cached(*chunks[0], 1)
+        else:
+            ctx.plan_sequence(*chunks[0], 1, path_ids=None if ids_of is None else ids_of[0][0])
     t0 = time.perf_counter()
     parts, again = one_replay()
     sec = time.perf_counter() - t0

@@ -461,8 +461,20 @@ int fsdp_ticket_stream_wait(fsdp_ctx* ctx, long long ticket, void* stream);
  * Routing: a pass with ids runs the path stage's one-kernel form under the rules of any pass (small batches, max_deg < 3), and
  * otherwise the three kernels in the form a context-wide path takes (32 knots per fit, 8 lanes per frame) for ALL of its frames,
  * those with id -1 included; results do not depend on the route.
- * Not offered: path ids for the sequence, cached, ranked, history, stage-level and skidpad calls and for the blocking
- * fsdp_plan_batch* calls. */
+ *   fsdp_plan_sequence_paths[_compact], fsdp_submit_sequence_paths[_compact]
+ *                               fsdp_plan_sequence[_compact] / fsdp_submit_sequence[_compact] plus path_ids, in front of results:
+ *                               int32, host memory, one id per frame of the WHOLE RECORDING, step-major like every other array
+ *                               (n_steps * n_planners entries; n_steps * planners_total for a planner slice, which reads its own
+ *                               planners' entries).  The id may change from step to step: a planner that maps its track part-way
+ *                               through a log goes from -1 to k.  The bytes are those of n_steps fsdp_submit_paths calls in
+ *                               lock-step whose prev_paths rows are chained as fsdp_plan_sequence chains them; n_replanned counts
+ *                               as there.  The ids are gathered into the ticket's own page-locked block (4 bytes per frame) and
+ *                               checked on the way: an id outside [-1, n_paths) is refused (1) before anything is enqueued, and
+ *                               the message names the frame by its index in the recording.  Refused besides, each by its reason:
+ *                               path_ids NULL, everything the three calls above refuse, and everything fsdp_submit_sequence
+ *                               refuses.  The plain sequence calls do not read the table.
+ * Not offered: path ids for fsdp_plan_sequence_cached, for the ranked, history, stage-level and skidpad calls and for
+ * the blocking fsdp_plan_batch* calls; device-memory forms of the sequence calls. */
 int fsdp_set_global_path_table(fsdp_ctx* ctx, const double* xy, const int32_t* path_offsets, int n_paths);
 int fsdp_submit_paths(fsdp_ctx* ctx, int n_frames, const int32_t* cone_offsets, const double* cones_xyt, const double* poses,
                       const double* prev_paths, const int32_t* path_ids, fsdp_frame_result* results, long long* ticket);
@@ -471,6 +483,19 @@ int fsdp_submit_paths_compact(fsdp_ctx* ctx, int n_frames, const int32_t* cone_o
 int fsdp_submit_device_paths(fsdp_ctx* ctx, int n_frames, int cone_capacity, const int32_t* counts, const double* cones, const double* poses,
                              const double* prev_paths, const int32_t* path_ids, double* paths, int32_t* status, double* next_prev,
                              fsdp_compact_result* records, void* after_stream, long long* ticket);
+int fsdp_plan_sequence_paths(fsdp_ctx* ctx, int n_planners, int n_steps, const int32_t* cone_offsets, const double* cones_xyt,
+                             const double* poses, const double* initial_prev, const int32_t* path_ids, fsdp_frame_result* results,
+                             double* final_prev, long long* n_replanned);
+int fsdp_plan_sequence_paths_compact(fsdp_ctx* ctx, int n_planners, int n_steps, const int32_t* cone_offsets, const double* cones_xyt,
+                                     const double* poses, const double* initial_prev, const int32_t* path_ids, fsdp_compact_result* results,
+                                     double* final_prev, long long* n_replanned);
+int fsdp_submit_sequence_paths(fsdp_ctx* ctx, int n_planners, int n_steps, int planner_lo, int planners_total, const int32_t* cone_offsets,
+                               const double* cones_xyt, const double* poses, const double* initial_prev, const int32_t* path_ids,
+                               fsdp_frame_result* results, double* final_prev, long long* n_replanned, long long* ticket);
+int fsdp_submit_sequence_paths_compact(fsdp_ctx* ctx, int n_planners, int n_steps, int planner_lo, int planners_total,
+                                       const int32_t* cone_offsets, const double* cones_xyt, const double* poses, const double* initial_prev,
+                                       const int32_t* path_ids, fsdp_compact_result* results, double* final_prev, long long* n_replanned,
+                                       long long* ticket);
 
 /* The resident form: one batch stays in HBM and is planned again and again (the benchmark's step; a caller that plans the
  * same frames under several global paths / previous paths). */
